@@ -9,6 +9,11 @@ drop_rate 0.2, training mode, fp32 -- the precision in which the 1e-4 logit pari
 One process per GPU.  A step = vsl_forward + vsl_loss + vsl_backward (the region of main_t7.py:103-110) on a batch
 already resident in HBM, plus -- for N > 1 -- ONE RCCL all-reduce of the flat fp32 gradient bucket (weak scaling: the
 per-GPU batch is fixed, losses use the global normalisers).  Rank 0 prints one JSON line.
+
+A plain run does only what that line's headline figure needs: set-up, --warmup steps, the --steps timed steps, the line.  `--full` adds
+the per-kernel HIP-event pass and the `roofline` object, the exchange-free region (N > 1), the CPU baseline and the `shapes` list, and
+times 5 regions of --steps steps (median).  `--dump-outputs DIR` writes what the last timed step returned (inputs are seeded: identical
+from run to run with the same arguments), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -98,6 +103,23 @@ def dtype_line(args):
     return ('f32 in / out and f32 accumulate everywhere; VisualProjection, the conv-block / q,k,v / embedding-linear GEMMs and every weight '
             'gradient as bf16x6 split MFMA (exact 3-way operand split, 6 products: fp32 grade), attention / CQAttention / heads / char-CNN as '
             'fp32-input MFMA')
+
+
+DUMP_BYTES = 64 * 2 ** 20
+
+
+def write_outputs(path, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: each tensor as <path>/<name>.npy in float32.  Above `limit` bytes in all, an array larger than its share keeps a fixed
+    seeded sample of its elements (flattened; the same indices from run to run)."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    share = limit // 4 // len(arrays)
+    big = sum(a.size for a in arrays.values()) * 4 > limit
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if big and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def host_cpu():
@@ -274,15 +296,25 @@ def main():
                     help='distinct synthetic batches resident in HBM, rotated step by step: 10 x 32 MiB of features at the headline shape exceed the '
                          '256 MiB Infinity Cache, so the feature stream of VisualProjection and of its weight gradient really comes from HBM '
                          '(1 = one batch re-used every step, Infinity-Cache resident)')
-    ap.add_argument('--regions', type=int, default=5,
-                    help='the timed region (exactly --steps steps between two barrier + synchronize pairs) is run this many times; `ms_per_step` / `value` '
-                         'are the MEDIAN region, every region is listed in `region_ms` (one driver run is then worth several: box noise exceeds 1 %%)')
+    ap.add_argument('--regions', type=int, default=None,
+                    help='the timed region (exactly --steps steps between two barrier + synchronize pairs) is run this many times (default 1, 5 with '
+                         '--full); `ms_per_step` / `value` are the MEDIAN region, every region is listed in `region_ms`')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the per-kernel HIP-event pass and the `roofline` object, the '
+                         'exchange-free region (N > 1), the CPU baseline and the `shapes` list; default --regions 5')
     ap.add_argument('--no-shapes', action='store_true',
-                    help='skip the `shapes` list (the other BASELINE configs and the bf16 mode at reduced step counts, after the headline regions; N = 1 only)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                    help='with --full: skip the `shapes` list (the other BASELINE configs and the bf16 mode at reduced step counts, after the headline regions; N = 1 only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-optimizer', action='store_true', help='time forward + losses + backward only (A/B runs)')
     ap.add_argument('--profile-all', action='store_true', help='also print the per-kernel HIP-event table to stderr')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned (losses, h_score, start / end logits, gradient bucket, '
+                         'updated parameters) as DIR/<name>.npy in float32')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -335,15 +367,17 @@ def main():
                     clip_norm=configs.clip_norm, engine=eng)
 
     def step(i, skip_exchange=False):
+        """-> what a caller of the step receives: {losses, h_score, start_logits, end_logits} (+ `grads` and `flat`, updated in place)"""
         batch = batches[i % nres]
-        eng.forward(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['v_mask'],
-                    batch['q_mask'], training=True, seed=i, sample_offset=rank * B)
+        h, sl, el = eng.forward(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['v_mask'],
+                                batch['q_mask'], training=True, seed=i, sample_offset=rank * B)
         losses, d_h, d_sl, d_el = eng.loss(batch['s_labels'], batch['e_labels'], batch['h_labels'], 1.0,
                                            configs.highlight_lambda, inv_batch=inv_batch, mask_sum=mask_sum, lazy=True)
+        res = dict(losses=losses, h_score=h, start_logits=sl, end_logits=el)
         skip_exchange = skip_exchange or os.environ.get('VSL_SKIP_ALLREDUCE') == '1'
         if xchg is None and dist is None and not args.no_optimizer:
             backward_exchange_step(eng, None, grads, (d_h, d_sl, d_el), opt)      # one process, as main.train: the update rides in the backward's last launch
-            return losses
+            return res
         if xchg is not None:
             xchg.backward(d_h, d_sl, d_el, grads, skip_exchange=skip_exchange)    # flat fp32 bucket, summed (losses carry 1/B_global)
         else:
@@ -352,22 +386,26 @@ def main():
                 dist.all_reduce(grads)
         if not args.no_optimizer:
             opt.step(grads, from_backward=xchg is None and dist is None)      # one process: the bucket is what the backward left
-        return losses
+        return res
 
     for i in range(args.warmup):
         step(i)
-    # find the dominant kernel group (untimed pass with every launch bracketed by HIP events)
-    eng.profile_select('*')
+    # the step after the warm-up: under --full (or --profile-all) an untimed pass with every launch bracketed by HIP events that finds the dominant
+    # kernel group; a plain run takes the same step unprofiled, so that both time the same steps on the same weights
+    profile = args.full or args.profile_all
+    if profile:
+        eng.profile_select('*')
     step(args.warmup)
-    torch.cuda.synchronize()
-    table = eng.profile_read()
-    dominant = max(table, key=lambda k: table[k][0])
-    if args.profile_all and rank == 0:
-        tot = sum(v[0] for v in table.values())
-        for k, (ms, n) in sorted(table.items(), key=lambda kv: -kv[1][0]):
-            print('%-18s %8.1f us  %3d launches  %5.1f%%' % (k, ms * 1e3, n, 100 * ms / tot), file=sys.stderr)
-    # timed region: events around the dominant kernel group and the one HBM-streaming kernel (VisualProjection)
-    eng.profile_select(dominant if dominant == 'vproj_fwd' else dominant + ',vproj_fwd')
+    if profile:
+        torch.cuda.synchronize()
+        table = eng.profile_read()
+        dominant = max(table, key=lambda k: table[k][0])
+        if args.profile_all and rank == 0:
+            tot = sum(v[0] for v in table.values())
+            for k, (ms, n) in sorted(table.items(), key=lambda kv: -kv[1][0]):
+                print('%-18s %8.1f us  %3d launches  %5.1f%%' % (k, ms * 1e3, n, 100 * ms / tot), file=sys.stderr)
+        # timed region (--full only): events around the dominant kernel group and the one HBM-streaming kernel (VisualProjection)
+        eng.profile_select((dominant if dominant == 'vproj_fwd' else dominant + ',vproj_fwd') if args.full else None)
 
     def sync():
         torch.cuda.synchronize()
@@ -380,7 +418,7 @@ def main():
         sync()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            losses = step(args.warmup + 1 + rg * args.steps + i)
+            last = step(args.warmup + 1 + rg * args.steps + i)
         sync()
         dt = time.perf_counter() - t0
         if dist is not None:
@@ -390,13 +428,16 @@ def main():
         region_dt.append(dt)
     dt = sorted(region_dt)[(len(region_dt) - 1) // 2]          # median (lower middle for an even count)
     nreg = len(region_dt)
-    ptab = eng.profile_read()
-    kt = (ptab[dominant][0] / nreg, ptab[dominant][1] // nreg)     # events accumulated over all regions -> per region
-    kvp = ptab.get('vproj_fwd')
-    eng.profile_select(None)
+    if args.full:
+        ptab = eng.profile_read()
+        kt = (ptab[dominant][0] / nreg, ptab[dominant][1] // nreg)     # events accumulated over all regions -> per region
+        kvp = ptab.get('vproj_fwd')
+        eng.profile_select(None)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict(last, grads=grads, params=flat))
     # the exchange's exposed cost: the same timed region once more without it (every rank runs it, so the barriers still pair up)
     dt_nox = None
-    if dist is not None:
+    if dist is not None and args.full:
         sync()
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -406,7 +447,7 @@ def main():
         tmax = torch.tensor([dt_nox], device='cuda', dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt_nox = float(tmax.item())
-    loss_val = float(losses[2].item())
+    loss_val = float(last['losses'][2].item())
     if not (loss_val == loss_val) or abs(loss_val) > 1e6:
         raise SystemExit('non-finite loss in the timed region: %r' % loss_val)
 
@@ -414,55 +455,56 @@ def main():
         ms_step = dt / args.steps * 1e3
         value = B * world * args.steps / dt
         fwd, fb = alg_flops_per_pair(T, Dv, Lq, Lc, predictor=args.predictor)
-        work = kernel_work(dominant, B, T, Dv, Lq)
-        k_s = kt[0] * 1e-3 / args.steps                      # seconds of this kernel group per step
-        # ---- roofline of the dominant kernel group (largest HIP-event time).  LIVE half: algorithmic flops / bytes per launch
-        #      over the average launch duration between HIP events recorded on the launch stream during the timed region
-        #      (a side-stream kernel's event time includes the wait for CUs the main chain holds).  STATIC half (`rocprof`,
-        #      `traffic`): the committed rocprofv3 summary of the same command, profiles/<tag>_profile.json.
-        n_launch = max(1, kt[1] // args.steps)
-        roof = {'kernel': dominant, 'launches_per_step': n_launch, 'ms_per_step': round(k_s * 1e3, 4),
-                'event_us_per_launch': round(k_s * 1e6 / n_launch, 2)}
-        if work:
-            t_m, t_h = work[0] / PEAK_MFMA_F32, work[1] / PEAK_HBM
-            if t_m >= t_h:
-                roof.update(bound='mfma', achieved=round(work[0] / k_s / 1e12, 3), peak=PEAK_MFMA_F32 / 1e12, unit='TFLOP/s')
-            else:
-                roof.update(bound='hbm', achieved=round(work[1] / k_s / 1e9, 1), peak=PEAK_HBM / 1e9, unit='GB/s')
-            roof['frac'] = round(roof['achieved'] / roof['peak'], 4)
-            roof['alg_flops_per_launch'] = int(work[0] / n_launch)
-            roof['alg_bytes_per_launch'] = int(work[1] / n_launch)
-        roof['traffic'] = None
-        try:
-            prof = json.load(open(os.path.join(ROOT, 'profiles', PROFILE_JSON)))
-            pg = prof['groups'].get(dominant)
-            if pg and [B, T, Dv, Lq] == prof['shape'] and args.predictor == 'transformer':
-                rp = {'avg_us': pg['avg_us'], 'launches_per_step': pg['launches_per_step'], 'source': prof['sources'][0]}
-                if work:
-                    per = work[0] / n_launch if roof.get('bound') == 'mfma' else work[1] / n_launch
-                    peak = PEAK_MFMA_F32 if roof.get('bound') == 'mfma' else PEAK_HBM
-                    rp['frac'] = round(per / (pg['avg_us'] * 1e-6) / peak, 4)
-                roof['rocprof'] = rp                          # static: kernel duration seen by rocprofv3 --kernel-trace
-                if 'traffic_bytes' in pg:
-                    roof['traffic'] = pg['traffic_bytes']
-                    roof['traffic_source'] = ('static, from %s + %s (separate rocprofv3 --pmc passes, FETCH_SIZE x2 + WRITE_SIZE, per launch over %d '
-                                              'launches)' % (prof['sources'][1], prof['sources'][2], pg['launches_counted']))
-        except Exception:
-            pass
-        roof['step_mfma_frac'] = round(fb * value / world / PEAK_MFMA_F32, 4)   # whole step vs the fp32 MFMA roof, per GPU
-        if kvp and kvp[1]:
-            # VisualProjection: the only kernel that streams the (B, T, Dv) feature tensor: algorithmic bytes (features in,
-            # projection out) over its live event time.  With --resident-batches >= 9 the features of a step were last touched > 256 MiB ago
-            vp_us = kvp[0] * 1e3 / kvp[1]
-            vp_bytes = (2 if args.dtype == 'bf16' else 4) * B * T * Dv + 4 * B * T * 128
-            roof['vproj_event_us'] = round(vp_us, 2)
-            roof['vproj_hbm_gbps'] = round(vp_bytes / (vp_us * 1e-6) / 1e9, 1)
-            roof['vproj_hbm_frac'] = round(vp_bytes / (vp_us * 1e-6) / PEAK_HBM, 4)
-            roof['vproj_features'] = ('%d resident batches = %.0f MiB of features, rotated: %s' %
-                                      (nres, feat_mib, 'streamed from HBM (> 256 MiB Infinity Cache)' if feat_mib > 256 else 'Infinity-Cache resident'))
-        # the split kernels reach fp32 grade with 6 bf16 products per product: the same launch against the dense bf16 peak
-        if work and dominant in ('wgrad', 'convblock_fwd', 'convblock_bwd', 'vproj_fwd'):
-            roof['bf16x6_frac_of_bf16_peak'] = round(6 * work[0] / k_s / PEAK_MFMA_BF16, 4)
+        if args.full:
+            work = kernel_work(dominant, B, T, Dv, Lq)
+            k_s = kt[0] * 1e-3 / args.steps                      # seconds of this kernel group per step
+            # ---- roofline of the dominant kernel group (largest HIP-event time).  LIVE half: algorithmic flops / bytes per launch
+            #      over the average launch duration between HIP events recorded on the launch stream during the timed region
+            #      (a side-stream kernel's event time includes the wait for CUs the main chain holds).  STATIC half (`rocprof`,
+            #      `traffic`): the committed rocprofv3 summary of the same command, profiles/<tag>_profile.json.
+            n_launch = max(1, kt[1] // args.steps)
+            roof = {'kernel': dominant, 'launches_per_step': n_launch, 'ms_per_step': round(k_s * 1e3, 4),
+                    'event_us_per_launch': round(k_s * 1e6 / n_launch, 2)}
+            if work:
+                t_m, t_h = work[0] / PEAK_MFMA_F32, work[1] / PEAK_HBM
+                if t_m >= t_h:
+                    roof.update(bound='mfma', achieved=round(work[0] / k_s / 1e12, 3), peak=PEAK_MFMA_F32 / 1e12, unit='TFLOP/s')
+                else:
+                    roof.update(bound='hbm', achieved=round(work[1] / k_s / 1e9, 1), peak=PEAK_HBM / 1e9, unit='GB/s')
+                roof['frac'] = round(roof['achieved'] / roof['peak'], 4)
+                roof['alg_flops_per_launch'] = int(work[0] / n_launch)
+                roof['alg_bytes_per_launch'] = int(work[1] / n_launch)
+            roof['traffic'] = None
+            try:
+                prof = json.load(open(os.path.join(ROOT, 'profiles', PROFILE_JSON)))
+                pg = prof['groups'].get(dominant)
+                if pg and [B, T, Dv, Lq] == prof['shape'] and args.predictor == 'transformer':
+                    rp = {'avg_us': pg['avg_us'], 'launches_per_step': pg['launches_per_step'], 'source': prof['sources'][0]}
+                    if work:
+                        per = work[0] / n_launch if roof.get('bound') == 'mfma' else work[1] / n_launch
+                        peak = PEAK_MFMA_F32 if roof.get('bound') == 'mfma' else PEAK_HBM
+                        rp['frac'] = round(per / (pg['avg_us'] * 1e-6) / peak, 4)
+                    roof['rocprof'] = rp                          # static: kernel duration seen by rocprofv3 --kernel-trace
+                    if 'traffic_bytes' in pg:
+                        roof['traffic'] = pg['traffic_bytes']
+                        roof['traffic_source'] = ('static, from %s + %s (separate rocprofv3 --pmc passes, FETCH_SIZE x2 + WRITE_SIZE, per launch over %d '
+                                                  'launches)' % (prof['sources'][1], prof['sources'][2], pg['launches_counted']))
+            except Exception:
+                pass
+            roof['step_mfma_frac'] = round(fb * value / world / PEAK_MFMA_F32, 4)   # whole step vs the fp32 MFMA roof, per GPU
+            if kvp and kvp[1]:
+                # VisualProjection: the only kernel that streams the (B, T, Dv) feature tensor: algorithmic bytes (features in,
+                # projection out) over its live event time.  With --resident-batches >= 9 the features of a step were last touched > 256 MiB ago
+                vp_us = kvp[0] * 1e3 / kvp[1]
+                vp_bytes = (2 if args.dtype == 'bf16' else 4) * B * T * Dv + 4 * B * T * 128
+                roof['vproj_event_us'] = round(vp_us, 2)
+                roof['vproj_hbm_gbps'] = round(vp_bytes / (vp_us * 1e-6) / 1e9, 1)
+                roof['vproj_hbm_frac'] = round(vp_bytes / (vp_us * 1e-6) / PEAK_HBM, 4)
+                roof['vproj_features'] = ('%d resident batches = %.0f MiB of features, rotated: %s' %
+                                          (nres, feat_mib, 'streamed from HBM (> 256 MiB Infinity Cache)' if feat_mib > 256 else 'Infinity-Cache resident'))
+            # the split kernels reach fp32 grade with 6 bf16 products per product: the same launch against the dense bf16 peak
+            if work and dominant in ('wgrad', 'convblock_fwd', 'convblock_bwd', 'vproj_fwd'):
+                roof['bf16x6_frac_of_bf16_peak'] = round(6 * work[0] / k_s / PEAK_MFMA_BF16, 4)
         out = {'metric': '(video,query) pairs/sec fwd+bwd, Charades I3D T=128 D=1024', 'value': round(value, 1),
                'unit': 'pairs/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
                'ms_per_step': round(ms_step, 4), 'regions': nreg, 'region_ms': [round(d / args.steps * 1e3, 4) for d in region_dt],
@@ -477,22 +519,24 @@ def main():
                                          ' + RCCL all-reduce of the flat grad bucket' if world > 1 else '',
                                          '' if args.no_optimizer else ' + clip_grad_norm(1.0) + AdamW update (fused HIP)'),
                           'global_batch': B * world, 'parallelism': 'dp%d' % world,
-                          'alg_mflop_per_pair': round(fb / 1e6, 1), 'loss': round(loss_val, 5)},
-               'roofline': roof}
+                          'alg_mflop_per_pair': round(fb / 1e6, 1), 'loss': round(loss_val, 5)}}
+        if args.full:
+            out['roofline'] = roof
         out['rccl_ranks'] = world if dist is not None else 0          # 0: no process group (plain single-process run)
-        if dist is not None:
+        if dt_nox is not None:
             ms_nox = dt_nox / args.steps * 1e3
             out['step_without_allreduce_ms'] = round(ms_nox, 4)
             out['allreduce_us'] = round((ms_step - ms_nox) * 1e3, 1)    # exposed cost of the exchange per step (can be ~0: overlapped)
+        if dist is not None:
             out['allreduce'] = ('two calls: grads[%d:] (predictor block) on a side stream behind vsl_io.early_grads_event, grads[:%d] behind the '
                                 'backward' % (xchg.split, xchg.split)) if xchg is not None else 'one call behind the backward'
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(configs, T, Lq, Lc)
             try:        # port-vs-reference ratio measured in the build container (tools/calibrate_cpu_baseline.py): the reference cannot travel
                 out['cpu_baseline']['calibration'] = json.load(open(os.path.join(ROOT, 'profiles', 'r04_cpu_calibration.json')))
             except Exception:
                 out['cpu_baseline']['calibration'] = None
-        if world == 1 and dist is None and not args.no_shapes and workload_name(args).startswith('configs[1]') and args.dtype == 'f32':
+        if args.full and world == 1 and dist is None and not args.no_shapes and workload_name(args).startswith('configs[1]') and args.dtype == 'f32':
             del model, batches, opt, eng, flat, grads             # the headline's workspace goes back to the allocator first
             torch.cuda.empty_cache()
             out['shapes'] = other_shapes(args)

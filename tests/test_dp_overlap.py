@@ -122,7 +122,8 @@ def _bench(extra_env, *args):
     env = dict(os.environ)
     env.update(extra_env)
     steps = [] if '--steps' in args else ['--steps', '6']
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *steps, '--warmup', '2', '--regions', '1', '--no-shapes', '--no-cpu-baseline', *args],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *steps, '--warmup', '2', '--regions', '1', '--full', '--no-shapes',
+                        '--no-cpu-baseline', *args],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads(r.stdout.strip().splitlines()[-1])

@@ -8,7 +8,7 @@ R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-shapes --regions 1"
+BENCH="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-shapes --regions 1"
 rocprofv3 --kernel-trace --stats -d $O/stats -o s -- $BENCH > $O/stats_bench.json 2> $O/stats.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -o f -- $BENCH > /dev/null 2> $O/fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write -o w -- $BENCH > /dev/null 2> $O/write.err
@@ -22,11 +22,11 @@ python tools/rocpd_pmc.py $WDB > $O/${TAG}_pmc_write_size.txt
 python tools/rocpd_mfma.py $(find $O/mfma -name "*.db" | head -1) > $O/${TAG}_pmc_mfma_busy.txt
 python tools/make_profile_json.py $SDB $FDB $WDB $O/${TAG}_profile.json $TAG
 cp $O/${TAG}_profile.json profiles/r06_profile.json
-python bench.py > $O/${TAG}_bench.json 2> $O/bench.err
-python bench.py --steps 30 --warmup 10 --no-cpu-baseline --profile-all 2> $O/${TAG}_hip_event_table.txt > /dev/null
-python bench.py --steps 30 --warmup 10 --no-cpu-baseline --dtype bf16 > $O/${TAG}_bench_bf16_mode.json 2>/dev/null
-python bench.py --steps 30 --warmup 10 --no-cpu-baseline --predictor rnn --batch 16 > $O/${TAG}_bench_rnn_b16_configs0.json 2>/dev/null
-python bench.py --steps 30 --warmup 10 --no-cpu-baseline --predictor rnn --batch 64 > $O/${TAG}_bench_rnn_b64.json 2>/dev/null
+python bench.py --full > $O/${TAG}_bench.json 2> $O/bench.err
+python bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --profile-all 2> $O/${TAG}_hip_event_table.txt > /dev/null
+python bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --dtype bf16 > $O/${TAG}_bench_bf16_mode.json 2>/dev/null
+python bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --predictor rnn --batch 16 > $O/${TAG}_bench_rnn_b16_configs0.json 2>/dev/null
+python bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --predictor rnn --batch 64 > $O/${TAG}_bench_rnn_b64.json 2>/dev/null
 bash tools/bench_shapes.sh > $O/${TAG}_bench_shapes.txt 2>/dev/null
 # round 6: the step's critical-path ledger from HIP events (no profiler attached), batch lengths off the 32-row tile, the row-tile query launches as A/B
 python tools/critical_path.py --out $O/${TAG}_critical_path.txt > /dev/null 2> $O/critical_path.err
