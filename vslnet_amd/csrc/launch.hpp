@@ -344,6 +344,14 @@ void launch_attn_bwd(const float* Q, const float* K, const float* V, const float
                      const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
                      Drop d3, hipStream_t s);
 int attn_bwd_dq_slabs(int L);             // L > 256: dQ is written as this many (R, 128) partial slabs (one per 256-key block); k_qkv_bwd adds them
+// the attention core of num_heads 4 / 16 (head sizes 32 / 8; kernels_attn_hd.hip), every L: the contracts of launch_attn_fwd / launch_attn_bwd,
+// dQ as attn_bwd_dq_slabs(L) partial slabs
+void launch_attn_hd_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
+                        int L, int H, int b_off, Drop d2, hipStream_t s);
+void launch_attn_hd_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
+                        const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
+                        Drop d3, hipStream_t s);
+inline bool attn_heads_supported(int H) { return H == 4 || H == 8 || H == 16; }
 void launch_qkv_bwd(const float* dQ, const float* dK, const float* dV, const float* x, const float* dr,
                     const float* ln_g, const uint16_t* WT3 /* split pack of the (384, 128) operand */, float* dx, float* p_lng, float* p_lnb, int R,
                     Drop d1, hipStream_t s, int dq_slabs = 1);
