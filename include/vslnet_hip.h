@@ -44,7 +44,7 @@ typedef struct {
 /* One forward / backward problem instance.  Replaces the argument list of VSLNet.forward (VSLNet_t7.py:52) plus
  * the tensors autograd keeps alive between forward and `total_loss.backward()` (main_t7.py:103-110). */
 typedef struct {
-    int32_t B, T, Lq, Lc;          /* batch, padded clips, padded query words, padded chars per word              */
+    int32_t B, T, Lq, Lc;          /* batch, padded clips (T <= 4096), padded query words, padded chars per word  */
     /* parameters */
     const float* params;           /* flat trainable parameter bucket, layout = vsl_param_info()                   */
     const float* pad_vec;          /* embedding_net.word_emb.pad_vec   (1, word_dim)  frozen                       */

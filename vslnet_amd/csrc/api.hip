@@ -908,13 +908,17 @@ void enc_bwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
         const AttnOutBwdArgs ao = attn_out_bwd_args(c, P, K, w, dy, dy2, app);
         LAUNCH("attn_out_bwd", launch_attn_out_bwd(ao.dy, ao.dy2, ao.r_in, ao.ln_g, ao.WTpack, ao.g_o, ao.dr, ao.p_lng, ao.p_lnb, R, ao.d4, ao.d5, c.s));
     }
-    if (H != 8)      // head sizes 32 / 8: kernels_attn_hd.hip (dQ in attn_bwd_dq_slabs(L) slabs as well)
+    if (attn_dq_query_major(L))      // L > ATTN_SLAB_MAX_L, every head count: dK / dV key-major + dQ query-major into slab 0 (kernels_attn_long.hip)
+        LAUNCH("attn_bwd", launch_attn_bwd_any(c.W(w.q), c.W(w.k), c.W(w.v), c.W(w.att), c.W(t.dr), c.W(w.lse), mask, c.W(t.dq), c.W(t.dk),
+                                   c.W(t.dv), Bn, L, H, 0, c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.s));
+    else if (H != 8)      // head sizes 32 / 8: kernels_attn_hd.hip (dQ in attn_bwd_dq_slabs(L) slabs as well)
         LAUNCH("attn_bwd", launch_attn_hd_bwd(c.W(w.q), c.W(w.k), c.W(w.v), c.W(w.att), c.W(t.dr), c.W(w.lse), mask, c.W(t.dq), c.W(t.dk),
                                   c.W(t.dv), Bn, L, H, 0, c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.s));
     else
         LAUNCH("attn_bwd", launch_attn_bwd(c.W(w.q), c.W(w.k), c.W(w.v), c.W(w.att), c.W(t.dr), c.W(w.lse), mask, c.W(t.dq), c.W(t.dk),
                                c.W(t.dv), Bn, L, H, 0, c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.s));
-    // whole tiles / sample tiles (and one dQ slab): the conv block's backward kernel computes its own incoming gradient from dq / dk / dv (CbBwdArgs::qk)
+    // whole tiles / sample tiles (and one dQ slab): the conv block's backward kernel computes its own incoming gradient from dq / dk / dv (CbBwdArgs::qk).
+    // The gate stays on the key-major slab count: L > 256 never fuses, the one-slab dQ of L > ATTN_SLAB_MAX_L included (k_qkv_bwd adds nothing there)
     static const bool fuse_on = !(getenv("VSL_QKV_FUSED") && getenv("VSL_QKV_FUSED")[0] == '0');
     const bool fuse_qkv = fuse_on && convblock_bwd_hosts_qkv(R, L) && attn_bwd_dq_slabs(L) == 1;
     const int nsl1 = fuse_qkv ? convblock_slabs(R, L) : ntiles;
@@ -922,7 +926,7 @@ void enc_bwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
     float* p_ln1b = c.slab(P.ln1b, D, nsl1);
     if (!fuse_qkv)
         LAUNCH("qkv_bwd", launch_qkv_bwd(c.W(t.dq), c.W(t.dk), c.W(t.dv), c.W(w.y[3]), c.W(t.dr), c.P(P.ln1g), reinterpret_cast<const uint16_t*>(c.PK(K.qkv_t3)),
-                              c.W(t.ga), p_ln1g, p_ln1b, R, c.drop(app * 16 + 4), c.s, attn_bwd_dq_slabs(L)));
+                              c.W(t.ga), p_ln1g, p_ln1b, R, c.drop(app * 16 + 4), c.s, attn_dq_slabs(L)));
     {   // out_layer + fused q/k/v weight gradients: every input exists now -> side stream, beside the conv chain
         WgradBatch wb;
         memset(&wb, 0, sizeof wb);
@@ -1435,7 +1439,7 @@ int build_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
     if (T > cf.max_pos_len || Lq > cf.max_pos_len)
         return fail("sequence length (T=%d, Lq=%d) exceeds max_pos_len=%d: the positional table has no such row "
                     "(layers_t7.py:196 -- IndexError in the reference)", T, Lq, cf.max_pos_len);
-    if (T > MAX_L) return fail("T=%d > %d clips not supported by the LDS-resident attention kernels", T, MAX_L);
+    if (T > MAX_L) return fail("T=%d > %d clips not supported by the attention kernels", T, MAX_L);
     if ((int64_t)B * std::max(T, Lq) * D * 4 >= (int64_t(1) << 31))     // (the conv-block kernels address (R, 128) tensors with 32-bit byte offsets; 0x80000000 marks a dropped lane)
         return fail("B*T = %lld rows: an (R, 128) fp32 activation must stay below 2 GiB for the 32-bit buffer offsets of the conv-block kernels", (long long)B * std::max(T, Lq));
     if (Lq > MAX_LQ) return fail("Lq=%d > %d query words: the CQAttention kernels keep the whole query of a sample in LDS "
@@ -1476,7 +1480,7 @@ int build_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
     for (int ap = 0; ap < (rnn ? 2 : 4); ++ap) {
         const int64_t Ra = ap == 1 ? Rq : R;
         EncTmp& t = p->tmp[ap];
-        t.dr = al(Ra * D); t.dq = al(Ra * D * attn_bwd_dq_slabs(ap == 1 ? Lq : T)); t.dk = al(Ra * D); t.dv = al(Ra * D);
+        t.dr = al(Ra * D); t.dq = al(Ra * D * attn_dq_slabs(ap == 1 ? Lq : T)); t.dk = al(Ra * D); t.dv = al(Ra * D);
         t.go = al(Ra * D);
         for (int i = 0; i < 4; ++i) t.gz[i] = al(Ra * D);
         t.ga = al(Ra * D);

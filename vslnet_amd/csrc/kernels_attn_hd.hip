@@ -214,7 +214,8 @@ constexpr int AHB_KB = 256, AHB_QP = 64, AHB_DSP = AHB_KB + 4;
 template <int HDV> constexpr size_t attn_hd_bwd_lds() {
     return (size_t)(AHB_KB * AttnHd<HDV>::KST + AHB_KB + AHB_QP * AHB_DSP + 2 * AHB_QP * AttnHd<HDV>::KST + 2 * AHB_QP) * sizeof(float);
 }
-template <int HDV, bool PAIR>
+// DQ = false (L > ATTN_SLAB_MAX_L): phase 1 alone -- dK / dV, no dS image, no dQ partials (k_attn_dq computes dQ query-major)
+template <int HDV, bool PAIR, bool DQ = true>
 __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ Q, const float* __restrict__ K,
                                                       const float* __restrict__ V, const float* __restrict__ att,
                                                       const float* __restrict__ dr, const float* __restrict__ lse,
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ 
                     const float m2 = m2v[r];
                     const float pd = p * m2;
                     const float ds = p * (dp[r] * m2 - Ds[ql]) * scale;
-                    dSs[ql * AHB_DSP + keyl] = ds;
+                    if (DQ) dSs[ql * AHB_DSP + keyl] = ds;
                     // dV^T[dd][key] += dA[q][dd] P[q][key] ; dK^T[dd][key] += Q[q][dd] dS[q][key]   (A[i = dd][k = query])
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
@@ -354,6 +355,7 @@ __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ 
                 }
             }
         }
+        if constexpr (DQ) {
         __syncthreads();                        // dS of this pass complete
         const int qt2 = qb + 16 * (w & 3), kres = w >> 2;
         f32x4 dqs[NT];
@@ -402,6 +404,7 @@ __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ 
                                     ((dqs[j][2] + p1.z) + p2.z) + p3.z, ((dqs[j][3] + p1.w) + p2.w) + p3.w);
             }
         }
+        }
         __syncthreads();                        // dS buffer, Qs / As / Ls / Ds free for the next pass
     }
     if (has_keys && k0 + keyl < L) {
@@ -415,19 +418,28 @@ __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ 
     }
 }
 
-template <int HDV, bool PAIR> static void attn_hd_bwd_go(const float* Q, const float* K, const float* V, const float* att, const float* dr,
+template <int HDV, bool PAIR, bool DQ = true> static void attn_hd_bwd_go(const float* Q, const float* K, const float* V, const float* att, const float* dr,
                                                          const float* lse, const float* mask, float* dQ, float* dK, float* dV, int B, int L,
                                                          int H, int b_off, Drop d2, Drop d3, hipStream_t s) {
     static size_t ok = 0;
     const int Lp = (L + 15) & ~15;
-    ensure_dynamic_lds((const void*)k_attn_hd_bwd<HDV, PAIR>, attn_hd_bwd_lds<HDV>(), ok, "k_attn_hd_bwd");
-    VSL_LAUNCH((k_attn_hd_bwd<HDV, PAIR>), dim3((Lp + AHB_KB - 1) / AHB_KB, H, B), dim3(1024), attn_hd_bwd_lds<HDV>(), s, Q, K, V, att, dr, lse,
+    ensure_dynamic_lds((const void*)k_attn_hd_bwd<HDV, PAIR, DQ>, attn_hd_bwd_lds<HDV>(), ok, "k_attn_hd_bwd");
+    VSL_LAUNCH((k_attn_hd_bwd<HDV, PAIR, DQ>), dim3((Lp + AHB_KB - 1) / AHB_KB, H, B), dim3(1024), attn_hd_bwd_lds<HDV>(), s, Q, K, V, att, dr, lse,
                mask, dQ, dK, dV, L, H, b_off, (size_t)B * L * D, d2, d3);
 }
 void launch_attn_hd_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
                         const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                        Drop d3, hipStream_t s) {
+                        Drop d3, hipStream_t s, bool dq) {
     const bool pair = L > 256;
+    if (!dq) {      // L > ATTN_SLAB_MAX_L (key pairs): dK / dV per key block, dQ from k_attn_dq (launch_attn_bwd_any)
+        if (H == 4) attn_hd_bwd_go<32, true, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
+        else if (H == 16) attn_hd_bwd_go<8, true, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
+        else {
+            fprintf(stderr, "launch_attn_hd_bwd: num_heads=%d has no attention kernel\n", H);
+            abort();
+        }
+        return;
+    }
     if (H == 4) {
         if (pair) attn_hd_bwd_go<32, true>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
         else attn_hd_bwd_go<32, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);

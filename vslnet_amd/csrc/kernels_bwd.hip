@@ -586,7 +586,8 @@ constexpr int ABL_KB = 256;
 constexpr size_t abl_lds() { return (size_t)(2 * ABL_KB * AB_KST + ABL_KB + AB_QP * (ABL_KB + 4) + 2 * AB_QP * AB_KST + 2 * AB_QP) * sizeof(float) + (size_t)2 * 3 * AB_QP * 16 * sizeof(uint16_t); }
 // PAIR: the probability site's masks are keyed by key PAIRS (the forward of L > 256, k_attn_fwd) ; false: one hash per element (the forward of
 // L <= 256, k_attn_block_fwd) -- the kernel then serves 128 < L <= 256 as ONE key block (launch_attn_bwd)
-template <bool PAIR>
+// DQ = false (L > ATTN_SLAB_MAX_L): phase 1 alone -- dK / dV, no dS image, no dQ partials (k_attn_dq computes dQ query-major)
+template <bool PAIR, bool DQ = true>
 __global__ __launch_bounds__(1024) void k_attn_bwd_long(const float* __restrict__ Q, const float* __restrict__ K,
                                                         const float* __restrict__ V, const float* __restrict__ att,
                                                         const float* __restrict__ dr, const float* __restrict__ lse,
@@ -746,12 +747,13 @@ __global__ __launch_bounds__(1024) void k_attn_bwd_long(const float* __restrict_
                     const float m2 = m2v[r];
                     const float pd = p * m2;
                     const float ds = p * (dp[r] * m2 - Ds[ql]) * scale;
-                    dSs[ql * AB_DSP + keyl] = ds;
+                    if (DQ) dSs[ql * AB_DSP + keyl] = ds;
                     dv = __builtin_amdgcn_mfma_f32_16x16x4f32(As[ql * AB_KST + ki], pd, dv, 0, 0, 0);
                     dk = __builtin_amdgcn_mfma_f32_16x16x4f32(Qs[ql * AB_KST + ki], ds, dk, 0, 0, 0);
                 }
             }
         }
+        if constexpr (DQ) {
         __syncthreads();                        // dS of this pass complete
         const int qt2 = qb + 16 * (w & 3), kr = w >> 2;
         f32x4 dqs = {0.f, 0.f, 0.f, 0.f};
@@ -783,6 +785,7 @@ __global__ __launch_bounds__(1024) void k_attn_bwd_long(const float* __restrict_
                     make_float4(((dqs[0] + p1.x) + p2.x) + p3.x, ((dqs[1] + p1.y) + p2.y) + p3.y,
                                 ((dqs[2] + p1.z) + p2.z) + p3.z, ((dqs[3] + p1.w) + p2.w) + p3.w);
         }
+        }
         __syncthreads();                        // dS buffer, Qs / As / Ls / Ds free for the next pass
     }
     if (has_keys && k0 + keyl < L) {
@@ -794,8 +797,15 @@ __global__ __launch_bounds__(1024) void k_attn_bwd_long(const float* __restrict_
 int attn_bwd_dq_slabs(int L) { const int Lp = (L + 15) & ~15; return Lp <= 256 ? 1 : (Lp + ABL_KB - 1) / ABL_KB; }
 void launch_attn_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
                      const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                     Drop d3, hipStream_t s) {
+                     Drop d3, hipStream_t s, bool dq) {
     const int Lp = (L + 15) & ~15;
+    if (!dq) {      // L > ATTN_SLAB_MAX_L: dK / dV per key block, dQ from k_attn_dq (launch_attn_bwd_any)
+        static size_t okn = 0;
+        ensure_dynamic_lds((const void*)k_attn_bwd_long<true, false>, abl_lds(), okn, "k_attn_bwd_long<true, false>");
+        VSL_LAUNCH((k_attn_bwd_long<true, false>), dim3((Lp + ABL_KB - 1) / ABL_KB, H, B), dim3(1024), abl_lds(), s, Q, K, V, att, dr, lse, mask,
+                   dQ, dK, dV, L, H, b_off, (size_t)B * L * D, d2, d3);
+        return;
+    }
     if (Lp <= 128) {
         static size_t ok128 = 0;
         ensure_dynamic_lds((const void*)k_attn_bwd_fused<128>, ab_lds<128>(), ok128, "k_attn_bwd_fused<128>");

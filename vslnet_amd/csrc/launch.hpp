@@ -340,9 +340,10 @@ void launch_rnn_bwd(const RnnBwdArgs& a, hipStream_t s);      // one image = W_h
 void launch_wgrad(const WgradBatch& wb, hipStream_t s);     // kernels_wgrad.hip
 void launch_attn_out_bwd(const float* dy, const float* dy2, const float* r, const float* ln_g, const float* WTpack, float* g_o,
                          float* dr, float* p_lng, float* p_lnb, int R, Drop d4, Drop d5, hipStream_t s);
+// dq = false (L > 256 only): dK / dV alone, the key blocks write no dQ partials (k_attn_dq computes dQ: launch_attn_bwd_any)
 void launch_attn_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
                      const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                     Drop d3, hipStream_t s);
+                     Drop d3, hipStream_t s, bool dq = true);
 int attn_bwd_dq_slabs(int L);             // L > 256: dQ is written as this many (R, 128) partial slabs (one per 256-key block); k_qkv_bwd adds them
 // the attention core of num_heads 4 / 16 (head sizes 32 / 8; kernels_attn_hd.hip), every L: the contracts of launch_attn_fwd / launch_attn_bwd,
 // dQ as attn_bwd_dq_slabs(L) partial slabs
@@ -350,7 +351,14 @@ void launch_attn_hd_fwd(const float* Q, const float* K, const float* V, const fl
                         int L, int H, int b_off, Drop d2, hipStream_t s);
 void launch_attn_hd_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
                         const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                        Drop d3, hipStream_t s);
+                        Drop d3, hipStream_t s, bool dq = true);
+// the attention backward of every head count (kernels_attn_long.hip): L <= ATTN_SLAB_MAX_L (or VSL_ATTN_DQ_SLABS=1) = the launchers above;
+// longer = their dK / dV-only instantiations + k_attn_dq, which writes the complete dQ into slab 0.  attn_dq_slabs(L): the slabs k_qkv_bwd
+// adds (and the plan allocates) on that route
+void launch_attn_bwd_any(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
+                         const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2, Drop d3, hipStream_t s);
+bool attn_dq_query_major(int L);
+int attn_dq_slabs(int L);
 inline bool attn_heads_supported(int H) { return H == 4 || H == 8 || H == 16; }
 void launch_qkv_bwd(const float* dQ, const float* dK, const float* dV, const float* x, const float* dr,
                     const float* ln_g, const uint16_t* WT3 /* split pack of the (384, 128) operand */, float* dx, float* p_lng, float* p_lnb, int R,

@@ -325,11 +325,13 @@ def synthetic_dataset(configs, n_train=512, n_test=128, n_words=200, n_chars=30,
 # limits of the HIP engine (vslnet_amd/csrc/common.hpp: MAX_LQ, MAX_LC; api.hip vsl_create): checked against the WHOLE dataset
 # before the first step, so that one long query or token cannot abort a run in the middle of an epoch
 ENGINE_MAX_WORDS, ENGINE_MAX_CHARS, ENGINE_MAX_CHAR_DIM = 128, 40, 128
+ENGINE_MAX_CLIPS = 4096             # common.hpp MAX_L: clips per video the attention kernels serve
 
 
-def validate_dataset(dataset, configs):
+def validate_dataset(dataset, configs, features=None):
     """Host-side checks the reference gets for free from nn.Embedding's IndexError: every id inside its table, every length
-    inside the engine's limits.  Raises ValueError naming the first offending record."""
+    inside the engine's limits.  Raises ValueError naming the first offending record.  The clip count of a record is that of its video
+    after sampling to max_pos_len clips (visual_feature_sampling): features[vid] when given, else the record's v_len."""
     n_words, n_chars = int(dataset['n_words']), int(dataset['n_chars'])
     if int(getattr(configs, 'char_dim', 50)) > ENGINE_MAX_CHAR_DIM:
         raise ValueError('--char_dim %d: the HIP embedding kernels stage character rows in LDS with a row stride of at most %d floats'
@@ -349,6 +351,14 @@ def validate_dataset(dataset, configs):
                     raise ValueError('%s: a token of %d characters; supported: <= %d' % (where, len(c), ENGINE_MAX_CHARS))
                 if len(c) and (c.min() < 0 or c.max() >= n_chars):
                     raise ValueError('%s: char id outside [0, %d)' % (where, n_chars))
+            if features is not None and r.get('vid') in features:
+                n_clips = int(np.shape(features[r['vid']])[0])
+            else:
+                n_clips = int(r['v_len']) if 'v_len' in r else 0
+            n_clips = min(n_clips, int(configs.max_pos_len))
+            if n_clips > ENGINE_MAX_CLIPS:
+                raise ValueError('%s: %d clips after sampling to max_pos_len=%d; supported: <= %d (the attention kernels)'
+                                 % (where, n_clips, configs.max_pos_len, ENGINE_MAX_CLIPS))
             if 's_ind' in r and not (0 <= int(r['s_ind']) <= int(r['e_ind'])):
                 raise ValueError('%s: span labels (%s, %s)' % (where, r['s_ind'], r['e_ind']))
 
@@ -359,7 +369,7 @@ def load_dataset(configs):
     if configs.task == 'synthetic':
         dataset, feats = synthetic_dataset(configs, getattr(configs, 'synthetic_train', 512), getattr(configs, 'synthetic_test', 128),
                                            seed=configs.seed)
-        validate_dataset(dataset, configs)
+        validate_dataset(dataset, configs, feats)
         return dataset, feats
     if configs.task not in ('charades', 'activitynet', 'tacos'):
         raise ValueError('Unknown task {}!!!'.format(configs.task))
@@ -373,5 +383,5 @@ def load_dataset(configs):
     features = load_video_features(feature_dir, configs.max_pos_len)
     if not features:
         raise ValueError('no *.npy video features under %s' % feature_dir)
-    validate_dataset(dataset, configs)
+    validate_dataset(dataset, configs, features)
     return dataset, features
