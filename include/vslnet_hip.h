@@ -184,9 +184,7 @@ int vsl_adamw_step(vsl_handle h, float* params, const float* grads, float* exp_a
 /* vsl_io.fused_step: vsl_backward followed by vsl_adamw_step(params, io->grads, exp_avg, exp_avg_sq, &hp, grad_norm_out) with
  * hp.norm_from_backward = 1, as ONE call (main_t7.py:110-113 without the host in between).  `params` is normally vsl_io.params itself: every
  * kernel that reads the weights is ordered in front of the update.  io->grads still receives the (unclipped) gradients.  The library issues
- * the final reduction and the update as two launches on the caller's stream; with VSL_FUSED_TAIL=1 in the environment they are ONE launch
- * whose workgroups hand their sums of squares to each other (same arithmetic, the norm summed in another fixed order) -- measured level with
- * the two launches, hence not the default; it needs every gradient to leave the final reduction (not word_table = 1). */
+ * the final reduction and the update as two launches on the caller's stream. */
 typedef struct vsl_fused_step {
     float* params;
     float* exp_avg;

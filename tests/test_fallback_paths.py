@@ -16,10 +16,11 @@ takes) -- the training suite's whole-tile shapes select the fused paths, so it i
 
 Round 6: VSL_QUERY_FUSED=0 -- the query branch as row-tile launches (linear_fwd + convblock_fwd<0> + attn_block_fwd / attn_out_bwd + attn_bwd +
 convblock_bwd<0>) instead of the sample-local k_query_fwd / k_query_bwd that every Lq <= 32 shape now selects; what Lq > 32 takes.  Same re-run.
-Later in round 6: VSL_CQ_FOLD=0 (k_cq_col as its own launch: what T > 128 or Lq > 32 takes) and VSL_LOSS_INLINE=0 / VSL_FUSED_TAIL=1 (the lazy loss in front
-of the heads' backward; the final reduction and AdamW as one launch), the last two also through tests/test_fused_loss.py and tests/test_optimizer.py, which drive
-those paths.  (The variants round 6 replaced outright left no switch: k_attn_block_fwd<2> and k_attn_bwd_fused<256> for 128 < L <= 256, 256-row chunks for the step's
-last weight-gradient batch, the unmerged tail batch -- their A/B numbers are in profiles/r06_notes.md.)"""
+Later in round 6: VSL_CQ_FOLD=0 (k_cq_col as its own launch: what T > 128 or Lq > 32 takes) and VSL_LOSS_INLINE=0 (the lazy loss in front of the heads'
+backward: what T < 32 or a mask sum left to the device takes), the latter also through the shapes of tests/test_fused_loss.py.  (The variants
+round 6 replaced outright left no switch: k_attn_block_fwd<2> and k_attn_bwd_fused<256> for 128 < L <= 256, 256-row chunks for the step's last
+weight-gradient batch, the unmerged tail batch -- their A/B numbers are in profiles/r06_notes.md.  Two switches that forced a variant no shape
+selects went later, as the rule above asks: the round-4 conv-block forward for whole tiles, and the final reduction, clip and AdamW as one launch.)"""
 import os
 import subprocess
 import sys

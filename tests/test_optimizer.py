@@ -136,14 +136,12 @@ def test_norm_from_backward_matches_the_two_kernel_step(predictor):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('variant', ['transformer', 'rnn', 'word_table', 'hf_order', 'two launches'])
-def test_fused_step_matches_backward_then_adamw(variant, monkeypatch):
-    """vsl_io.fused_step (round 6): the optimizer step applied by the backward's LAST launch (final reduction + global norm + AdamW in one
-    kernel whose workgroups hand their sums of squares to each other) against backward() followed by adamw_step(norm_from_backward=True).
-    Three consecutive training steps from the same state: identical gradients, the same norm to fp32 rounding (another summation order),
-    the same parameters and moments.  word_table = 1 (its table gradient does not leave the reduction) takes the library's two-launch form, and
-    so does every configuration unless VSL_FUSED_TAIL=1 asks for the one launch (the library's default: profiles/r06_notes.md section 7)."""
-    monkeypatch.setenv('VSL_FUSED_TAIL', '0' if variant == 'two launches' else '1')
+@pytest.mark.parametrize('variant', ['transformer', 'rnn', 'word_table', 'hf_order'])
+def test_fused_step_matches_backward_then_adamw(variant):
+    """vsl_io.fused_step (round 6): the optimizer step issued by the backward behind its final reduction (reduce + adamw) against backward()
+    followed by adamw_step(norm_from_backward=True).  Three consecutive training steps from the same state: identical gradients, the same norm
+    to fp32 rounding, the same parameters and moments.  word_table = 1: its table gradient does not leave the reduction, so the norm is summed
+    over the bucket instead."""
     from oracle import vslnet_oracle as O
     from vslnet_amd.engine import Engine, flat_from_state_dict
     from vslnet_amd.dp import FlatAdamW

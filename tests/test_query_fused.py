@@ -92,11 +92,5 @@ def test_which_launches_a_step_takes_and_what_the_ledger_records():
         for d in r['deps']:
             assert recs[d]['stop_us'] <= r['start_us'] + 0.5, 'launch %d (%s) started before its dependency %d (%s) stopped' % (i, r['name'], d, recs[d]['name'])
     assert any(len(r['deps']) >= 2 for r in recs)                 # the joins
-    os.environ['VSL_FUSED_TAIL'] = '1'                          # the final reduction + clip + AdamW as one launch (off by default)
-    try:
-        fused = [r['name'] for r in launches(20)]
-    finally:
-        del os.environ['VSL_FUSED_TAIL']
-    assert fused[-1] == 'reduce_adamw' and 'adamw' not in fused and len(fused) == len(names) - 1
     names40 = [r['name'] for r in launches(40)]
     assert 'query_fwd' not in names40 and 'query_bwd' not in names40 and names40.count('convblock_fwd') == 4

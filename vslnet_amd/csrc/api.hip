@@ -104,10 +104,7 @@ struct vsl_handle_s {
     unsigned* loss_counter = nullptr;    // arrival counter of k_loss_fused (zero between calls)
     uint8_t* decay_dev = nullptr;        // per-element weight-decay flag of the flat bucket (vsl_adamw_step)
     float* opt_scratch = nullptr;        // OPT_BLOCKS partial sums of grads^2
-    unsigned long long* tail_gran = nullptr;   // vsl_io.fused_step: one {tag, sum of squares} granule per workgroup of the fused tail launch
     int cus = 0;                         // CUs of the device (vsl_create)
-    int tail_cap = 0;                    // ... their number = the largest grid that launch may take (4 workgroups per CU)
-    unsigned tail_tag = 0;               // ... the tag of the last such launch
     const float* sq_src = nullptr;       // the last vsl_backward's per-block sums of squares (Plan::sq_dev), their count, the bucket they describe
     int sq_n = 0;
     const float* sq_grads = nullptr;
@@ -1411,22 +1408,10 @@ void run_backward(Ctx& c) {
         LAUNCH("reduce", launch_reduce(c.ws, io->grads, p.segs_dev, p.blk2seg_dev + 2 * p.nblocks_early, nlate, p.sq_dev + p.nblocks_early, c.s));
         return;
     }
-    // the optimizer step inside the call (vsl_io.fused_step): one launch when every gradient leaves the reductions, the two launches otherwise
+    // the optimizer step inside the call (vsl_io.fused_step): the reduction, then AdamW (clip norm from the reduction's sums of squares when
+    // they cover the whole bucket)
     const vsl_adamw& hp = fs->hp;
     const float bc1 = (float)(1.0 - std::pow((double)hp.beta1, (double)hp.step)), bc2s = (float)std::sqrt(1.0 - std::pow((double)hp.beta2, (double)hp.step));
-    // ONE launch only on request (VSL_FUSED_TAIL=1, read per call): same-box it is level with the two launches (profiles/r06_notes.md section 7), and a
-    // launch whose workgroups wait for each other is the wrong default for a process that may be given fewer CUs than the device reports
-    const char* ft = getenv("VSL_FUSED_TAIL");
-    const bool fuse = ft && atoi(ft) != 0;
-    const int grid = fuse && p.sq_cover ? reduce_adamw_grid(nlate, c.h->tail_cap) : 0;
-    if (grid > 0) {
-        if (++c.h->tail_tag == 0) ++c.h->tail_tag;
-        LAUNCH("reduce_adamw", launch_reduce_adamw(c.ws, io->grads, p.segs_dev, p.blk2seg_dev + 2 * p.nblocks_early, nlate, p.sq_dev + p.nblocks_early,
-                                                   p.sq_dev, p.blk2seg_dev, p.nblocks_early, grid, c.h->tail_gran, c.h->tail_tag, fs->params,
-                                                   fs->exp_avg, fs->exp_avg_sq, c.h->decay_dev, hp.lr, hp.beta1, hp.beta2, hp.eps,
-                                                   hp.weight_decay, hp.clip_norm, bc1, bc2s, fs->grad_norm_out, hp.hf_order, c.s));
-        return;
-    }
     LAUNCH("reduce", launch_reduce(c.ws, io->grads, p.segs_dev, p.blk2seg_dev + 2 * p.nblocks_early, nlate, p.sq_dev + p.nblocks_early, c.s));
     LAUNCH("adamw", launch_adamw(fs->params, io->grads, fs->exp_avg, fs->exp_avg_sq, c.h->decay_dev, c.h->opt_scratch, c.h->param_floats, hp.lr,
                                  hp.beta1, hp.beta2, hp.eps, hp.weight_decay, hp.clip_norm, bc1, bc2s, fs->grad_norm_out, c.s, hp.hf_order,
@@ -1765,7 +1750,6 @@ int vsl_destroy(vsl_handle h) {
     if (h->loss_counter) (void)hipFree(h->loss_counter);
     if (h->decay_dev) (void)hipFree(h->decay_dev);
     if (h->opt_scratch) (void)hipFree(h->opt_scratch);
-    if (h->tail_gran) (void)hipFree(h->tail_gran);
     delete h;
     return 0;
 }
@@ -1855,7 +1839,7 @@ int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_str
     return 0;
 }
 
-// the optimizer's device-side constants (first use): decay flags, scratch of the two-kernel step, granules of the fused tail
+// the optimizer's device-side constants (first use): decay flags, scratch of the two-kernel step
 static int ensure_opt_state(vsl_handle_s* h) {
     if (h->decay_dev) return 0;
     std::vector<uint8_t> mask((size_t)h->param_floats, 0);          // VSLNet_t7.py:9-13: no decay for bias / layer_norm / LayerNorm parameters
@@ -1864,12 +1848,9 @@ static int ensure_opt_state(vsl_handle_s* h) {
                         p.name.find("LayerNorm") != std::string::npos;
         if (!nd) std::fill(mask.begin() + p.off, mask.begin() + p.off + p.numel, (uint8_t)1);
     }
-    h->tail_cap = reduce_adamw_resident(h->cus);
-    if (hipMalloc(&h->decay_dev, mask.size()) != hipSuccess || hipMalloc(&h->opt_scratch, (OPT_BLOCKS + 4) * sizeof(float)) != hipSuccess ||
-        hipMalloc(&h->tail_gran, (size_t)h->tail_cap * sizeof(unsigned long long)) != hipSuccess)
+    if (hipMalloc(&h->decay_dev, mask.size()) != hipSuccess || hipMalloc(&h->opt_scratch, (OPT_BLOCKS + 4) * sizeof(float)) != hipSuccess)
         return fail("optimizer state: hipMalloc failed");
-    if (hipMemcpy(h->decay_dev, mask.data(), mask.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(h->tail_gran, 0, (size_t)h->tail_cap * sizeof(unsigned long long)) != hipSuccess)      // tag 0 is never a launch's tag
+    if (hipMemcpy(h->decay_dev, mask.data(), mask.size(), hipMemcpyHostToDevice) != hipSuccess)
         return fail("optimizer state: hipMemcpy failed");
     return 0;
 }

@@ -55,6 +55,25 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
     for (int i = 1; i < nw; ++i) r = is_max ? fmaxf(r, red[i]) : r + red[i];
     return r;
 }
+// log-sum-exp of one sample's T logits by a 256-thread workgroup (every thread gets the result).  Every log-sum-exp of the loss comes from here
+// (k_loss_a -> scratch -> k_loss_c, k_loss_fused, and k_head_bwd's inline seeds of vsl_io.fused_loss), and every seed from loss_ce_seed /
+// loss_hl_seed (tile_bodies.hpp), so the seeds are the same bits whichever kernel computes them.
+__device__ __forceinline__ float loss_sample_lse(const float* __restrict__ x, int T, float* red) {
+    const int tid = threadIdx.x;
+    float mx = -3.0e38f;
+    for (int t = tid; t < T; t += 256) mx = fmaxf(mx, x[t]);
+    mx = block_reduce(mx, red, true);
+    float ss = 0.f;
+    for (int t = tid; t < T; t += 256) ss += expf(x[t] - mx);
+    ss = block_reduce(ss, red, false);
+    return mx + logf(ss);
+}
+// the four loss values from the batch sums of the CE terms (ce), of the highlight numerator (num) and the mask sum d
+__device__ __forceinline__ void loss_store(float* __restrict__ losses, float ce, float num, float d, float inv_batch, float w_loc, float w_hl) {
+    const float loc = ce * inv_batch;                                   // CrossEntropyLoss(mean) twice (:367-368)
+    const float hl = num / (d + 1e-12f);                                // (:298)
+    losses[0] = loc; losses[1] = hl; losses[2] = w_loc * loc + w_hl * hl; losses[3] = d;
+}
 __global__ __launch_bounds__(256) void k_loss_a(const float* __restrict__ sl, const float* __restrict__ el,
                                                 const float* __restrict__ h, const int64_t* __restrict__ s_lab,
                                                 const int64_t* __restrict__ e_lab, const int64_t* __restrict__ h_lab,
@@ -63,28 +82,17 @@ __global__ __launch_bounds__(256) void k_loss_a(const float* __restrict__ sl, co
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* s = sl + (size_t)b * T;
     const float* e = el + (size_t)b * T;
-    float ms = -3.0e38f, me = -3.0e38f;
-    for (int t = tid; t < T; t += 256) { ms = fmaxf(ms, s[t]); me = fmaxf(me, e[t]); }
-    ms = block_reduce(ms, red, true);
-    me = block_reduce(me, red, true);
-    float ss = 0.f, se = 0.f, num = 0.f, den = 0.f;
+    const float lses = loss_sample_lse(s, T, red), lsee = loss_sample_lse(e, T, red);
+    float num = 0.f, den = 0.f;
     for (int t = tid; t < T; t += 256) {
-        ss += expf(s[t] - ms);
-        se += expf(e[t] - me);
-        const float m = vmask[(size_t)b * T + t];
-        const float y = (float)h_lab[(size_t)b * T + t];
-        const float p = h[(size_t)b * T + t];
-        const float wgt = y == 0.f ? 1.f : 2.f * y;                         // (:293)
-        const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(logf(1.f - p), -100.f);   // BCELoss log clamp
-        num += -(y * lp + (1.f - y) * lq) * wgt * m;
+        const size_t i = (size_t)b * T + t;
+        const float m = vmask[i];
+        num += loss_hl_term(h[i], (float)h_lab[i], m);
         den += m;
     }
-    ss = block_reduce(ss, red, false);
-    se = block_reduce(se, red, false);
     num = block_reduce(num, red, false);
     den = block_reduce(den, red, false);
     if (tid == 0) {
-        const float lses = ms + logf(ss), lsee = me + logf(se);
         scratch[b] = lses;
         scratch[B + b] = lsee;
         scratch[2 * B + b] = (lses - s[s_lab[b]]) + (lsee - e[e_lab[b]]);
@@ -100,12 +108,7 @@ __global__ __launch_bounds__(256) void k_loss_b(int B, float inv_batch, float ma
     ce = block_reduce(ce, red, false);
     num = block_reduce(num, red, false);
     den = block_reduce(den, red, false);
-    if (threadIdx.x == 0) {
-        const float d = mask_sum_override > 0.f ? mask_sum_override : den;
-        const float loc = ce * inv_batch;                                   // CrossEntropyLoss(mean) twice (:367-368)
-        const float hl = num / (d + 1e-12f);                                // (:298)
-        losses[0] = loc; losses[1] = hl; losses[2] = w_loc * loc + w_hl * hl; losses[3] = d;
-    }
+    if (threadIdx.x == 0) loss_store(losses, ce, num, mask_sum_override > 0.f ? mask_sum_override : den, inv_batch, w_loc, w_hl);
 }
 // gradient seeds + (block (0,0)) the loss values: every block re-reduces the B per-sample partials itself (a few hundred
 // floats, L2-resident), which saves the single-block kernel between k_loss_a and this one on the critical path
@@ -123,34 +126,15 @@ __global__ __launch_bounds__(256) void k_loss_c(const float* __restrict__ sl, co
     num = block_reduce(num, red, false);
     den = block_reduce(den, red, false);
     const float dsum = mask_sum_override > 0.f ? mask_sum_override : den;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        const float loc = ce * inv_batch;                                   // CrossEntropyLoss(mean) twice (:367-368)
-        const float hl = num / (dsum + 1e-12f);                             // (:298)
-        losses[0] = loc; losses[1] = hl; losses[2] = w_loc * loc + w_hl * hl; losses[3] = dsum;
-    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) loss_store(losses, ce, num, dsum, inv_batch, w_loc, w_hl);
     const int b = blockIdx.y;
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= T) return;
     const size_t i = (size_t)b * T + t;
     const float cs = w_loc * inv_batch;
-    d_sl[i] = cs * (expf(sl[i] - scratch[b]) - (t == (int)s_lab[b] ? 1.f : 0.f));
-    d_el[i] = cs * (expf(el[i] - scratch[B + b]) - (t == (int)e_lab[b] ? 1.f : 0.f));
-    const float y = (float)h_lab[i], p = h[i], m = vmask[i];
-    const float wgt = y == 0.f ? 1.f : 2.f * y;
-    // d BCE / dp = (p - y) / max(p (1 - p), 1e-12)   (torch's binary_cross_entropy_backward)
-    d_h[i] = w_hl * wgt * m / (dsum + 1e-12f) * (p - y) / fmaxf(p * (1.f - p), 1e-12f);
-}
-// log-sum-exp of one sample's T logits by a 256-thread workgroup (every thread gets the result).  k_loss_fused and k_head_bwd's inline seeds
-// (vsl_io.fused_loss) both go through this function, so the seeds are the same bits whichever kernel computes them.
-__device__ __forceinline__ float loss_sample_lse(const float* __restrict__ x, int T, float* red) {
-    const int tid = threadIdx.x;
-    float mx = -3.0e38f;
-    for (int t = tid; t < T; t += 256) mx = fmaxf(mx, x[t]);
-    mx = block_reduce(mx, red, true);
-    float ss = 0.f;
-    for (int t = tid; t < T; t += 256) ss += expf(x[t] - mx);
-    ss = block_reduce(ss, red, false);
-    return mx + logf(ss);
+    d_sl[i] = loss_ce_seed(sl[i], scratch[b], t, (int)s_lab[b], cs);
+    d_el[i] = loss_ce_seed(el[i], scratch[B + b], t, (int)e_lab[b], cs);
+    d_h[i] = loss_hl_seed(h[i], (float)h_lab[i], vmask[i], w_hl, dsum);
 }
 // One launch when the caller supplies the global mask sum (the data-parallel path and bench.py do): the sample's workgroup writes its
 // gradient seeds itself -- they need nothing from other samples then -- and the LAST workgroup to arrive (agent-scope counter) adds the
@@ -167,34 +151,20 @@ __global__ __launch_bounds__(256) void k_loss_fused(const float* __restrict__ sl
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* s = sl + (size_t)b * T;
     const float* e = el + (size_t)b * T;
-    float ms = -3.0e38f, me = -3.0e38f;
-    for (int t = tid; t < T; t += 256) { ms = fmaxf(ms, s[t]); me = fmaxf(me, e[t]); }
-    ms = block_reduce(ms, red, true);
-    me = block_reduce(me, red, true);
-    float ss = 0.f, se = 0.f, num = 0.f;
+    const float lses = loss_sample_lse(s, T, red), lsee = loss_sample_lse(e, T, red);
+    float num = 0.f;
     for (int t = tid; t < T; t += 256) {
-        ss += expf(s[t] - ms);
-        se += expf(e[t] - me);
-        const float m = vmask[(size_t)b * T + t];
-        const float y = (float)h_lab[(size_t)b * T + t];
-        const float p = h[(size_t)b * T + t];
-        const float wgt = y == 0.f ? 1.f : 2.f * y;                         // (:293)
-        const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(logf(1.f - p), -100.f);   // BCELoss log clamp
-        num += -(y * lp + (1.f - y) * lq) * wgt * m;
+        const size_t i = (size_t)b * T + t;
+        num += loss_hl_term(h[i], (float)h_lab[i], vmask[i]);
     }
-    ss = block_reduce(ss, red, false);
-    se = block_reduce(se, red, false);
     num = block_reduce(num, red, false);
-    const float lses = ms + logf(ss), lsee = me + logf(se);
     const float cs = w_loc * inv_batch;
     const int sb = (int)s_lab[b], eb = (int)e_lab[b];
     for (int t = tid; t < T; t += 256) {
         const size_t i = (size_t)b * T + t;
-        d_sl[i] = cs * (expf(s[t] - lses) - (t == sb ? 1.f : 0.f));
-        d_el[i] = cs * (expf(e[t] - lsee) - (t == eb ? 1.f : 0.f));
-        const float y = (float)h_lab[i], p = h[i], m = vmask[i];
-        const float wgt = y == 0.f ? 1.f : 2.f * y;
-        d_h[i] = w_hl * wgt * m / (mask_sum + 1e-12f) * (p - y) / fmaxf(p * (1.f - p), 1e-12f);
+        d_sl[i] = loss_ce_seed(s[t], lses, t, sb, cs);
+        d_el[i] = loss_ce_seed(e[t], lsee, t, eb, cs);
+        d_h[i] = loss_hl_seed(h[i], (float)h_lab[i], vmask[i], w_hl, mask_sum);
     }
     if (tid == 0) {
         // the two partials go out WRITE-THROUGH (sc1 stores) and are drained before the arrival is counted; the last arriver reads them with
@@ -215,8 +185,7 @@ __global__ __launch_bounds__(256) void k_loss_fused(const float* __restrict__ sl
     ce = block_reduce(ce, red, false);
     nm = block_reduce(nm, red, false);
     if (tid == 0) {
-        const float loc = ce * inv_batch, hl = nm / (mask_sum + 1e-12f);
-        losses[0] = loc; losses[1] = hl; losses[2] = w_loc * loc + w_hl * hl; losses[3] = mask_sum;
+        loss_store(losses, ce, nm, mask_sum, inv_batch, w_loc, w_hl);
         __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // ready for the next call (stream order)
     }
 }
@@ -1715,8 +1684,7 @@ void launch_word_table_bwd(const float* dE, const int64_t* word_ids, float* gtab
 // sq[unit] = sum of squares of the unit's 256 results (also returned, valid in thread 0): every gradient of the bucket leaves this code, so the
 // clip's global norm needs no pass of its own over the bucket (vsl_adamw.norm_from_backward; k_adamw adds the partials in unit order).
 __device__ __forceinline__ float reduce_unit(const float* __restrict__ ws, float* __restrict__ grads, const ReduceSeg* __restrict__ segs,
-                                             const int* __restrict__ blk2seg, float* __restrict__ sq, int unit, float4 (&part)[4][64],
-                                             float4* keep = nullptr /* wave 0: this lane's four results (ragged units: one per 64-element pass) */) {
+                                             const int* __restrict__ blk2seg, float* __restrict__ sq, int unit, float4 (&part)[4][64]) {
     const int si = blk2seg[2 * unit], off = blk2seg[2 * unit + 1];
     const ReduceSeg* __restrict__ sgp = segs + si;
     const int n = sgp->n, nsrc = sgp->nsrc, rl = sgp->rl, ds = sgp->ds, dst = sgp->dst;
@@ -1760,7 +1728,6 @@ __device__ __forceinline__ float reduce_unit(const float* __restrict__ ws, float
         } else acc = make_float4(0.f, 0.f, 0.f, 0.f);
         float q = 0.f;
         if (grp == 0) {                                  // (wave 0)
-            if (keep) *keep = acc;
             q = wave_sum((acc.x * acc.x + acc.y * acc.y) + (acc.z * acc.z + acc.w * acc.w));
             if (l4 == 0) sq[unit] = q;
         }
@@ -1771,7 +1738,6 @@ __device__ __forceinline__ float reduce_unit(const float* __restrict__ ws, float
         // 256 exposed memory latencies)
         float* sp = reinterpret_cast<float*>(&part[0][0]);
         float q2 = 0.f;
-        float kp[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int base = 0; base < 256; base += 64) {
             const int e = off + base + l4;
@@ -1800,11 +1766,9 @@ __device__ __forceinline__ float reduce_unit(const float* __restrict__ ws, float
                 const float r = (sp[l4] + sp[64 + l4]) + (sp[128 + l4] + sp[192 + l4]);
                 grads[dst + (e / rl) * ds + (e % rl)] = r;
                 q2 += r * r;
-                kp[base >> 6] = r;
             }
         }
         if (grp == 0) {
-            if (keep) *keep = make_float4(kp[0], kp[1], kp[2], kp[3]);
             q2 = wave_sum(q2);
             if (l4 == 0) sq[unit] = q2;
         }
@@ -1887,146 +1851,6 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
     adamw_span(p, g, m, v, decay, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256, n4, coef, hp);
 }
 
-// =========================================================================================================
-// The step's tail as ONE launch (single process, vsl_io.fused_step): the final reduction, the clip's global norm and the AdamW update.
-//   phase 1  the workgroup reduces its (at most TAIL_UNITS) units -- unit u = blockIdx.x + j gridDim.x, the code of k_reduce -- keeps their
-//            results in LDS and adds their sums of squares;
-//   hand-off thread 0 publishes that sum as an 8-byte {launch tag, value} granule (ONE agent-scope write-through store: the mechanism of the
-//            fused rnn head, kernels_lstm.hip); wave 0 of every workgroup polls all gridDim.x granules until they carry this launch's tag
-//            (~2.5 us across XCDs) while waves 1 - 3 add the partials of the EARLY reduction (an earlier launch);
-//   phase 2  clip factor from the norm (fixed summation order: deterministic for a given grid), then AdamW on the elements THIS workgroup
-//            reduced (from LDS) and on its share of the early reduction's units (their gradients are in `grads` since an earlier launch).
-// Nothing but the granules crosses workgroups inside the launch, so there is no L2 write-back / invalidate in it (a first version that
-// updated the bucket grid-stride behind release / acquire fences took 38 - 78 us for 256 - 1024 workgroups: profiles/r06_notes.md).
-// All gridDim.x workgroups must be resident at once (they wait for each other): the launcher keeps the grid <= 4 per CU (16 of a CU's 32
-// wave slots, 8 KB of LDS each) and nothing else is in flight on the caller's streams at this point of the step.
-// =========================================================================================================
-constexpr int TAIL_UNITS = 4;
-struct FusedTail {
-    float *p, *m, *v;
-    const uint8_t* decay;
-    const float* sq_early;      // the early reduction's per-unit sums of squares
-    const int* blk2seg_early;   // ... and its unit table
-    int n_early;
-    unsigned long long* gran;   // [gridDim.x] {tag, value}
-    unsigned tag;
-    int nunits;
-    float clip;
-    AdamHp hp;
-    float* norm_out;
-};
-// AdamW on the 256 elements of one reduction unit: lane l4 of the calling wave owns the unit's float4 l4 (ragged units: element l4 of each 64-element pass)
-__device__ __forceinline__ void adamw_unit(const FusedTail& f, const ReduceSeg* __restrict__ segs, const int* __restrict__ blk2seg, int unit, int l4,
-                                           const float4 g, float coef) {
-    const int si = blk2seg[2 * unit], off = blk2seg[2 * unit + 1];
-    const ReduceSeg* __restrict__ sgp = segs + si;
-    const int n = sgp->n, rl = sgp->rl, ds = sgp->ds, dst = sgp->dst;
-    if (sgp->vec) {
-        const int i = off + l4 * 4;
-        if (i < n) adamw_vec4(f.p, f.m, f.v, f.decay, (int64_t)((dst + (i / rl) * ds + (i % rl)) >> 2), g, coef, f.hp);
-    } else {
-        const float gs[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int e = off + 64 * k + l4;
-            if (e < n) {
-                const int d = dst + (e / rl) * ds + (e % rl);
-                float pe = f.p[d], me = f.m[d], ve = f.v[d];
-                adamw_elem(pe, me, ve, gs[k], f.decay[d], coef, f.hp);
-                f.p[d] = pe; f.m[d] = me; f.v[d] = ve;
-            }
-        }
-    }
-}
-// the gradients of one EARLY unit back from the bucket, in the layout adamw_unit takes
-__device__ __forceinline__ float4 unit_grads(const float* __restrict__ grads, const ReduceSeg* __restrict__ segs, const int* __restrict__ blk2seg,
-                                             int unit, int l4) {
-    const int si = blk2seg[2 * unit], off = blk2seg[2 * unit + 1];
-    const ReduceSeg* __restrict__ sgp = segs + si;
-    const int n = sgp->n, rl = sgp->rl, ds = sgp->ds, dst = sgp->dst;
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sgp->vec) {
-        const int i = off + l4 * 4;
-        if (i < n) g = *reinterpret_cast<const float4*>(grads + dst + (i / rl) * ds + (i % rl));
-    } else {
-        float gs[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int e = off + 64 * k + l4;
-            if (e < n) gs[k] = grads[dst + (e / rl) * ds + (e % rl)];
-        }
-        g = make_float4(gs[0], gs[1], gs[2], gs[3]);
-    }
-    return g;
-}
-__global__ __launch_bounds__(256) void k_reduce_adamw(const float* __restrict__ ws, float* __restrict__ grads,
-                                                      const ReduceSeg* __restrict__ segs, const int* __restrict__ blk2seg,
-                                                      float* __restrict__ sq, FusedTail f) {
-    __shared__ float4 part[4][64];
-    __shared__ float4 kept[TAIL_UNITS][64];
-    __shared__ float red[4];
-    const int l4 = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float mine = 0.f;                                    // (thread 0) sum of squares of this workgroup's units, in unit order
-#pragma unroll
-    for (int j = 0; j < TAIL_UNITS; ++j) {
-        const int u = blockIdx.x + j * gridDim.x;        // (block-uniform)
-        if (u < f.nunits) {
-            float4 k4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            mine += reduce_unit(ws, grads, segs, blk2seg, sq, u, part, &k4);
-            if (wv == 0) kept[j][l4] = k4;
-            __syncthreads();                             // `part` is free again
-        }
-    }
-    using gu64 = unsigned long long;
-    if (threadIdx.x == 0)
-        __hip_atomic_store(f.gran + blockIdx.x, ((gu64)f.tag << 32) | __float_as_uint(mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    float s = 0.f;
-    if (threadIdx.x >= 64) {                             // waves 1 - 3: the early reduction's partials (an earlier launch: plain loads)
-        for (int k = threadIdx.x - 64; k < f.n_early; k += 192) s += f.sq_early[k];
-    } else {                                             // wave 0 polls (the other waves wait at the barrier below: no polling traffic of theirs)
-        for (int k = threadIdx.x; k < (int)gridDim.x; k += 64) {
-            gu64 g = __hip_atomic_load(f.gran + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            while ((unsigned)(g >> 32) != f.tag) {
-                __builtin_amdgcn_s_sleep(4);
-                g = __hip_atomic_load(f.gran + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            s += __uint_as_float((unsigned)g);
-        }
-    }
-    s = wave_sum(s);
-    if (l4 == 0) red[wv] = s;
-    __syncthreads();
-    const float norm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
-    if (blockIdx.x == 0 && threadIdx.x == 0 && f.norm_out) *f.norm_out = norm;
-    const float coef = f.clip > 0.f ? fminf(1.0f, f.clip / (norm + 1e-6f)) : 1.0f;       // clip_grad_norm_
-    // phase 2: wave w takes the workgroup's unit w ...
-    {
-        const int u = blockIdx.x + wv * gridDim.x;
-        if (wv < TAIL_UNITS && u < f.nunits) adamw_unit(f, segs, blk2seg, u, l4, kept[wv][l4], coef);
-    }
-    // ... and one early unit per wave and round (the early table sits in front of the late one: blk2seg_early)
-    for (int e = 4 * blockIdx.x + wv; e < f.n_early; e += 4 * gridDim.x)
-        adamw_unit(f, segs, f.blk2seg_early, e, l4, unit_grads(grads, segs, f.blk2seg_early, e, l4), coef);
-}
-int reduce_adamw_resident(int cus) {       // workgroups of k_reduce_adamw that may wait for each other: half of what the occupancy calculator admits, at most 4 per CU
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_reduce_adamw, 256, 0) != hipSuccess) return 0;
-    return std::max(0, std::min(4, per_cu / 2)) * cus;
-}
-int reduce_adamw_grid(int nunits, int cap) {      // the grid launch_reduce_adamw takes for `nunits` late units with at most `cap` resident workgroups, 0 = does not fit
-    if (nunits <= 0 || cap <= 0 || (int64_t)nunits > (int64_t)TAIL_UNITS * cap) return 0;
-    return std::min(nunits, cap);
-}
-void launch_reduce_adamw(const float* partial, float* grads, const ReduceSeg* segs_dev, const int* blk2seg_dev, int nunits, float* sq,
-                         const float* sq_early, const int* blk2seg_early, int n_early, int grid, unsigned long long* gran, unsigned tag,
-                         float* params, float* m, float* v, const uint8_t* decay_mask, float lr, float b1, float b2, float eps, float wd,
-                         float clip, float bc1, float bc2_sqrt, float* norm_out, int hf_order, hipStream_t s) {
-    FusedTail f;
-    f.p = params; f.m = m; f.v = v; f.decay = decay_mask; f.sq_early = sq_early; f.blk2seg_early = blk2seg_early; f.n_early = n_early;
-    f.gran = gran; f.tag = tag; f.nunits = nunits; f.clip = clip; f.hp = AdamHp{lr, b1, b2, eps, wd, bc1, bc2_sqrt, hf_order};
-    f.norm_out = norm_out;
-    VSL_LAUNCH(k_reduce_adamw, dim3(grid), dim3(256), 0, s, partial, grads, segs_dev, blk2seg_dev, sq, f);
-}
 void launch_adamw(float* params, const float* grads, float* m, float* v, const uint8_t* decay_mask, float* partials, int64_t n,
                   float lr, float b1, float b2, float eps, float wd, float clip, float bc1, float bc2_sqrt, float* norm_out,
                   hipStream_t s, int hf_order, const float* sq_from_backward, int nsq) {

@@ -263,12 +263,10 @@ constexpr int CB_PS = 384;                      // per-layer small parameters in
 // SH = rows a layer's valid range shrinks by on each side: 3 = row tiles with a recomputed halo (12 + 32 + 12 rows);
 // 0 = SAMPLE tiles for sequences of at most 32 rows (the query pass: Lq = 20): one workgroup per sample, its rows at the top
 // of a 32-row window, no halo and no recomputation -- rows >= L and the taps that leave the window are the conv's zero padding.
-// FULL: R and L are multiples of the 32-row tile (every BASELINE shape): every tile is whole and lies inside one sample, so the boundary
-// flags below are compile-time constants and the per-row store / tap predicates disappear (12 % of the kernel's instructions were
-// v_cmp / v_cndmask / exec-mask branches).
+// Whole tiles (R and L multiples of 32, L > 32) take k_convblock_fwd2 below; this kernel serves sample tiles and ragged row tiles.
 // The five GEMMs run on the bf16 matrix cores at fp32 grade (gemm16s): the depthwise output / LN1 output is split into three bf16 planes
 // while it is stored (LDS +18 KB for the row tiles), the weight slices come from the split packs.
-template <int SH, bool FULL>
+template <int SH>
 __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
     // sample tiles: 3 zero rows above and below the window in the LN / depthwise buffer stand for the taps that leave it
     constexpr int HL = 4 * SH, NW = TILE_M + 2 * HL, VOFF = SH ? 0 : HALO, VUR = SH ? NW + 12 : NW + 2 * HALO;
@@ -332,15 +330,15 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
     for (int k = 0; k < DWK; ++k) wkc[k] = a.dw_w[0][(tid & 127) * DWK + k];
     // a window that lies inside one sample needs no boundary tests in the depthwise conv (block-uniform)
     const bool interior = SH && rw0 >= 0 && rw0 + NW <= R && (rw0 % L) + NW <= L;
-    const bool full = FULL || (SH && r0 + TILE_M <= R);
+    const bool full = SH && r0 + TILE_M <= R;
     // Owner rows inside ONE sample (every tile when L % 32 == 0, and always in sample mode): the window rows of other samples
     // only ever act as that sample's zero padding (their own outputs feed no owner row), so their LayerNorm output is written
     // as zeros and the depthwise conv runs without per-tap tests.  [klo, khi) = window rows of the owner sample.
     const int s_own = r0 / L;
-    const bool one_owner = FULL || !SH || (full && (r0 + TILE_M - 1) / L == s_own);
+    const bool one_owner = !SH || (full && (r0 + TILE_M - 1) / L == s_own);
     const int klo = max(0, s_own * L - rw0), khi = min(NW, (s_own + 1) * L - rw0);
-    const bool plain = FULL || interior || one_owner;
-    auto row_ok = [&](int wr) { return FULL || (SH ? (full || rw0 + wr < R) : wr < L); };     // may window row wr (an owner row) be stored?
+    const bool plain = interior || one_owner;
+    auto row_ok = [&](int wr) { return SH ? (full || rw0 + wr < R) : wr < L; };     // may window row wr (an owner row) be stored?
     __syncthreads();
     ESTAMP(1);
     const Drop nodrop{0u, 0u, 1.f};
@@ -476,7 +474,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
     {
         const float* Pq = Ps + 4 * CB_PS;
         // LN1 output: three bf16 planes in the (now free) GEMM operand buffer, rows 0..31 ; h1 goes to memory straight from the registers
-        const int gn = FULL ? TILE_M : (SH ? min(TILE_M, R - r0) : L);
+        const int gn = SH ? min(TILE_M, R - r0) : L;
         ln_rows512_split(Xs + HL * LDP, Ub, UPS, TILE_M, Pq, Pq + 128, a.qf.d1, r0, a.qf.h1 ? a.qf.h1 + (size_t)r0 * D : nullptr, gn);
         b3_load(b3B, a.Wqkv3, D, 3 * D, D + 16 * w);
         __builtin_amdgcn_sched_barrier(0);
@@ -930,23 +928,20 @@ static void launch_cbf2_t(const CbFwdArgs& a, int grid, hipStream_t s) {
 static void launch_cbf2(const CbFwdArgs& a, int grid, hipStream_t s) {
     if (a.dp[0].thresh) launch_cbf2_t<true>(a, grid, s); else launch_cbf2_t<false>(a, grid, s);
 }
-template <int SH, bool FULL>
+template <int SH>
 static void launch_cbf(const CbFwdArgs& a, int grid, hipStream_t s) {
     static size_t ok = 0;
     const size_t lds = cb_fwd_lds_split(SH);
-    ensure_dynamic_lds((const void*)k_convblock_fwd<SH, FULL>, lds, ok, "k_convblock_fwd");
-    VSL_LAUNCH((k_convblock_fwd<SH, FULL>), dim3(grid), dim3(CB_T), lds, s, a);
+    ensure_dynamic_lds((const void*)k_convblock_fwd<SH>, lds, ok, "k_convblock_fwd");
+    VSL_LAUNCH((k_convblock_fwd<SH>), dim3(grid), dim3(CB_T), lds, s, a);
 }
 void launch_convblock_fwd(const CbFwdArgs& a, hipStream_t s) {
     if (a.L <= TILE_M) {                    // sample tiles: one workgroup per sample
-        launch_cbf<0, false>(a, a.R / a.L, s);
+        launch_cbf<0>(a, a.R / a.L, s);
         return;
     }
-    static const bool cb2 = !(getenv("VSL_CB2") && atoi(getenv("VSL_CB2")) == 0);
-    if (a.R % TILE_M == 0 && a.L % TILE_M == 0) {              // whole tiles inside one sample each
-        if (cb2) launch_cbf2(a, a.R / TILE_M, s);
-        else launch_cbf<3, true>(a, a.R / TILE_M, s);
-    } else launch_cbf<3, false>(a, (a.R + TILE_M - 1) / TILE_M, s);
+    if (a.R % TILE_M == 0 && a.L % TILE_M == 0) launch_cbf2(a, a.R / TILE_M, s);     // whole tiles inside one sample each
+    else launch_cbf<3>(a, (a.R + TILE_M - 1) / TILE_M, s);
     static int left = 6;
     if (edbg_on() && a.R > 4096) { int l2 = left, l3 = left; edbg_report("convblock_fwd: load | L0 | L1 | L2 | L3 | qkv", 7, s, left); edbg_report2("  L0: LN | dw | gemm | epilogue | barrier", 8, 13, s, l2); edbg_report2("  L0 gemm: (stamp 14 = group 0 done) group 1", 14, 16, s, l3); }
 }
@@ -969,7 +964,9 @@ void launch_convblock_fwd(const CbFwdArgs& a, hipStream_t s) {
 // QKV (whole tiles only): the workgroup first does k_qkv_bwd's work on its whole 56-row window (CbBwdArgs::qk) -- dy is born in LDS.  The halo
 // rows are recomputed (1.75 x the K = 384 product), but the product's price is its 288 KB weight stream per workgroup, which a 32-row and a 56-row
 // tile pay alike; what goes away is a launch of the dependent chain with its own cold start, and dy's trip through memory.
-template <int SH, bool FULL, int TAIL = 0, bool QKV = false>        // SH 3: row tiles with a recomputed halo ; 0: sample tiles for L <= 32 ; FULL: see k_convblock_fwd
+// FULL: R and L are multiples of the 32-row tile (every BASELINE shape): every tile is whole and lies inside one sample, so the boundary
+// flags are compile-time constants and the per-row store / tap predicates disappear.
+template <int SH, bool FULL, int TAIL = 0, bool QKV = false>        // SH 3: row tiles with a recomputed halo ; 0: sample tiles for L <= 32
 __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
     constexpr int HL = 4 * SH, NW = TILE_M + 2 * HL, VUR = SH ? NW + 12 : NW, XR = NW - 2 * SH;
     constexpr int ZPS = NW * CB_LDB;                     // elements between the dz planes

@@ -77,13 +77,20 @@ __device__ __forceinline__ void attn_out_bwd_tile(const AttnOutBwdArgs& a, const
     ln_bwd_tile(Gs, Xs, lres, a.ln_g, a.dr, a.p_lng, a.p_lnb, r0, R, nullptr, active);
 }
 
+// The loss of one element (kernels_bwd.hip k_loss_*) and its seeds (there, and inline in k_head_bwd / cqcat_bwd_tile): one definition.
 // CrossEntropy seed of logit x at position t (mean over the batch folded into cs = w_loc * inv_batch)
 __device__ __forceinline__ float loss_ce_seed(float x, float lse, int t, int label, float cs) { return cs * (expf(x - lse) - (t == label ? 1.f : 0.f)); }
-// highlight (weighted BCE, VSLNet_t7.py / layers_t7.py:291-299) seed of score p with label y under mask m
+// highlight (weighted BCE, VSLNet_t7.py / layers_t7.py:291-299): weight of label y (:293)
+__device__ __forceinline__ float loss_hl_weight(float y) { return y == 0.f ? 1.f : 2.f * y; }
+// ... the numerator's term of score p with label y under mask m (BCELoss clamps its logs at -100)
+__device__ __forceinline__ float loss_hl_term(float p, float y, float m) {
+    const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(logf(1.f - p), -100.f);
+    return -(y * lp + (1.f - y) * lq) * loss_hl_weight(y) * m;
+}
+// ... and its seed
 __device__ __forceinline__ float loss_hl_seed(float p, float y, float m, float w_hl, float mask_sum) {
-    const float wgt = y == 0.f ? 1.f : 2.f * y;
     // d BCE / dp = (p - y) / max(p (1 - p), 1e-12)   (torch's binary_cross_entropy_backward)
-    return w_hl * wgt * m / (mask_sum + 1e-12f) * (p - y) / fmaxf(p * (1.f - p), 1e-12f);
+    return w_hl * loss_hl_weight(y) * m / (mask_sum + 1e-12f) * (p - y) / fmaxf(p * (1.f - p), 1e-12f);
 }
 // gating + HighLightLayer + CQConcatenate backward (VSLNet_t7.py:60, layers_t7.py:262-289 backward):  dgated = dg0 + dg1 + dg2 ;
 // dlogit = (sum_c dgated * f2 + dh_loss) * h (1 - h) ; df2 = dgated * h + dlogit * wh ; df1 = df2 W1 ; partials of wh / bh.

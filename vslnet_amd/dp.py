@@ -125,11 +125,11 @@ def backward_and_exchange(engine, xchg, grads, seeds):
 
 def backward_exchange_step(engine, xchg, grads, seeds, opt):
     """One training step from the loss seeds on: backward, gradient exchange, clip + AdamW -- what `main.train` and `bench.py` run.
-    One process with rows in the batch: the update rides in the backward's last launch (`Engine.backward(fused_step=...)`: final reduction,
-    global norm and AdamW as one kernel).  More than one rank: `backward_and_exchange`, then the two-kernel step on the SUMMED bucket."""
+    One process with rows in the batch: the update is issued by the backward itself, behind its final reduction (`Engine.backward(fused_step=...)`).
+    More than one rank: `backward_and_exchange`, then the two-kernel step on the SUMMED bucket."""
     import torch.distributed as dist
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(xchg.group if xchg is not None else None) > 1
-    if not multi and xchg is None and seeds is not None and opt.engine is not None and getattr(engine, 'fused_tail', False):
+    if not multi and xchg is None and seeds is not None and opt.engine is not None and getattr(engine, 'has_fused_io', False):
         engine.backward(seeds[0], seeds[1], seeds[2], grads, fused_step=opt.fused_step())
         return
     touched = backward_and_exchange(engine, xchg, grads, seeds)

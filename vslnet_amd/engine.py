@@ -172,8 +172,8 @@ class Engine:
         check_hw_queues()
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.lib = load_library()
-        # vsl_io.fused_step (ABI 8): an older build loaded through VSLNET_HIP_LIB for an A/B run takes the two calls instead
-        self.fused_tail = hasattr(self.lib, 'vsl_abi_version') and self.lib.vsl_abi_version() >= 8
+        # vsl_io.fused_loss / fused_step (ABI 8): an older build loaded through VSLNET_HIP_LIB for an A/B run takes the separate calls instead
+        self.has_fused_io = hasattr(self.lib, 'vsl_abi_version') and self.lib.vsl_abi_version() >= 8
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
             raise ValueError('unknown predictor %r' % (configs.predictor,))
@@ -327,7 +327,7 @@ class Engine:
         if want_grads:
             l.d_h_score, l.d_start_logits, l.d_end_logits = _ptr(d[0]), _ptr(d[1]), _ptr(d[2])
         self._flush_loss()
-        if lazy and want_grads and scores is None and self.fused_tail:
+        if lazy and want_grads and scores is None and self.has_fused_io:
             self._pending_loss = (l, io, (start_labels, end_labels, h_labels, losses, d))
             return losses, d[0], d[1], d[2]
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
