@@ -166,3 +166,137 @@ def hip_dropout(seed):
         scale = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
         return torch.from_numpy(np.where(h >= thresh, scale, np.float32(0.0)).astype(np.float32).reshape(shape))
     return mask
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# training mode against the oracle on the HIP path's own dropout masks
+# ---------------------------------------------------------------------------------------------------------------------------
+def extreme_ragged(b):
+    """Batch transform: the last sample's video shrinks to 1 clip (features zeroed, span 0..0, highlight labels rebuilt), the first sample's
+    query to 1 word (trailing word and char ids zeroed).  Every other sample keeps its lengths, so the masks of those two samples cover a
+    whole row tile / key block of padding beside full-length neighbours.  Needs B >= 2 (sample 0 keeps the batch's full T, the last its full Lq)."""
+    B, T = b['v_mask'].shape
+    assert B >= 2, 'an extreme-ragged batch needs two samples'
+    b = {k: v.clone() for k, v in b.items()}
+    b['vfeats'][-1, 1:] = 0.0
+    b['lens'][-1] = 1
+    b['v_mask'] = O.convert_length_to_mask(b['lens'])
+    assert b['v_mask'].shape == (B, T)
+    b['s_labels'][-1] = 0
+    b['e_labels'][-1] = 0
+    b['h_labels'] = O.highlight_labels(b['s_labels'], b['e_labels'], b['lens'], T)
+    b['word_ids'][0, 1:] = 0
+    b['char_ids'][0, 1:] = 0
+    b['q_mask'] = (b['word_ids'] != 0).float()
+    assert int(b['q_mask'][0].sum()) == 1 and int(b['q_mask'][-1].sum()) == b['q_mask'].shape[1]
+    return b
+
+
+def check_routes(names, want=(), never=(), seeds_inline=None, context=''):
+    """Route assertions on the launch ledger of one step (`names`: eng.profile_launches() names in enqueue order).  `want`: labels that must
+    appear, `never`: labels that must not.  seeds_inline (the production loss with the caller's mask sum): True -> the loss launch leaves the
+    dependent chain and runs behind the span heads' backward, which computes its seeds from the logits; False -> the loss launches in front of it."""
+    missing = [n for n in want if n not in names]
+    present = [n for n in never if n in names]
+    assert not missing and not present, '%s: route moved -- missing %s, unexpected %s; ledger %s' % (context, missing, present, names)
+    if seeds_inline is not None:
+        assert 'loss' in names and 'head_bwd' in names, (context, names)
+        behind = names.index('loss') > names.index('head_bwd')
+        assert behind == seeds_inline, '%s: loss seeds %s the heads\' backward, expected %s; ledger %s' % (
+            context, 'inside' if behind else 'in front of', 'inside' if seeds_inline else 'in front of', names)
+
+
+def check_training_against_oracle(B, T, Lq, Lc, cfg=None, param_seed=21, batch_seed=22, step_seed=(7 << 33) + 12345, lazy=False, transform=None,
+                                  scaled_bias_floor=False, want=(), never=(), seeds_inline=None, context=''):
+    """One training step (drop_rate 0.2 unless `cfg` says otherwise) against the oracle evaluated on the HIP path's dropout masks, recomputed on the
+    host (hip_dropout), and on the ReLU branches the HIP forward took (inside their fp32 noise: assert_forced_relu_inside_noise).
+    cfg: O.make_cfg keywords (num_heads, predictor, video_feature_dim, word_dim, char_dim, word_table, word_size, max_pos_len, ...).
+    lazy: the production loss sequence of main.train / bench.py -- loss(lazy=True, inv_batch=1/B, mask_sum=...) then backward; otherwise the
+    eager loss with the device-side mask sum.  transform: batch -> batch before the step (extreme_ragged).  scaled_bias_floor: as in
+    test_hip_training.check_shape_against_oracle.  want / never / seeds_inline: route assertions on the ledger of this very step (check_routes).
+    Gates: logits 1e-4 * scale, h_score 2e-5, total loss 1e-4, every gradient 1e-4 * |g|inf + 1e-6, extract_index bit-equal.
+    Returns a namespace of what the step left (engine, params, batch, the flat gradient, the HIP path's ReLU masks) for further checks."""
+    from vslnet_amd.engine import Engine, flat_from_state_dict
+    kw = dict(max_pos_len=max(T, Lq), word_size=102, drop_rate=0.2)
+    kw.update(cfg or {})
+    cfg = O.make_cfg(**kw)
+    P = O.random_params(cfg, seed=param_seed)
+    b = O.synthetic_batch(cfg, B, T, Lq, Lc, seed=batch_seed, ragged=True)
+    if transform is not None:
+        b = transform(b)
+    d = {k: v.cuda().contiguous() for k, v in b.items()}
+    eng = Engine(cfg)
+    flat = flat_from_state_dict(eng, P)
+    pad, glove = P.get('embedding_net.word_emb.pad_vec'), P.get('embedding_net.word_emb.glove_vec')     # absent: trainable word table
+    profile = bool(want or never or seeds_inline is not None)
+    if profile:
+        eng.profile_select('*')
+    try:
+        h, sl, el = eng.forward(flat, None if pad is None else pad.cuda(), None if glove is None else glove.cuda(), d['word_ids'], d['char_ids'],
+                                d['vfeats'], d['v_mask'], d['q_mask'], training=True, seed=step_seed)
+        if lazy:
+            losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0, inv_batch=1.0 / B,
+                                               mask_sum=float(b['v_mask'].sum()), lazy=True)
+        else:
+            losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0)
+        g = eng.backward(d_h, d_sl, d_el, eng.new_flat()).clone()
+        torch.cuda.synchronize()
+        names = [r['name'] for r in eng.profile_launches()] if profile else []
+    finally:
+        if profile:
+            eng.profile_select(None)
+    if profile:
+        check_routes(names, want, never, seeds_inline, context)
+    try:
+        O.record_relu_signs()
+        O.force_dropout(hip_dropout(step_seed))
+        with torch.no_grad():
+            O.total_loss(P, cfg, b, training=True)
+        flips, hip_masks = relu_flips(eng, B, T, Lq, predictor=cfg.predictor)
+        O.record_relu_signs(False)
+        O.force_relu_signs(hip_masks)
+        O.force_dropout(hip_dropout(step_seed))
+        O.record_bias_terms(scaled_bias_floor)
+        Pg = {k: v.clone().requires_grad_(k not in O.FROZEN) for k, v in P.items()}
+        total, (oh, osl, oel, _, _) = O.total_loss(Pg, cfg, b, training=True)
+        n_sites = O.DROP_CALLS
+        O.force_relu_signs(None)
+        O.force_dropout(None)
+        assert n_sites == (41 if cfg.predictor == 'transformer' else 23), (context, n_sites)
+        assert_forced_relu_inside_noise(O, (context, flips))
+        total.backward()
+        bias_S = O.bias_term_sums(Pg) if scaled_bias_floor else {}
+    finally:
+        O.record_relu_signs(False)
+        O.force_relu_signs(None)
+        O.force_dropout(None)
+        O.record_bias_terms(False)
+    fin = osl.detach().abs() < 1e29
+    scale = max(1.0, float(osl.detach()[fin].abs().max()))
+    assert float((sl.cpu() - osl.detach())[fin].abs().max()) <= 1e-4 * scale, context
+    assert float((el.cpu() - oel.detach())[fin].abs().max()) <= 1e-4 * scale, context
+    assert float((h.cpu() - oh.detach()).abs().max()) <= 2e-5, context
+    assert abs(float(losses[2]) - float(total.detach())) <= 1e-4 * max(1.0, abs(float(total.detach()))), (context, float(losses[2]), float(total))
+    bad = []
+    for k, t in eng.views(g).items():
+        ref = Pg[k].grad if Pg[k].grad is not None else torch.zeros_like(Pg[k])
+        err = float((t.cpu() - ref).abs().max())
+        tol = 1e-4 * float(ref.abs().max()) + max(1e-6, RELU_NOISE_KAPPA * 2.0 ** -24 * bias_S.get(k, 0.0))
+        if k == 'cq_attention.w4Q' and Lq == 1:
+            # one query word: the softmax over j is the constant 1, so dw4Q is structurally zero (SURVEY 8a: w4Q only acts through that softmax).
+            # What both sides compute is the cancellation residue of sum_i S_col (dS - dot); the gate for a structural zero is absolute, at the
+            # size of that residue (test_hip_training.check_shape_against_oracle)
+            tol = 2e-5
+        elif k == 'cq_attention.w4Q' and int(b['q_mask'].sum(1).min()) == 1:
+            # a one-word query beside longer ones (extreme_ragged): that sample's share of dw4Q is the same structural zero, and its residue -- summed
+            # over all T clips of the sample -- stays while the true gradient shrinks to what the other samples give.  The fp32 oracle itself then
+            # misses the relative gate against its own fp64 evaluation (2.6 x at H 16, B 2, T 255, Lq 20: 4.2e-6 against 1.6e-6), so the
+            # structural-zero floor above applies on top of the relative gate
+            tol = max(tol, 2e-5)
+        if not err <= tol:
+            bad.append((k, err, tol))
+    assert not bad, (context, flips, bad[:6])
+    si, ei = eng.extract_index(sl, el)
+    osi, oei = O.extract_index(osl.detach(), oel.detach())
+    assert torch.equal(si.cpu(), osi) and torch.equal(ei.cpu(), oei), context
+    return SimpleNamespace(cfg=cfg, P=P, b=b, d=d, eng=eng, flat=flat, g=g, hip_masks=hip_masks, flips=flips, names=names)

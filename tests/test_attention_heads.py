@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from oracle import vslnet_oracle as O
-from tests.helpers import GOLDEN, ROOT, assert_forced_relu_inside_noise, grad_tol, load_golden
+from tests.helpers import GOLDEN, ROOT, assert_forced_relu_inside_noise, check_training_against_oracle, grad_tol, load_golden
 
 HEAD_CASES = ['heads4_tf', 'heads16_tf']
 
@@ -229,46 +229,8 @@ def test_eval_mode_matches_oracle(num_heads, T, Lq, predictor):
 @pytest.mark.parametrize('B,T,Lq,predictor', [(3, 40, 7, 'transformer'), (2, 128, 20, 'transformer'), (2, 200, 9, 'transformer'),
                                               (2, 301, 7, 'transformer'), (4, 33, 6, 'rnn')])
 def test_training_mode_matches_oracle_on_the_same_dropout_masks(num_heads, B, T, Lq, predictor):
-    from tests.helpers import relu_flips, hip_dropout
-    cfg = O.make_cfg(video_feature_dim=64, max_pos_len=max(T, Lq), word_size=102, drop_rate=0.2, predictor=predictor, num_heads=num_heads)
-    P = O.random_params(cfg, seed=21)
-    b = O.synthetic_batch(cfg, B, T, Lq, 6, seed=22, ragged=True)
-    d = _dev(b)
-    eng, flat = _engine(cfg, P)
-    seed = (7 << 33) + 12345
-    h, sl, el = _fwd(eng, flat, P, d, True, seed)
-    losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0)
-    g = eng.backward(d_h, d_sl, d_el, eng.new_flat())
-    torch.cuda.synchronize()
-    O.record_relu_signs()
-    O.force_dropout(hip_dropout(seed))
-    with torch.no_grad():
-        O.total_loss(P, cfg, b, training=True)
-    _, hip_masks = relu_flips(eng, B, T, Lq, predictor=predictor)
-    O.record_relu_signs(False)
-    O.force_relu_signs(hip_masks)
-    O.force_dropout(hip_dropout(seed))
-    Pg = {k: v.clone().requires_grad_(k not in O.FROZEN) for k, v in P.items()}
-    total, (oh, osl, oel, _, _) = O.total_loss(Pg, cfg, b, training=True)
-    n_sites = O.DROP_CALLS
-    O.force_relu_signs(None)
-    O.force_dropout(None)
-    assert n_sites == (41 if predictor == 'transformer' else 23)
-    assert_forced_relu_inside_noise(O)
-    total.backward()
-    fin = osl.detach().abs() < 1e29
-    scale = max(1.0, float(osl.detach()[fin].abs().max()))
-    assert float((sl.cpu() - osl.detach())[fin].abs().max()) <= 1e-4 * scale
-    assert float((el.cpu() - oel.detach())[fin].abs().max()) <= 1e-4 * scale
-    assert float((h.cpu() - oh.detach()).abs().max()) <= 2e-5
-    assert abs(float(losses[2]) - float(total.detach())) <= 1e-4 * max(1.0, abs(float(total.detach())))
-    bad = []
-    for k, t in eng.views(g).items():
-        ref = Pg[k].grad if Pg[k].grad is not None else torch.zeros_like(Pg[k])
-        err, tol = float((t.cpu() - ref).abs().max()), 1e-4 * float(ref.abs().max()) + 1e-6
-        if not err <= tol:
-            bad.append((k, err, tol))
-    assert not bad, bad[:6]
+    check_training_against_oracle(B, T, Lq, 6, cfg=dict(video_feature_dim=64, predictor=predictor, num_heads=num_heads), param_seed=21, batch_seed=22,
+                                  step_seed=(7 << 33) + 12345)
 
 
 @pytest.mark.gpu

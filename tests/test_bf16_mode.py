@@ -21,7 +21,10 @@ def _round_bf16(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
 
-@pytest.mark.parametrize('B,T,Dv,training', [(3, 40, 64, False), (2, 128, 1024, False), (3, 40, 1024, True)])
+# (Dv % 8 == 0 is all the mode requires: Dv 8 and 40 end inside k_vproj_fwd_bf16's first 128-wide k chunk, 520 one 8-wide group into its fifth;
+# T 129 and 257 take the element-hash and the key-pair attention kernels in training mode)
+@pytest.mark.parametrize('B,T,Dv,training', [(3, 40, 64, False), (2, 128, 1024, False), (3, 40, 1024, True),
+                                             (3, 40, 8, True), (2, 129, 40, True), (2, 257, 520, True), (3, 40, 8, False)])
 def test_bf16_mode_matches_the_oracle_on_rounded_inputs(B, T, Dv, training):
     from vslnet_amd.engine import Engine, flat_from_state_dict
     from tests.helpers import hip_dropout

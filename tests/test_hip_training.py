@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import vslnet_oracle as O
-from tests.helpers import RELU_NOISE_KAPPA, assert_forced_relu_inside_noise
+from tests.helpers import RELU_NOISE_KAPPA, assert_forced_relu_inside_noise, check_training_against_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -115,47 +115,8 @@ def test_training_mode_matches_oracle_on_the_same_dropout_masks(dv, B, T, Lq, Lc
     """drop_rate 0.2 (the benchmark's mode), all 41 dropout sites: the oracle is handed the HIP path's masks -- recomputed on
     the host from the documented counter-based hash (tests/helpers.py) -- and must then agree with the training-mode forward
     (logits 1e-4) and with every gradient (1e-4 * |g|inf + 1e-6), like the eval-mode parity tests."""
-    from tests.helpers import relu_flips, hip_dropout
-    cfg = O.make_cfg(video_feature_dim=dv, max_pos_len=max(T, Lq), word_size=102, drop_rate=0.2, predictor=predictor, char_dim=abs(char_dim),
-                     word_table=char_dim < 0)
-    P = O.random_params(cfg, seed=21)
-    b = O.synthetic_batch(cfg, B, T, Lq, Lc, seed=22, ragged=True)
-    d = _dev(b)
-    eng, flat = _engine(cfg, P)
-    seed = (7 << 33) + 12345                     # exercises the high word of the 64-bit seed too
-    h, sl, el = _fwd(eng, flat, P, d, True, seed)
-    losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0)
-    g = eng.backward(d_h, d_sl, d_el, eng.new_flat())
-    torch.cuda.synchronize()
-    O.record_relu_signs()
-    O.force_dropout(hip_dropout(seed))
-    with torch.no_grad():
-        O.total_loss(P, cfg, b, training=True)
-    _, hip_masks = relu_flips(eng, B, T, Lq, predictor=predictor)
-    O.record_relu_signs(False)
-    O.force_relu_signs(hip_masks)
-    O.force_dropout(hip_dropout(seed))
-    Pg = {k: v.clone().requires_grad_(k not in O.FROZEN) for k, v in P.items()}
-    total, (oh, osl, oel, _, _) = O.total_loss(Pg, cfg, b, training=True)
-    n_sites = O.DROP_CALLS
-    O.force_relu_signs(None)
-    O.force_dropout(None)
-    assert n_sites == (41 if predictor == 'transformer' else 23)
-    assert_forced_relu_inside_noise(O)
-    total.backward()
-    fin = osl.detach().abs() < 1e29
-    scale = max(1.0, float(osl.detach()[fin].abs().max()))
-    assert float((sl.cpu() - osl.detach())[fin].abs().max()) <= 1e-4 * scale
-    assert float((el.cpu() - oel.detach())[fin].abs().max()) <= 1e-4 * scale
-    assert float((h.cpu() - oh.detach()).abs().max()) <= 2e-5
-    assert abs(float(losses[2]) - float(total.detach())) <= 1e-4 * max(1.0, abs(float(total.detach())))
-    bad = []
-    for k, t in eng.views(g).items():
-        ref = Pg[k].grad if Pg[k].grad is not None else torch.zeros_like(Pg[k])
-        err, tol = float((t.cpu() - ref).abs().max()), 1e-4 * float(ref.abs().max()) + 1e-6
-        if not err <= tol:
-            bad.append((k, err, tol))
-    assert not bad, bad[:6]
+    check_training_against_oracle(B, T, Lq, Lc, cfg=dict(video_feature_dim=dv, predictor=predictor, char_dim=abs(char_dim), word_table=char_dim < 0),
+                                  param_seed=21, batch_seed=22, step_seed=(7 << 33) + 12345)     # (the step seed exercises the high word of the 64-bit seed too)
 
 
 def test_headline_shape_at_full_size():
@@ -163,44 +124,11 @@ def test_headline_shape_at_full_size():
     (1) against the oracle on the same dropout masks -- logits 1e-4, every gradient 1e-4 * |g|inf + 1e-6;
     (2) size-independent property the data-parallel path rests on: with the GLOBAL normalisers (1/B, sum of the mask) and
         `sample_offset`, the training-mode gradients of three uneven shards add up to the gradient of the full batch."""
-    from tests.helpers import relu_flips, hip_dropout
     B, T, Lq, Lc = 64, 128, 20, 10
-    cfg = O.make_cfg(video_feature_dim=1024, max_pos_len=128, word_size=1002, drop_rate=0.2)
-    P = O.random_params(cfg, seed=12345)
-    b = O.synthetic_batch(cfg, B, T, Lq, Lc, seed=0, ragged=True)
-    d = _dev(b)
-    eng, flat = _engine(cfg, P)
     seed = 20260928
-    h, sl, el = _fwd(eng, flat, P, d, True, seed)
-    losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0)
-    g = eng.backward(d_h, d_sl, d_el, eng.new_flat()).clone()
-    torch.cuda.synchronize()
-    O.record_relu_signs()
-    O.force_dropout(hip_dropout(seed))
-    with torch.no_grad():
-        O.total_loss(P, cfg, b, training=True)
-    flips, hip_masks = relu_flips(eng, B, T, Lq)
-    O.record_relu_signs(False)
-    O.force_relu_signs(hip_masks)
-    O.force_dropout(hip_dropout(seed))
-    Pg = {k: v.clone().requires_grad_(k not in O.FROZEN) for k, v in P.items()}
-    total, (oh, osl, oel, _, _) = O.total_loss(Pg, cfg, b, training=True)
-    O.force_relu_signs(None)
-    O.force_dropout(None)
-    assert_forced_relu_inside_noise(O, flips)
-    total.backward()
-    fin = osl.detach().abs() < 1e29
-    scale = max(1.0, float(osl.detach()[fin].abs().max()))
-    assert float((sl.cpu() - osl.detach())[fin].abs().max()) <= 1e-4 * scale
-    assert float((el.cpu() - oel.detach())[fin].abs().max()) <= 1e-4 * scale
-    assert abs(float(losses[2]) - float(total.detach())) <= 1e-4 * max(1.0, abs(float(total.detach())))
-    bad = []
-    for k, t in eng.views(g).items():
-        ref = Pg[k].grad if Pg[k].grad is not None else torch.zeros_like(Pg[k])
-        err, tol = float((t.cpu() - ref).abs().max()), 1e-4 * float(ref.abs().max()) + 1e-6
-        if not err <= tol:
-            bad.append((k, err, tol))
-    assert not bad, (flips, bad[:6])
+    r = check_training_against_oracle(B, T, Lq, Lc, cfg=dict(video_feature_dim=1024, max_pos_len=128, word_size=1002), param_seed=12345,
+                                      batch_seed=0, step_seed=seed)
+    eng, flat, P, b, d, g, hip_masks = r.eng, r.flat, r.P, r.b, r.d, r.g, r.hip_masks
     # ---- (2) shards add up, in TRAINING mode: `sample_offset` continues the dropout counters, so the masks of a shard are
     #      the rows of the full batch's masks and N ranks reproduce the single-process gradient
     from tests.helpers import hip_relu_masks

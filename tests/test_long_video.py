@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from oracle import vslnet_oracle as O
-from tests.helpers import ROOT, assert_forced_relu_inside_noise
+from tests.helpers import ROOT, check_training_against_oracle
 from tests.test_attention_heads import _dev, _engine, _err, _fwd, _grads_vs_oracle
 
 
@@ -59,47 +59,8 @@ def test_eval_mode_matches_oracle_on_long_videos(T, B, num_heads, predictor):
 @pytest.mark.parametrize('num_heads', [8, 4, 16])
 @pytest.mark.parametrize('T,B', [(1100, 2), (2048, 1)])
 def test_training_mode_matches_oracle_on_the_same_dropout_masks(num_heads, T, B):
-    from tests.helpers import relu_flips, hip_dropout
-    Lq = 7
-    cfg = O.make_cfg(video_feature_dim=64, max_pos_len=T, word_size=102, drop_rate=0.2, num_heads=num_heads)
-    P = O.random_params(cfg, seed=51)
-    b = O.synthetic_batch(cfg, B, T, Lq, 6, seed=52, ragged=True)
-    d = _dev(b)
-    eng, flat = _engine(cfg, P)
-    seed = (5 << 33) + 4321
-    h, sl, el = _fwd(eng, flat, P, d, True, seed)
-    losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0)
-    g = eng.backward(d_h, d_sl, d_el, eng.new_flat())
-    torch.cuda.synchronize()
-    O.record_relu_signs()
-    O.force_dropout(hip_dropout(seed))
-    with torch.no_grad():
-        O.total_loss(P, cfg, b, training=True)
-    _, hip_masks = relu_flips(eng, B, T, Lq)
-    O.record_relu_signs(False)
-    O.force_relu_signs(hip_masks)
-    O.force_dropout(hip_dropout(seed))
-    Pg = {k: v.clone().requires_grad_(k not in O.FROZEN) for k, v in P.items()}
-    total, (oh, osl, oel, _, _) = O.total_loss(Pg, cfg, b, training=True)
-    n_sites = O.DROP_CALLS
-    O.force_relu_signs(None)
-    O.force_dropout(None)
-    assert n_sites == 41
-    assert_forced_relu_inside_noise(O)
-    total.backward()
-    fin = osl.detach().abs() < 1e29
-    scale = max(1.0, float(osl.detach()[fin].abs().max()))
-    assert float((sl.cpu() - osl.detach())[fin].abs().max()) <= 1e-4 * scale
-    assert float((el.cpu() - oel.detach())[fin].abs().max()) <= 1e-4 * scale
-    assert float((h.cpu() - oh.detach()).abs().max()) <= 2e-5
-    assert abs(float(losses[2]) - float(total.detach())) <= 1e-4 * max(1.0, abs(float(total.detach())))
-    bad = []
-    for k, t in eng.views(g).items():
-        ref = Pg[k].grad if Pg[k].grad is not None else torch.zeros_like(Pg[k])
-        err, tol = float((t.cpu() - ref).abs().max()), 1e-4 * float(ref.abs().max()) + 1e-6
-        if not err <= tol:
-            bad.append((k, err, tol))
-    assert not bad, bad[:6]
+    check_training_against_oracle(B, T, 7, 6, cfg=dict(video_feature_dim=64, num_heads=num_heads), param_seed=51, batch_seed=52,
+                                  step_seed=(5 << 33) + 4321)
 
 
 @pytest.mark.gpu
