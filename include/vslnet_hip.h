@@ -26,7 +26,7 @@ typedef struct vsl_handle_s* vsl_handle;
 /* fields of the `configs` namespace read by VSLNet.__init__ (VSLNet_t7.py:24-38) */
 typedef struct {
     int32_t dim;               /* configs.dim              (kernels are specialised for 128)              */
-    int32_t num_heads;         /* configs.num_heads        (4, 8 or 16: head size 32, 16 or 8)            */
+    int32_t num_heads;         /* configs.num_heads (1, 2, 4, 8 or 16: head size 128, 64, 32, 16 or 8)    */
     int32_t max_pos_len;       /* configs.max_pos_len      (rows of the positional table; T, Lq <= it)    */
     int32_t video_feature_dim; /* configs.video_feature_dim (multiple of 4: 1024 I3D, 4096 / 500 C3D)         */
     int32_t word_dim;          /* configs.word_dim = 300   (word_dim + 100 must be a multiple of 8)       */

@@ -1,8 +1,9 @@
-"""Training-step rate at num_heads 4 / 8 / 16, all in one process: ms/step (median of timed regions) and the per-launch time of the attention
+"""Training-step rate at several head counts, all in one process: ms/step (median of timed regions) and the per-launch time of the attention
 kernels (Engine.profile_select('*')).  Shapes: BASELINE configs[1] (B=64, T=128, Dv=1024, Lq=20, Lc=10, transformer, drop 0.2, train mode) and
-configs[4] (B=16, T=1024).  At 8 heads and L <= 128 the attention core runs inside attn_block_fwd; 4 and 16 heads run attn_fwd + attn_out_fwd.
+configs[4] (B=16, T=1024).  At 8 heads and L <= 128 the attention core runs inside attn_block_fwd; the other head counts run attn_fwd +
+attn_out_fwd.  Every ratio is against the 8-head step of the same shape, which is measured first.
 
-    python tools/heads_rate.py [--steps 20] [--regions 5]        # output committed as profiles/heads_rate.txt
+    python tools/heads_rate.py [--heads 1 2 4 8 16] [--steps 20] [--regions 5]        # output committed as profiles/heads_rate.txt
 """
 import argparse
 import os
@@ -59,11 +60,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--regions', type=int, default=5)
+    ap.add_argument('--heads', type=int, nargs='+', default=[4, 16], help='head counts to measure besides 8 (8 always runs first)')
     a = ap.parse_args()
     print('device: %s   median of %d regions x %d steps, train mode, drop 0.2' % (torch.cuda.get_device_name(), a.regions, a.steps))
     for name, B, T in SHAPES:
         ref = None
-        for heads in (8, 4, 16):
+        for heads in [8] + [h for h in a.heads if h != 8]:
             ms, per = run(name, B, T, heads, a.steps, a.regions)
             ref = ms if heads == 8 else ref
             print('%-10s B=%-3d T=%-5d heads %-2d  %8.3f ms/step  (%.3fx the 8-head step)' % (name, B, T, heads, ms, ms / ref))

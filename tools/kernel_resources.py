@@ -1,6 +1,7 @@
 """Per-kernel register / LDS / code-size table of the product library, from the compiler's own resource report (no GPU needed):
 
     python tools/kernel_resources.py > profiles/r06_kernel_resources.txt
+    python tools/kernel_resources.py kernels_attn_wide.hip > profiles/attn_wide_resources.txt      # some translation units only
 
 Columns: VGPRs + AGPRs one wave allocates (gfx950: 512 per SIMD lane, shared by every resident wave of the SIMD), waves per SIMD one workgroup
 brings (threads / 256), the share of a SIMD's register file ONE workgroup takes, static LDS, code bytes.  A CU hosts two workgroups only if
@@ -26,7 +27,7 @@ def demangle(names):
 
 def main():
     rows = []
-    for src in SOURCES:
+    for src in sys.argv[1:] or SOURCES:
         if src == 'api.hip':
             continue
         cmd = [_hipcc()] + [f for f in FLAGS if f != '-fPIC'] + FILE_FLAGS.get(src, []) + ['--cuda-device-only', '-S', os.path.join(CSRC, src), '-o', '/tmp/_kr.s']

@@ -1,11 +1,11 @@
-"""Golden fixtures for num_heads 4 and 16, produced by running the REFERENCE itself (build container only; never on the GPU box).
+"""Golden fixtures for num_heads 1, 2, 4 and 16, produced by running the REFERENCE itself (build container only; never on the GPU box).
 
-    python tools/make_golden_heads.py
+    python tools/make_golden_heads.py [NAME ...]        # default: every case below
 
 Each case is oracle/make_golden.py's `tiny_tf` spec with another head count, written by its own `run_case` (oracle/ is imported, not changed).
 A fixture holds about 2.4 MB of float32 data that does not compress, so it is stored as `tests/golden/<name>.npz` (config, inputs, checksums,
 taps, outputs and the first gradients) plus `<name>.part<k>.npz` files with the remaining gradients, each under 1 MiB.
-tests/test_attention_heads.py (load_heads_golden) merges them.
+tests/test_attention_heads.py (load_heads_golden) merges them; tests/test_attention_heads_wide.py reads heads1_tf / heads2_tf the same way.
 """
 import glob
 import os
@@ -21,7 +21,7 @@ from oracle.make_golden import CASES, load_reference, run_case  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 PART_BYTES = 900 * 1024          # raw bytes per file (float32 gradients compress by a few per cent at most)
-HEAD_CASES = {'heads4_tf': 4, 'heads16_tf': 16}
+HEAD_CASES = {'heads4_tf': 4, 'heads16_tf': 16, 'heads1_tf': 1, 'heads2_tf': 2}
 
 
 def split(name):
@@ -53,7 +53,9 @@ def split(name):
 def main():
     VSLNet, _, _ = load_reference()
     torch.set_num_threads(8)
-    for name, heads in HEAD_CASES.items():
+    names = sys.argv[1:] or list(HEAD_CASES)
+    for name in names:
+        heads = HEAD_CASES[name]
         over, B, T, Lq, Lc, ragged = CASES['tiny_tf']
         run_case(VSLNet, name, (dict(over, num_heads=heads), B, T, Lq, Lc, ragged))
         split(name)

@@ -628,7 +628,9 @@ void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
         LAUNCH("attn_block_fwd", launch_attn_block_fwd(ab, Bn, c.s));
         return;
     }
-    if (H != 8)      // head sizes 32 / 8: kernels_attn_hd.hip (no L <= 128 fusion)
+    if (H <= 2)      // head sizes 128 / 64: kernels_attn_wide.hip (no L <= 128 fusion)
+        LAUNCH("attn_fwd", launch_attn_wide_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.W(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
+    else if (H != 8)      // head sizes 32 / 8: kernels_attn_hd.hip (no L <= 128 fusion)
         LAUNCH("attn_fwd", launch_attn_hd_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.W(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
     else
         LAUNCH("attn_fwd", launch_attn_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.W(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
@@ -908,6 +910,9 @@ void enc_bwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
     if (attn_dq_query_major(L))      // L > ATTN_SLAB_MAX_L, every head count: dK / dV key-major + dQ query-major into slab 0 (kernels_attn_long.hip)
         LAUNCH("attn_bwd", launch_attn_bwd_any(c.W(w.q), c.W(w.k), c.W(w.v), c.W(w.att), c.W(t.dr), c.W(w.lse), mask, c.W(t.dq), c.W(t.dk),
                                    c.W(t.dv), Bn, L, H, 0, c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.s));
+    else if (H <= 2)      // head sizes 128 / 64: kernels_attn_wide.hip (dK / dV key-major, dQ query-major as attn_bwd_dq_slabs(L) slabs)
+        LAUNCH("attn_bwd", launch_attn_wide_bwd(c.W(w.q), c.W(w.k), c.W(w.v), c.W(w.att), c.W(t.dr), c.W(w.lse), mask, c.W(t.dq), c.W(t.dk),
+                                    c.W(t.dv), Bn, L, H, 0, c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.s, false));
     else if (H != 8)      // head sizes 32 / 8: kernels_attn_hd.hip (dQ in attn_bwd_dq_slabs(L) slabs as well)
         LAUNCH("attn_bwd", launch_attn_hd_bwd(c.W(w.q), c.W(w.k), c.W(w.v), c.W(w.att), c.W(t.dr), c.W(w.lse), mask, c.W(t.dq), c.W(t.dk),
                                   c.W(t.dv), Bn, L, H, 0, c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.s));
@@ -1652,7 +1657,7 @@ int vsl_create(const vsl_config* cfg, vsl_handle* out) {
     if (cfg->num_heads <= 0 || cfg->dim % cfg->num_heads != 0)
         return fail("The channels (%d) is not a multiple of attention heads (%d)", cfg->dim, cfg->num_heads);   // layers_t7.py:146
     if (!attn_heads_supported(cfg->num_heads))
-        return fail("num_heads=%d: the attention kernels support num_heads 4, 8 and 16 (head sizes 32, 16 and 8)", cfg->num_heads);
+        return fail("num_heads=%d: the attention kernels support num_heads 1, 2, 4, 8 and 16 (head sizes 128, 64, 32, 16 and 8)", cfg->num_heads);
     if (cfg->predictor != 0 && cfg->predictor != 1) return fail("predictor must be 0 ('rnn') or 1 ('transformer'), got %d", cfg->predictor);
     if (cfg->video_feature_dim <= 0 || cfg->video_feature_dim % 4) return fail("video_feature_dim=%d must be a positive multiple of 4 (rows are read as float4)", cfg->video_feature_dim);
     if ((cfg->word_dim + 100) % 8) return fail("word_dim + 100 = %d must be a multiple of 8", cfg->word_dim + 100);

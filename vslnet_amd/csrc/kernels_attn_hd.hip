@@ -1,5 +1,6 @@
 // Attention core of num_heads 4 and 16 (head sizes 32 and 8), forward and backward.  The 16-wide kernels of 8 heads (k_attn_fwd,
-// k_attn_bwd_fused, k_attn_bwd_long, k_attn_block_fwd) are untouched; api.hip routes every H != 8 shape here, L <= 128 included.
+// k_attn_bwd_fused, k_attn_bwd_long, k_attn_block_fwd) are untouched; api.hip routes every H = 4 / 16 shape here, L <= 128 included
+// (num_heads 1 / 2, head sizes 128 / 64: kernels_attn_wide.hip).
 //   a8 (:174-182)  S = Q K^T / sqrt(hd) + (1 - mask[key]) * -1e30 ; P = softmax ; O = drop(P) V
 // Same contracts as the 16-wide pair: Q / K / V / att are (R, 128) rows with head h at columns h hd .. h hd + hd - 1, LSE is saved per
 // (b, h, q) in natural-log units, and dQ leaves the backward as attn_bwd_dq_slabs(L) partial slabs (one per 256-key block) that k_qkv_bwd adds.

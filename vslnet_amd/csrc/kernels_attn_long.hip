@@ -1,4 +1,5 @@
-// Attention backward of long videos (1024 < L <= MAX_L): dQ query-major, for every head size (16, 32 and 8: num_heads 8, 4 and 16).
+// Attention backward of long videos (1024 < L <= MAX_L): dQ query-major, for every head size (16, 32 and 8: num_heads 8, 4 and 16 here;
+// 128 and 64, num_heads 1 and 2, with the query-major dQ kernel of kernels_attn_wide.hip, which launch_attn_bwd_any hands them to).
 //   a8 (:174-182)  S = Q K^T / sqrt(hd) + (1 - mask[key]) * -1e30 ; P = softmax ; O = drop(P) V
 // The key-major kernels (k_attn_bwd_long, k_attn_hd_bwd) run one workgroup per 256-key block; their dQ is a partial over that block, so up to
 // L = 1024 it leaves them as attn_bwd_dq_slabs(L) (R, 128) slabs that k_qkv_bwd adds.  That workspace and the extra reads grow as L^2 / 256.
@@ -185,6 +186,10 @@ int attn_dq_slabs(int L) { return attn_dq_query_major(L) ? 1 : attn_bwd_dq_slabs
 void launch_attn_bwd_any(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
                          const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2, Drop d3, hipStream_t s) {
     const bool qmaj = attn_dq_query_major(L);
+    if (H <= 2) {   // head sizes 128 / 64: their own dK / dV and query-major dQ kernels (kernels_attn_wide.hip)
+        launch_attn_wide_bwd(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, qmaj);
+        return;
+    }
     if (H != 8) launch_attn_hd_bwd(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, !qmaj);
     else launch_attn_bwd(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, !qmaj);
     if (!qmaj) return;

@@ -352,6 +352,14 @@ void launch_attn_hd_fwd(const float* Q, const float* K, const float* V, const fl
 void launch_attn_hd_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
                         const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
                         Drop d3, hipStream_t s, bool dq = true);
+// the attention core of num_heads 1 / 2 (head sizes 128 / 64; kernels_attn_wide.hip), every L: the same contracts.  The backward is a key-major
+// dK / dV kernel plus a query-major dQ kernel; query_major = false: dQ as attn_bwd_dq_slabs(L) partial slabs (one per 256-key block),
+// true (L > ATTN_SLAB_MAX_L): the complete dQ in slab 0 -- attn_dq_slabs(L) either way
+void launch_attn_wide_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
+                          int L, int H, int b_off, Drop d2, hipStream_t s);
+void launch_attn_wide_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
+                          const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
+                          Drop d3, hipStream_t s, bool query_major);
 // the attention backward of every head count (kernels_attn_long.hip): L <= ATTN_SLAB_MAX_L (or VSL_ATTN_DQ_SLABS=1) = the launchers above;
 // longer = their dK / dV-only instantiations + k_attn_dq, which writes the complete dQ into slab 0.  attn_dq_slabs(L): the slabs k_qkv_bwd
 // adds (and the plan allocates) on that route
@@ -359,7 +367,7 @@ void launch_attn_bwd_any(const float* Q, const float* K, const float* V, const f
                          const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2, Drop d3, hipStream_t s);
 bool attn_dq_query_major(int L);
 int attn_dq_slabs(int L);
-inline bool attn_heads_supported(int H) { return H == 4 || H == 8 || H == 16; }
+inline bool attn_heads_supported(int H) { return H == 1 || H == 2 || H == 4 || H == 8 || H == 16; }
 void launch_qkv_bwd(const float* dQ, const float* dK, const float* dV, const float* x, const float* dr,
                     const float* ln_g, const uint16_t* WT3 /* split pack of the (384, 128) operand */, float* dx, float* p_lng, float* p_lnb, int R,
                     Drop d1, hipStream_t s, int dq_slabs = 1);
