@@ -99,10 +99,17 @@ typedef struct {
      * the loss launch leaves the dependent chain: the span heads' and the highlight layer's backward compute their seeds from the logits
      * themselves (VSLNet_t7.py:67-72 and main_t7.py:107-110 as one call). */
     const struct vsl_loss_io* fused_loss;
+    /* INFERENCE mode (0 = off: everything above): a forward that will never be differentiated.  The forward kernels store only what a later
+     * forward kernel reads (no saved activation, no ReLU words, no LSE), and `workspace` needs vsl_inference_workspace_floats() floats only:
+     * a forward-only plan whose buffers are reused by liveness.  The outputs are bit for bit those of vsl_forward with training = 0.
+     * Excludes `training` (there is no dropout in this mode).  vsl_backward on this io, or in this workspace before another training forward
+     * has run in it, is an error, and so is vsl_workspace_offset: there is nothing saved.  vsl_loss and the launch ledger work.
+     * This is evaluation under torch.no_grad() (runner.eval_test, main.py --mode test); the reference has no counterpart. */
+    int32_t inference;
 } vsl_io;
 /* Every struct of this header must be zero-initialised by the caller before the fields are set: new optional fields are appended, and
  * zero means "off".  vsl_abi_version() changes whenever a struct layout or an entry point's meaning changes; a binding checks it once. */
-#define VSL_ABI_VERSION 8
+#define VSL_ABI_VERSION 9
 int vsl_abi_version(void);
 
 /* labels + weights for the fused loss (replaces compute_loss / compute_highlight_loss, VSLNet_t7.py:67-72, and the
@@ -134,8 +141,12 @@ int vsl_param_info(vsl_handle h, int index, char* name, int name_cap, int64_t* o
                    int64_t dims[4]);
 int64_t vsl_param_floats(vsl_handle h);
 
-/* number of floats the caller must provide in vsl_io.workspace for this shape */
+/* number of floats the caller must provide in vsl_io.workspace for this shape (the training plan: every saved activation, the backward's
+ * temporaries and partial slabs; also enough for an inference forward of the same shape) */
 int vsl_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, int64_t* out);
+/* the same for a forward with vsl_io.inference != 0: the forward-only plan (a handful of live (B T, 128) tensors; never more than
+ * vsl_workspace_floats() of the shape).  A shape whose training plan exceeds the 2^31-float limit may still fit this one.  No reference counterpart. */
+int vsl_inference_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, int64_t* out);
 
 /* VSLNet.forward (VSLNet_t7.py:52-62) */
 int vsl_forward(vsl_handle h, const vsl_io* io, void* hip_stream);
@@ -193,7 +204,8 @@ typedef struct vsl_fused_step {
     float* grad_norm_out;      /* optional */
 } vsl_fused_step;
 
-/* workspace introspection for the parity tests: float offset of a named saved activation, -1 if unknown.
+/* workspace introspection for the parity tests: float offset of a named saved activation, -1 if unknown, -2 (and vsl_last_error()) when the
+ * handle's last forward was an inference forward, which saves nothing.
  * names: "video_affine", "embedding_net", "venc", "qenc", "cq_attention", "cq_concat", "gated", "pred_s", "pred_e" */
 int64_t vsl_workspace_offset(vsl_handle h, int B, int T, int Lq, int Lc, const char* name);
 

@@ -12,7 +12,7 @@ name = sys.argv[2] if len(sys.argv) > 2 else 'base'          # -> vslnet_amd/lib
 tmp = '/tmp/vsl_base_src'
 files = ['vslnet_amd/csrc/api.hip', 'vslnet_amd/csrc/kernels_fwd.hip', 'vslnet_amd/csrc/kernels_bwd.hip', 'vslnet_amd/csrc/kernels_enc.hip',
          'vslnet_amd/csrc/kernels_wgrad.hip', 'vslnet_amd/csrc/kernels_split.hip', 'vslnet_amd/csrc/kernels_lstm.hip', 'vslnet_amd/csrc/kernels_query.hip', 'vslnet_amd/csrc/kernels_attn_hd.hip',
-         'vslnet_amd/csrc/kernels_attn_long.hip', 'vslnet_amd/csrc/common.hpp', 'vslnet_amd/csrc/launch.hpp', 'vslnet_amd/csrc/tile_bodies.hpp', 'include/vslnet_hip.h']
+         'vslnet_amd/csrc/kernels_attn_long.hip', 'vslnet_amd/csrc/kernels_attn_wide.hip', 'vslnet_amd/csrc/common.hpp', 'vslnet_amd/csrc/launch.hpp', 'vslnet_amd/csrc/tile_bodies.hpp', 'include/vslnet_hip.h']
 for f in files:
     os.makedirs(os.path.dirname(os.path.join(tmp, f)), exist_ok=True)
     try:

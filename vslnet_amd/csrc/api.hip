@@ -64,6 +64,7 @@ struct SlabRec { int dst, n, nslabs, ss, rl, ds, vn; int64_t src; };
 
 struct Plan {
     int B, T, Lq, Lc;
+    int kind = 0;                       // 0: training plan (every save + the whole backward) ; 1: inference plan (build_infer_plan: what the forward keeps live, reused by liveness)
     int64_t pack, vf, E, argpos, qf;
     EncWs ve, qe, p1, p2;
     LstmWs lstm[2];
@@ -108,7 +109,9 @@ struct vsl_handle_s {
     const float* sq_src = nullptr;       // the last vsl_backward's per-block sums of squares (Plan::sq_dev), their count, the bucket they describe
     int sq_n = 0;
     const float* sq_grads = nullptr;
-    std::map<std::tuple<int, int, int, int>, Plan*> plans;
+    std::map<std::tuple<int, int, int, int, int>, Plan*> plans;      // key: B, T, Lq, Lc, kind
+    const void* infer_ws = nullptr;      // workspace the last INFERENCE forward ran in (it holds no saves: vsl_backward on it is refused) ; a training forward in it clears this
+    bool last_infer = false;             // the handle's last forward was an inference forward (vsl_workspace_offset then has nothing to point at)
     uint64_t plan_clock = 0;
     // side streams for the independent chains (query branch, weight gradients) + fork/join events
     hipStream_t side[2] = {nullptr, nullptr};
@@ -443,6 +446,9 @@ struct Ctx {
     const vsl_loss_io* pend_loss = nullptr;   // vsl_io.fused_loss off the dependent chain: launched on the weight-gradient stream behind its first ordering point (loss_on_side)
     int pw_rows = 0;                    // rows per chunk of the NEXT enc_bwd's pointwise weight-gradient jobs (0 = WG_ROWS): the step's last batch, run_backward
     bool defer_w = false;
+    bool inf() const { return p->kind == 1; }
+    // a tensor only the backward reads: its address in a training forward, nullptr in an inference forward (the kernels then do not store it)
+    float* SV(int64_t off) const { return p->kind == 1 ? nullptr : ws + off; }
     const float* P(int off) const { return io->params + off; }
     const float* PK(int off) const { return ws + p->pack + off; }
     float* W(int64_t off) const { return ws + off; }
@@ -602,13 +608,13 @@ void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
         CbFwdArgs a;
         memset(&a, 0, sizeof a);
         if (!c.dry) {
-            a.xin = xin; a.pos = c.P(P.pos); a.x0_out = c.W(w.x0);
+            a.xin = xin; a.pos = c.P(P.pos); a.x0_out = c.SV(w.x0); a.nosave = c.inf();
             for (int i = 0; i < 4; ++i) {
                 a.ln_g[i] = c.P(P.lng[i]); a.ln_b[i] = c.P(P.lnb[i]); a.dw_w[i] = c.P(P.dw[i]);
-                a.pw_b[i] = c.P(P.pwb[i]); a.y[i] = c.W(w.y[i]); a.u[i] = c.W(w.u[i]);
-                a.relu_mask[i] = reinterpret_cast<uint32_t*>(c.W(w.mask[i])); a.dp[i] = c.drop(app * 16 + i);
+                a.pw_b[i] = c.P(P.pwb[i]); a.y[i] = i == 3 ? c.W(w.y[i]) : c.SV(w.y[i]); a.u[i] = c.SV(w.u[i]);      // (y[3]: the attention block's residual input)
+                a.relu_mask[i] = reinterpret_cast<uint32_t*>(c.SV(w.mask[i])); a.dp[i] = c.drop(app * 16 + i);
             }
-            a.qf = QkvFuse{c.P(P.ln1g), c.P(P.ln1b), c.P(P.qb), c.P(P.kb), c.P(P.vb), c.W(w.h1), c.W(w.q), c.W(w.k), c.W(w.v),
+            a.qf = QkvFuse{c.P(P.ln1g), c.P(P.ln1b), c.P(P.qb), c.P(P.kb), c.P(P.vb), c.SV(w.h1), c.W(w.q), c.W(w.k), c.W(w.v),
                            c.drop(app * 16 + 4)};
             for (int i = 0; i < 4; ++i) a.W3[i] = reinterpret_cast<const uint16_t*>(c.PK(K.pw_f3[i]));
             a.Wqkv3 = reinterpret_cast<const uint16_t*>(c.PK(K.qkv_f3));
@@ -621,20 +627,21 @@ void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
         memset(&ab, 0, sizeof ab);
         if (!c.dry) {
             ab = AttnBlockArgs{c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob),
-                               c.W(w.att), c.W(w.lse), c.W(w.r), c.W(w.h2), c.W(w.out), L, 0,
+                               c.SV(w.att), c.SV(w.lse), c.SV(w.r), c.SV(w.h2), c.W(w.out), L, 0,
                                c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8)};
+            ab.nosave = c.inf();
             if (ht) { ab.head_tail = 1; ab.hs = ht->hs; ab.he = ht->he; ab.head_x = ht->x; ab.head_vmask = ht->vmask; }
         }
         LAUNCH("attn_block_fwd", launch_attn_block_fwd(ab, Bn, c.s));
         return;
     }
     if (H <= 2)      // head sizes 128 / 64: kernels_attn_wide.hip (no L <= 128 fusion)
-        LAUNCH("attn_fwd", launch_attn_wide_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.W(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
+        LAUNCH("attn_fwd", launch_attn_wide_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.SV(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
     else if (H != 8)      // head sizes 32 / 8: kernels_attn_hd.hip (no L <= 128 fusion)
-        LAUNCH("attn_fwd", launch_attn_hd_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.W(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
+        LAUNCH("attn_fwd", launch_attn_hd_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.SV(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
     else
-        LAUNCH("attn_fwd", launch_attn_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.W(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
-    LAUNCH("attn_out_fwd", launch_attn_out_fwd(c.W(w.att), c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob), c.W(w.r), c.W(w.h2),
+        LAUNCH("attn_fwd", launch_attn_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.SV(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
+    LAUNCH("attn_out_fwd", launch_attn_out_fwd(c.W(w.att), c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob), c.SV(w.r), c.SV(w.h2),
                         c.W(w.out), R, c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8), c.s));
 }
 
@@ -739,7 +746,7 @@ void run_forward(Ctx& c) {
     c.s = qlong ? c.main : sq;
     const bool wt = cf.word_table != 0;       // trainable word table: its rows 0, 1, 2.. are pad, unk, the vocabulary
     LAUNCH("embed_fwd", launch_embed_fwd(io.word_ids, io.char_ids, wt ? c.P(P.unk) : io.pad_vec, c.P(P.unk) + (wt ? cf.word_dim : 0), wt ? c.P(P.unk) + 2 * cf.word_dim : io.glove_vec, c.P(P.char_tab), char_ptrs(c), c.PK(K.ccw_img), c.W(p.E),
-                     reinterpret_cast<int8_t*>(c.W(p.argpos)), Rq, p.Lc, cf.word_dim, cf.char_dim, c.drop(SITE_WORD),
+                     reinterpret_cast<int8_t*>(c.SV(p.argpos)), Rq, p.Lc, cf.word_dim, cf.char_dim, c.drop(SITE_WORD),
                      c.drop(SITE_CHAR), c.s));
     if (split3 && !c.dry) {                // behind embed_fwd: the shared encoder's packs (main stream) and the Embedding linear's (third stream)
         for (int k = 0; k < 2; ++k) {
@@ -756,18 +763,18 @@ void run_forward(Ctx& c) {
         memset(&qa, 0, sizeof qa);
         if (!c.dry) {
             const EncP& E = P.fe; const EncPk& EK = K.fe; const EncWs& w = p.qe;
-            qa.E = c.W(p.E); qa.Wemb3 = reinterpret_cast<const uint16_t*>(c.PK(K.emb_f3)); qa.b_emb = c.P(P.emb_b); qa.qf = c.W(p.qf);
-            qa.pos = c.P(E.pos); qa.x0 = c.W(w.x0);
+            qa.E = c.W(p.E); qa.Wemb3 = reinterpret_cast<const uint16_t*>(c.PK(K.emb_f3)); qa.b_emb = c.P(P.emb_b); qa.qf = c.SV(p.qf); qa.nosave = c.inf();
+            qa.pos = c.P(E.pos); qa.x0 = c.SV(w.x0);
             for (int i = 0; i < 4; ++i) {
                 qa.W3[i] = reinterpret_cast<const uint16_t*>(c.PK(EK.pw_f3[i]));
                 qa.ln_g[i] = c.P(E.lng[i]); qa.ln_b[i] = c.P(E.lnb[i]); qa.dw_w[i] = c.P(E.dw[i]); qa.pw_b[i] = c.P(E.pwb[i]);
-                qa.y[i] = c.W(w.y[i]); qa.u[i] = c.W(w.u[i]); qa.relu_mask[i] = reinterpret_cast<uint32_t*>(c.W(w.mask[i])); qa.dp[i] = c.drop(16 + i);
+                qa.y[i] = c.SV(w.y[i]); qa.u[i] = c.SV(w.u[i]); qa.relu_mask[i] = reinterpret_cast<uint32_t*>(c.SV(w.mask[i])); qa.dp[i] = c.drop(16 + i);
             }
             qa.Wqkv3 = reinterpret_cast<const uint16_t*>(c.PK(EK.qkv_f3)); qa.Wo3 = reinterpret_cast<const uint16_t*>(c.PK(EK.o_f3));
             qa.ln1_g = c.P(E.ln1g); qa.ln1_b = c.P(E.ln1b); qa.bq = c.P(E.qb); qa.bk = c.P(E.kb); qa.bv = c.P(E.vb);
-            qa.h1 = c.W(w.h1); qa.q = c.W(w.q); qa.k = c.W(w.k); qa.v = c.W(w.v); qa.d1 = c.drop(16 + 4);
+            qa.h1 = c.SV(w.h1); qa.q = c.SV(w.q); qa.k = c.SV(w.k); qa.v = c.SV(w.v); qa.d1 = c.drop(16 + 4);
             qa.mask = io.q_mask; qa.ln2_g = c.P(E.ln2g); qa.ln2_b = c.P(E.ln2b); qa.bo = c.P(E.ob);
-            qa.att = c.W(w.att); qa.lse = c.W(w.lse); qa.r = c.W(w.r); qa.h2 = c.W(w.h2); qa.out = c.W(w.out);
+            qa.att = c.SV(w.att); qa.lse = c.SV(w.lse); qa.r = c.SV(w.r); qa.h2 = c.SV(w.h2); qa.out = c.W(w.out);
             qa.d2 = c.drop(16 + 5); qa.d3 = c.drop(16 + 6); qa.d4 = c.drop(16 + 7); qa.d5 = c.drop(16 + 8);
             qa.EW = cf.word_dim + 100; qa.L = Lq; qa.b_off = 0;
         }
@@ -786,17 +793,17 @@ void run_forward(Ctx& c) {
     // one launch and one boundary less on the dependent chain (VSL_CQ_FOLD=0: three launches)
     static const bool fold_on = !(getenv("VSL_CQ_FOLD") && getenv("VSL_CQ_FOLD")[0] == '0');
     const bool cq_fold = fold_on && cq_col_folds(T, Lq);
-    const CqPoolArgs pool{c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b), c.W(p.alpha), c.W(p.pooled), c.W(p.pb)};
+    const CqPoolArgs pool{c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb)};
     LAUNCH("cq_score", launch_cq_score(c.W(p.ve.out), c.W(p.qe.out), io.q_mask, c.P(P.w4C), c.P(P.w4Q), c.P(P.w4mlu), c.W(p.S), c.W(p.Srow), B, T,
                     Lq, 0, c.drop(SITE_CQ_C), c.drop(SITE_CQ_Q), c.s, cq_fold ? &pool : nullptr));
     // M = S_col^T C is produced as per-tile partials (the backward's cqP1 arena is free until then) and summed by cq_out
     if (!cq_fold)
         LAUNCH("cq_col", launch_cq_col(c.W(p.ve.out), c.W(p.qe.out), c.W(p.S), io.v_mask, io.q_mask, c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b),
-                      c.W(p.Scol), c.W(p.cqP1), c.W(p.alpha), c.W(p.pooled), c.W(p.pb), B, T, Lq, c.s));
+                      c.SV(p.Scol), c.W(p.cqP1), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb), B, T, Lq, c.s));
     // cq_out also carries CQConcatenate + HighLightLayer + gating (row-local on the tile it produces)
-    LAUNCH("cq_out", launch_cq_out(c.W(p.ve.out), c.W(p.qe.out), c.W(p.Srow), c.W(p.cqP1), c.W(p.M), c.PK(K.cqa_f), c.P(P.cqa_b), c.W(p.cat),
-                  c.W(p.f1), c.PK(K.cat1_f), c.W(p.pb), c.P(P.hl_w), c.P(P.hl_b), io.v_mask, c.W(p.f2), io.h_score, c.W(p.gated), B, T, Lq,
-                  c.s, cq_fold ? c.W(p.S) : nullptr, cq_fold ? c.W(p.Scol) : nullptr));
+    LAUNCH("cq_out", launch_cq_out(c.W(p.ve.out), c.W(p.qe.out), c.W(p.Srow), c.W(p.cqP1), c.SV(p.M), c.PK(K.cqa_f), c.P(P.cqa_b), c.SV(p.cat),
+                  c.SV(p.f1), c.PK(K.cat1_f), c.W(p.pb), c.P(P.hl_w), c.P(P.hl_b), io.v_mask, c.SV(p.f2), io.h_score, c.W(p.gated), B, T, Lq,
+                  c.s, cq_fold ? c.W(p.S) : nullptr, cq_fold ? c.SV(p.Scol) : nullptr));
     if (cf.predictor == 0) {
         // rnn head (:341-343): start = LSTM_s(x) * mask ; end = LSTM_e(start) * mask ; no LayerNorm in front of the span blocks
         // The recurrence is latency bound (one sample per CU, 0.6 us per step).  Up to RNN_FUSED_MAX_B samples the whole head is ONE launch: start
@@ -807,8 +814,8 @@ void run_forward(Ctx& c) {
         const std::vector<int> chunks = lstm_chunks(T);
         auto lstm = [&](int l, int t0, int t1) {
             const LstmWs& w = p.lstm[l];
-            LAUNCH("lstm_fwd", launch_lstm_fwd(c.W(w.gi), c.P(P.l_whh[l]), c.PK(K.l_hf[l]), c.P(P.l_bih[l]), c.P(P.l_bhh[l]), io.v_mask, c.W(w.gates),
-                                               c.W(w.cseq), c.W(w.tseq), c.W(w.hprev), c.W(w.out), B, T, c.s, t0, t1));
+            LAUNCH("lstm_fwd", launch_lstm_fwd(c.W(w.gi), c.P(P.l_whh[l]), c.PK(K.l_hf[l]), c.P(P.l_bih[l]), c.P(P.l_bhh[l]), io.v_mask, c.SV(w.gates),
+                                               c.W(w.cseq), c.SV(w.tseq), c.W(w.hprev), c.W(w.out), B, T, c.s, t0, t1));      // (cseq, hprev: a later chunk resumes from them)
         };
         // gate projections gi = x W_ih^T: (rows,128) x (128,512), no bias, bf16x6 on the matrix cores
         auto gi = [&](int l, const float* x, int rows, int seg = 0, int off = 0) {
@@ -824,11 +831,11 @@ void run_forward(Ctx& c) {
             for (int l = 0; l < 2; ++l) {
                 const LstmWs& w = p.lstm[l];
                 a.Whh[l] = c.PK(K.l_hf[l]); a.bih[l] = c.P(P.l_bih[l]); a.bhh[l] = c.P(P.l_bhh[l]);
-                a.gates[l] = c.W(w.gates); a.cseq[l] = c.W(w.cseq); a.tseq[l] = c.W(w.tseq); a.hprev[l] = c.W(w.hprev); a.out[l] = c.W(w.out);
+                a.gates[l] = c.SV(w.gates); a.cseq[l] = c.SV(w.cseq); a.tseq[l] = c.SV(w.tseq); a.hprev[l] = c.SV(w.hprev); a.out[l] = c.W(w.out);
             }
             a.h_gran = reinterpret_cast<unsigned long long*>(c.W(p.h_gran)); a.gi_gran = reinterpret_cast<unsigned long long*>(c.W(p.gi_gran));
             long long gen = 0;
-            a.epoch = rnn_epoch(&gen); a.B = B; a.T = T;
+            a.epoch = rnn_epoch(&gen); a.B = B; a.T = T; a.nosave = c.inf();
             rnn_granules_fresh(c, *c.p, gen);
             LAUNCH("rnn_fwd", launch_rnn_fwd(a, c.s));
         } else if (chunks.size() < 2 || sq == main_s) {
@@ -855,16 +862,16 @@ void run_forward(Ctx& c) {
             }
             c.order(sq, main_s);
         }
-        HeadArgs hs{c.W(p.lstm[0].out), nullptr, nullptr, c.PK(K.s0_f), c.P(P.s0b), c.P(P.s1w), c.P(P.s1b), c.W(p.hid_s), nullptr, io.start_logits};
-        HeadArgs he{c.W(p.lstm[1].out), nullptr, nullptr, c.PK(K.e0_f), c.P(P.e0b), c.P(P.e1w), c.P(P.e1b), c.W(p.hid_e), nullptr, io.end_logits};
+        HeadArgs hs{c.W(p.lstm[0].out), nullptr, nullptr, c.PK(K.s0_f), c.P(P.s0b), c.P(P.s1w), c.P(P.s1b), c.SV(p.hid_s), nullptr, io.start_logits};
+        HeadArgs he{c.W(p.lstm[1].out), nullptr, nullptr, c.PK(K.e0_f), c.P(P.e0b), c.P(P.e1w), c.P(P.e1b), c.SV(p.hid_e), nullptr, io.end_logits};
         LAUNCH("head_fwd", launch_head_fwd(hs, he, c.W(p.gated), io.v_mask, R, c.s));
         return;
     }
     enc_fwd(c, P.pe, K.pe, p.p1, c.W(p.gated), io.v_mask, B, 2);
-    HeadArgs hs{c.W(p.p1.out), c.P(P.sln_g), c.P(P.sln_b), c.PK(K.s0_f), c.P(P.s0b), c.P(P.s1w), c.P(P.s1b), c.W(p.hid_s),
-                c.W(p.lnf_s), io.start_logits};
-    HeadArgs he{c.W(p.p2.out), c.P(P.eln_g), c.P(P.eln_b), c.PK(K.e0_f), c.P(P.e0b), c.P(P.e1w), c.P(P.e1b), c.W(p.hid_e),
-                c.W(p.lnf_e), io.end_logits};
+    HeadArgs hs{c.W(p.p1.out), c.P(P.sln_g), c.P(P.sln_b), c.PK(K.s0_f), c.P(P.s0b), c.P(P.s1w), c.P(P.s1b), c.SV(p.hid_s),
+                c.SV(p.lnf_s), io.start_logits};
+    HeadArgs he{c.W(p.p2.out), c.P(P.eln_g), c.P(P.eln_b), c.PK(K.e0_f), c.P(P.e0b), c.P(P.e1w), c.P(P.e1b), c.SV(p.hid_e),
+                c.SV(p.lnf_e), io.end_logits};
     // T <= 128: the second pass' attention-block kernel goes on with both span heads on its tiles (one launch less on the dependent chain)
     static const bool heads_on = !(getenv("VSL_HEADS_FUSED") && getenv("VSL_HEADS_FUSED")[0] == '0');
     const bool heads_hosted = heads_on && cf.num_heads == 8 && attn_block_fwd_hosts_heads(T);
@@ -1423,7 +1430,8 @@ void run_backward(Ctx& c) {
                                  p.sq_cover ? p.sq_dev : nullptr, p.nblocks));
 }
 
-int build_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
+// limits of a shape that are about addressing, not about the size of a plan (both plan kinds)
+int check_shape(vsl_handle_s* h, int B, int T, int Lq, int Lc) {
     const vsl_config& cf = h->cfg;
     if (B <= 0 || T <= 0 || Lq <= 0) return fail("empty batch (B=%d T=%d Lq=%d)", B, T, Lq);
     if (T > cf.max_pos_len || Lq > cf.max_pos_len)
@@ -1435,6 +1443,81 @@ int build_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
     if (Lq > MAX_LQ) return fail("Lq=%d > %d query words: the CQAttention kernels keep the whole query of a sample in LDS "
                                  "(the reference truncates at max_pos_len words, data_gen.py:188)", Lq, MAX_LQ);
     if (Lc < 4 || Lc > MAX_LC) return fail("Lc=%d must be in [4, %d] (the widest char conv has kernel 4, layers_t7.py:52)", Lc, MAX_LC);
+    if (cf.predictor == 0 && (int64_t)B * T * 4 * D >= (int64_t(1) << 31)) return fail("B*T = %lld too large for the 32-bit offsets of the LSTM kernels", (long long)B * T);
+    return 0;
+}
+
+// The inference plan (vsl_io.inference): what a forward keeps live and nothing else -- no saves, no backward temporaries, no partial arena, no
+// reduction tables.  Buffers are reused by liveness along the main stream's order (run_forward):
+//   region : y3, q, k, v, att of ONE encoder application -- the video pass, then both predictor passes; VisualProjection's output (dead once the
+//            video pass' conv block has run) sits in the att slot; between the video pass and the predictor the same floats hold the CQ kernels'
+//            S, Srow and the per-tile partials of M (the region is as large as the larger of the two uses); rnn: the start LSTM's gate projection
+//   a      : the video encoder's output, dead behind cq_out -> the second predictor pass' / the end LSTM's output
+//   gated, p1.out : live up to the span heads
+// The query branch runs beside the video pass on its own stream and has its own (B Lq)-row scratch.  The rnn head keeps the second gate projection
+// and its hand-off granules (B <= 80) or, for the chunked launches, the c_t / h_t sequences a later time chunk resumes from.
+// Every offset a forward does not use is -1 (Ctx::SV hands the kernels nullptr for those).
+int build_infer_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
+    if (int rc = check_shape(h, B, T, Lq, Lc)) return rc;
+    const vsl_config& cf = h->cfg;
+    Plan* p = new Plan();
+    p->kind = 1;
+    p->B = B; p->T = T; p->Lq = Lq; p->Lc = Lc;
+    const int64_t R = (int64_t)B * T, Rq = (int64_t)B * Lq, RD = ((R * D) + 3) & ~int64_t(3);
+    const int EW = cf.word_dim + 100;
+    auto none = [](EncWs& w, int64_t Rw, int L) {
+        w.x0 = w.h1 = w.q = w.k = w.v = w.lse = w.att = w.r = w.h2 = w.out = -1;
+        for (int i = 0; i < 4; ++i) w.y[i] = w.u[i] = w.mask[i] = -1;
+        w.R = (int)Rw; w.L = L;
+    };
+    none(p->ve, R, T); none(p->qe, Rq, Lq); none(p->p1, R, T); none(p->p2, R, T);
+    p->argpos = p->Scol = p->M = p->alpha = p->pooled = p->cat = p->f1 = p->f2 = p->hid_s = p->hid_e = p->lnf_s = p->lnf_e = -1;
+    p->gz_s = p->gz_e = p->dfeat_s = p->dfeat_e = p->dxh_s = p->dxh_e = p->g_s1 = p->g_gated = -1;
+    p->df2 = p->df1 = p->dC = p->dSr = p->dSs = p->dQtot = p->dvf = p->dqf = p->dE = p->cqP2 = p->cqP3 = p->cqP4 = p->cqP5 = -1;
+    for (EncTmp& t : p->tmp) { t.dr = t.dq = t.dk = t.dv = t.go = t.ga = -1; for (int64_t& g : t.gz) g = -1; }
+    for (LstmWs& w : p->lstm) w.gi = w.gates = w.cseq = w.tseq = w.hprev = w.out = w.dG = w.carry = -1;
+    Bump al;
+    p->pack = al(h->pack_floats);
+    p->loss_scratch = al(5 * (int64_t)B + 8);          // (vsl_loss on the outputs of an inference forward)
+    // the query branch's own scratch (beside the video pass on another stream)
+    p->E = al(Rq * EW); p->qf = al(Rq * D);
+    p->qe.y[3] = al(Rq * D); p->qe.q = al(Rq * D); p->qe.k = al(Rq * D); p->qe.v = al(Rq * D); p->qe.att = al(Rq * D); p->qe.out = al(Rq * D);
+    p->pb = al((int64_t)B * D);
+    // the region
+    const int64_t nt = (T + TILE_M - 1) / TILE_M;
+    const int64_t SL = ((R * Lq) + 3) & ~int64_t(3);
+    const int64_t cq_need = 2 * SL + (((int64_t)B * nt * Lq * D + 3) & ~int64_t(3));
+    const int64_t region = al(std::max(5 * RD, cq_need));
+    EncWs* seq[3] = {&p->ve, &p->p1, &p->p2};
+    for (EncWs* w : seq) { w->y[3] = region; w->q = region + RD; w->k = region + 2 * RD; w->v = region + 3 * RD; w->att = region + 4 * RD; }
+    p->vf = region + 4 * RD;
+    p->S = region; p->Srow = region + SL; p->cqP1 = region + 2 * SL;
+    p->ve.out = al(R * D);
+    p->gated = al(R * D);
+    p->p1.out = al(R * D);
+    p->p2.out = p->ve.out;
+    if (cf.predictor == 0) {
+        for (int l = 0; l < 2; ++l) {
+            LstmWs& w = p->lstm[l];
+            w.gi = l == 0 ? region : al(R * 4 * D);
+            if (!rnn_fused_ok(B)) { w.cseq = al(R * D); w.hprev = al(R * D); }      // chunked launches: a chunk resumes from the last c_t, h_t of the one before
+            w.out = l == 0 ? p->p1.out : p->p2.out;
+        }
+        if (rnn_fused_ok(B)) {
+            p->h_gran = al(R * 2 * D); p->gi_gran = al(R * 8 * D);
+            p->gran_floats = (p->gi_gran + R * 8 * D) - p->h_gran;      // the two allocations are consecutive
+        }
+    }
+    p->partial = al(0); p->partial_floats = 0;
+    p->total = al.cur;
+    if (p->total >= (int64_t(1) << 31)) { delete p; return fail("inference workspace of %lld floats exceeds the 2^31 offset range", (long long)p->total); }
+    *out = p;
+    return 0;
+}
+
+int build_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
+    if (int rc = check_shape(h, B, T, Lq, Lc)) return rc;
+    const vsl_config& cf = h->cfg;
     Plan* p = new Plan();
     p->B = B; p->T = T; p->Lq = Lq; p->Lc = Lc;
     const int64_t R = (int64_t)B * T, Rq = (int64_t)B * Lq;
@@ -1445,7 +1528,6 @@ int build_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
     plan_encoder(al, p->ve, B, T, H); plan_encoder(al, p->qe, B, Lq, H);
     const bool rnn = cf.predictor == 0;
     if (rnn) {
-        if (R * 4 * D >= (int64_t(1) << 31)) { delete p; return fail("B*T = %lld too large for the 32-bit offsets of the LSTM kernels", (long long)R); }
         p->p1.R = p->p2.R = (int)R; p->p1.L = p->p2.L = T;
         for (int l = 0; l < 2; ++l) {
             LstmWs& w = p->lstm[l];
@@ -1575,12 +1657,12 @@ void free_plan(Plan* p) {
 // shape a realistic run sees (64 entries thrashed under shuffled real-data batches) and evicts the least recently used one
 // beyond that.  (A forward and its backward use the same shape back to back, so a live plan is never evicted.)
 constexpr size_t MAX_PLANS = 2048;
-int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
-    auto key = std::make_tuple(B, T, Lq, Lc);
+int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, int kind = 0) {
+    auto key = std::make_tuple(B, T, Lq, Lc, kind);
     auto it = h->plans.find(key);
     if (it != h->plans.end()) { it->second->last_use = ++h->plan_clock; *out = it->second; return 0; }
     Plan* p = nullptr;
-    if (int rc = build_plan(h, B, T, Lq, Lc, &p)) return rc;
+    if (int rc = kind ? build_infer_plan(h, B, T, Lq, Lc, &p) : build_plan(h, B, T, Lq, Lc, &p)) return rc;
     if (h->plans.size() >= MAX_PLANS) {
         auto victim = h->plans.begin();
         for (auto jt = h->plans.begin(); jt != h->plans.end(); ++jt)
@@ -1781,8 +1863,17 @@ int vsl_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, int64_t* ou
     return 0;
 }
 
+int vsl_inference_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, int64_t* out) {
+    if (!h || !out) return fail("null argument");
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, B, T, Lq, Lc, &p, 1)) return rc;
+    *out = p->total;
+    return 0;
+}
+
 int64_t vsl_workspace_offset(vsl_handle h, int B, int T, int Lq, int Lc, const char* name) {
     Plan* p = nullptr;
+    if (h && h->last_infer) { fail("vsl_workspace_offset: the last forward saved nothing (inference mode): there is no saved activation to point at"); return -2; }
     if (!h || !name || get_plan(h, B, T, Lq, Lc, &p)) return -1;
     const std::string n = name;
     const std::pair<const char*, int64_t> tab[] = {
@@ -1819,13 +1910,17 @@ int64_t vsl_workspace_offset(vsl_handle h, int B, int T, int Lq, int Lc, const c
 
 int vsl_forward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
+    if (io->inference && io->training) return fail("vsl_forward: inference and training exclude each other (the inference kernels have no dropout)");
     Plan* p = nullptr;
-    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p)) return rc;
+    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, io->inference ? 1 : 0)) return rc;
     Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
     c.main = c.s;
     CallScope scope(h);
     run_forward(c);
     HIP_OK(hipGetLastError());
+    h->last_infer = io->inference != 0;
+    if (io->inference) h->infer_ws = io->workspace;
+    else if (h->infer_ws == io->workspace) h->infer_ws = nullptr;
     return 0;
 }
 
@@ -1835,7 +1930,7 @@ int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_str
     if ((l->d_h_score == nullptr) != (l->d_start_logits == nullptr) || (l->d_h_score == nullptr) != (l->d_end_logits == nullptr))
         return fail("gradient seed outputs must be all set or all null");
     Plan* p = nullptr;
-    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p)) return rc;
+    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, io->inference ? 1 : 0)) return rc;      // (its scratch lies where that forward's plan put it)
     ProfScope ps(h, "loss");
     launch_loss(io->start_logits, io->end_logits, io->h_score, l->start_labels, l->end_labels, l->h_labels, io->v_mask, io->B,
                 io->T, l->inv_batch, l->mask_sum, l->w_loc, l->w_highlight, io->workspace + p->loss_scratch, l->losses,
@@ -1862,6 +1957,8 @@ static int ensure_opt_state(vsl_handle_s* h) {
 
 int vsl_backward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
+    if (io->inference || io->workspace == h->infer_ws)
+        return fail("vsl_backward: the last forward saved nothing (inference mode): run vsl_forward with inference = 0 for a batch that is to be differentiated");
     if (const vsl_loss_io* l = io->fused_loss) {
         if (!l->start_labels || !l->end_labels || !l->h_labels || !l->losses) return fail("vsl_backward: fused_loss has a null pointer");
         if (!l->d_start_logits || !l->d_end_logits || !l->d_h_score) return fail("vsl_backward: fused_loss needs the three gradient seed outputs");

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void k_attn_hd_fwd(const float* __restrict__ Q
                 *reinterpret_cast<float4*>(att + (rowbase + q) * D + h * HDV + 16 * j + 4 * g) =
                     make_float4((o[j][0][0] + o[j][1][0]) * inv, (o[j][0][1] + o[j][1][1]) * inv,
                                 (o[j][0][2] + o[j][1][2]) * inv, (o[j][0][3] + o[j][1][3]) * inv);
-        if (g == 0) lse[((size_t)b * H + h) * L + q] = m * AH_LN2 + __logf(l);
+        if (g == 0 && lse) lse[((size_t)b * H + h) * L + q] = m * AH_LN2 + __logf(l);
     }
 }
 

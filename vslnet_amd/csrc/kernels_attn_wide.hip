@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void k_attn_wide_fwd(const float* __restrict__
             }
             *reinterpret_cast<float4*>(att + (rowbase + qo) * D + h * HDV + NT * cc + 4 * f) = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
         }
-        if (cc == 0) lse[((size_t)b * H + h) * L + qo] = M * AW_LN2 + __logf(sum);
+        if (cc == 0 && lse) lse[((size_t)b * H + h) * L + qo] = M * AW_LN2 + __logf(sum);
     }
 }
 

@@ -266,7 +266,7 @@ constexpr int CB_PS = 384;                      // per-layer small parameters in
 // Whole tiles (R and L multiples of 32, L > 32) take k_convblock_fwd2 below; this kernel serves sample tiles and ragged row tiles.
 // The five GEMMs run on the bf16 matrix cores at fp32 grade (gemm16s): the depthwise output / LN1 output is split into three bf16 planes
 // while it is stored (LDS +18 KB for the row tiles), the weight slices come from the split packs.
-template <int SH>
+template <int SH, bool SAVE = true>     // SAVE = false (inference): x0, u, the ReLU words, y0..y2 and h1 are not stored
 __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
     // sample tiles: 3 zero rows above and below the window in the LN / depthwise buffer stand for the taps that leave it
     constexpr int HL = 4 * SH, NW = TILE_M + 2 * HL, VOFF = SH ? 0 : HALO, VUR = SH ? NW + 12 : NW + 2 * HALO;
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
         if (e < NW * 32) {
             const float4 v = make_float4(xv[q].x + pv[q].x, xv[q].y + pv[q].y, xv[q].z + pv[q].z, xv[q].w + pv[q].w);
             const int r = rw0 + wr;
-            if (wr >= HL && wr < HL + TILE_M && (SH ? r < R : wr < L)) *reinterpret_cast<float4*>(a.x0_out + (size_t)r * D + c) = v;
+            if (SAVE && wr >= HL && wr < HL + TILE_M && (SH ? r < R : wr < L)) *reinterpret_cast<float4*>(a.x0_out + (size_t)r * D + c) = v;
             *reinterpret_cast<float4*>(&Xs[wr * LDP + c]) = v;
         }
     }
@@ -382,12 +382,14 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
                     t = t + 1 == L ? 0 : t + 1;
                 }
             }
-            float* ug = a.u[l] + (ptrdiff_t)(rw0 + os) * D + c;
+            if constexpr (SAVE) {
+                float* ug = a.u[l] + (ptrdiff_t)(rw0 + os) * D + c;
 #pragma unroll
-            for (int i = 0; i < QS; ++i) {
-                if (os + i < o0 + n) {                           // wave-uniform
-                    const int wr = os + i;
-                    if (wr >= HL && wr < HL + TILE_M && row_ok(wr)) ug[(ptrdiff_t)i * D] = uo[i];   // saved: A operand of the weight gradient
+                for (int i = 0; i < QS; ++i) {
+                    if (os + i < o0 + n) {                       // wave-uniform
+                        const int wr = os + i;
+                        if (wr >= HL && wr < HL + TILE_M && row_ok(wr)) ug[(ptrdiff_t)i * D] = uo[i];   // saved: A operand of the weight gradient
+                    }
                 }
             }
             {                                                    // GEMM operand: three bf16 planes, two channels of a row per dword
@@ -434,7 +436,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
             // (quad swaps, half-row mirror, row mirror), two rows per register.  Not __ballot: four ballots kept in SGPR pairs
             // across the rr loop came out wrong for the waves 4..7 of a workgroup, timing dependent
             // (tests/test_hip_parity.py::test_saved_relu_decisions_match_the_saved_activations).
-            if (owner_tile) {
+            if (SAVE && owner_tile) {
                 auto row_or = [](int v) {
                     v |= __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);       // quad_perm [1,0,3,2]
                     v |= __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);       // quad_perm [2,3,0,1]
@@ -453,7 +455,8 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
         if (l == 0) ESTAMP(11);
         __syncthreads();
         if (l == 0) ESTAMP(12);
-        // owner rows of the layer output -> memory (16-byte stores)
+        // owner rows of the layer output -> memory (16-byte stores); without the saves only the block output y3 leaves (the attention block's residual input)
+        if constexpr (SAVE || l == 3)
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int e = tid + q * CB_T;
@@ -475,7 +478,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
         const float* Pq = Ps + 4 * CB_PS;
         // LN1 output: three bf16 planes in the (now free) GEMM operand buffer, rows 0..31 ; h1 goes to memory straight from the registers
         const int gn = SH ? min(TILE_M, R - r0) : L;
-        ln_rows512_split(Xs + HL * LDP, Ub, UPS, TILE_M, Pq, Pq + 128, a.qf.d1, r0, a.qf.h1 ? a.qf.h1 + (size_t)r0 * D : nullptr, gn);
+        ln_rows512_split(Xs + HL * LDP, Ub, UPS, TILE_M, Pq, Pq + 128, a.qf.d1, r0, (SAVE && a.qf.h1) ? a.qf.h1 + (size_t)r0 * D : nullptr, gn);
         b3_load(b3B, a.Wqkv3, D, 3 * D, D + 16 * w);
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
@@ -541,7 +544,7 @@ __device__ __forceinline__ float4 buf_load4(brsrc_t r, uint32_t off) {
     return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
 }
 
-template <bool DROP>
+template <bool DROP, bool SAVE = true>     // SAVE = false (inference): only y3, q, k, v leave the workgroup
 __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
     constexpr int HL = 12, NW = TILE_M + 2 * HL, NT = CB_T;
     constexpr int LPR = 8, NJ = 32 / LPR;                      // LayerNorm: lanes per row, float4 columns per lane (4 sub + 4 LPR j)
@@ -593,7 +596,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
             const int e = tid + q * NT;
             const int wr = e >> 5, c = (e & 31) * 4;
             const float4 v = make_float4(xv[q].x + pv[q].x, xv[q].y + pv[q].y, xv[q].z + pv[q].z, xv[q].w + pv[q].w);
-            buf_store4(r0o, (e < NW * 32 && wr >= HL && wr < HL + TILE_M) ? (uint32_t)(((rw0 + wr) * D + c) * 4) : BUF_OOB, v);
+            if constexpr (SAVE) buf_store4(r0o, (e < NW * 32 && wr >= HL && wr < HL + TILE_M) ? (uint32_t)(((rw0 + wr) * D + c) * 4) : BUF_OOB, v);
             if (e < NW * 32) *reinterpret_cast<float4*>(&Xs[wr * LDP + c]) = v;
         }
     }
@@ -648,7 +651,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
             float4 v[NJ];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) v[j] = *reinterpret_cast<const float4*>(s + 4 * LPR * j);
-            if (l > 0) {
+            if (SAVE && l > 0) {
                 const brsrc_t ry = buf_rsrc(a.y[l > 0 ? l - 1 : 0], rbytes);
                 const uint32_t yo = (act && wr >= HL && wr < HL + TILE_M) ? (uint32_t)(((rw0 + wr) * D + sub * 4) * 4) : BUF_OOB;
 #pragma unroll
@@ -710,7 +713,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
                 const int row = os + i;
                 const bool rok = sact && row < o0 + n;           // wave-uniform
                 // saved: A operand of the weight gradient (owner rows; a wave stores whole 512-byte rows)
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{__float_as_uint(u.x), __float_as_uint(u.y)}, ru,
+                if constexpr (SAVE) __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{__float_as_uint(u.x), __float_as_uint(u.y)}, ru,
                                                       (rok && row >= HL && row < HL + TILE_M) ? (uint32_t)(((rw0 + row) * D + 2 * lane) * 4) : BUF_OOB, 0, 0);
                 if (rok) {
                     uint32_t th, tm, tl;
@@ -762,6 +765,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
                 av = h >= dp.thresh ? av * dp.scale : 0.f;
             }
             xb[(16 * i + rr) * LDP] = xold[rr] + av;
+            if constexpr (!SAVE) return;                         // (the ReLU bit words exist for the backward alone)
             const int bit = z > 0.f ? (mybit << (16 * (rr & 1))) : 0;
             if (rr == 0) pos01 = bit; else if (rr == 1) pos01 |= bit; else if (rr == 2) pos23 = bit; else pos23 |= bit;
             if (rr == 3) {
@@ -806,7 +810,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
         __syncthreads();
         if (l == 0) ESTAMP(11);
         // ReLU decisions of the owner rows: one 16-byte store per row (the (R, 4) uint32 words)
-        {
+        if constexpr (SAVE) {
             const u32x4_t mv = *reinterpret_cast<const u32x4_t*>(MB + (HL + (tid & 31)) * C2_MBW);
             __builtin_amdgcn_raw_buffer_store_b128(mv, buf_rsrc(a.relu_mask[l], (uint32_t)a.R * 16), tid < TILE_M ? (uint32_t)((r0 + tid) * 16) : BUF_OOB, 0, 0);
         }
@@ -864,7 +868,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
                     o0v.x *= drop_keep_scale(d1, base); o0v.y *= drop_keep_scale(d1, base + 1);
                     o1v.x *= drop_keep_scale(d1, base + 2); o1v.y *= drop_keep_scale(d1, base + 3);
                 }
-                buf_store4(rhb, go + 16 * LPR * j, make_float4(o0v.x, o0v.y, o1v.x, o1v.y));
+                if constexpr (SAVE) buf_store4(rhb, go + 16 * LPR * j, make_float4(o0v.x, o0v.y, o1v.x, o1v.y));
                 if (act) {
                     uint32_t h0, m0, l0, h1, m1, l1;
                     split3(o0v.x, o0v.y, h0, m0, l0);
@@ -918,22 +922,27 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
 constexpr size_t cb_fwd2_lds() {
     return (size_t)((C2_XR + C2_VUR) * LDP + 3 * (TILE_M + 24) * CB_LDB / 2 + 4 * CB_PS + 640 + C2_XR * C2_MBW / 2 + 4 * D * DWK) * sizeof(float);
 }
-template <bool DROP>
+template <bool DROP, bool SAVE = true>
 static void launch_cbf2_t(const CbFwdArgs& a, int grid, hipStream_t s) {
     static size_t ok = 0;
     const size_t lds = cb_fwd2_lds();
-    ensure_dynamic_lds((const void*)k_convblock_fwd2<DROP>, lds, ok, "k_convblock_fwd2");
-    VSL_LAUNCH((k_convblock_fwd2<DROP>), dim3(grid), dim3(CB_T), lds, s, a);
+    ensure_dynamic_lds((const void*)k_convblock_fwd2<DROP, SAVE>, lds, ok, "k_convblock_fwd2");
+    VSL_LAUNCH((k_convblock_fwd2<DROP, SAVE>), dim3(grid), dim3(CB_T), lds, s, a);
 }
 static void launch_cbf2(const CbFwdArgs& a, int grid, hipStream_t s) {
-    if (a.dp[0].thresh) launch_cbf2_t<true>(a, grid, s); else launch_cbf2_t<false>(a, grid, s);
+    if (a.nosave) launch_cbf2_t<false, false>(a, grid, s);
+    else if (a.dp[0].thresh) launch_cbf2_t<true>(a, grid, s); else launch_cbf2_t<false>(a, grid, s);
+}
+template <int SH, bool SAVE = true>
+static void launch_cbf_t(const CbFwdArgs& a, int grid, hipStream_t s) {
+    static size_t ok = 0;
+    const size_t lds = cb_fwd_lds_split(SH);
+    ensure_dynamic_lds((const void*)k_convblock_fwd<SH, SAVE>, lds, ok, "k_convblock_fwd");
+    VSL_LAUNCH((k_convblock_fwd<SH, SAVE>), dim3(grid), dim3(CB_T), lds, s, a);
 }
 template <int SH>
 static void launch_cbf(const CbFwdArgs& a, int grid, hipStream_t s) {
-    static size_t ok = 0;
-    const size_t lds = cb_fwd_lds_split(SH);
-    ensure_dynamic_lds((const void*)k_convblock_fwd<SH>, lds, ok, "k_convblock_fwd");
-    VSL_LAUNCH((k_convblock_fwd<SH>), dim3(grid), dim3(CB_T), lds, s, a);
+    if (a.nosave) launch_cbf_t<SH, false>(a, grid, s); else launch_cbf_t<SH>(a, grid, s);
 }
 void launch_convblock_fwd(const CbFwdArgs& a, hipStream_t s) {
     if (a.L <= TILE_M) {                    // sample tiles: one workgroup per sample
@@ -1501,7 +1510,8 @@ int convblock_slabs(int R, int L) { return L <= TILE_M ? R / L : (R + TILE_M - 1
 // =========================================================================================================
 // HT (QB = 1 only): the workgroup goes on with both span heads on its tile (AttnBlockArgs::head_tail): threads 0-255 the start head, 256-511 the end
 // head, whose features are the y tile this kernel has just produced; the other waves only join the barriers.
-template <int QB, bool HT = false>     // 16-query blocks per wave: 2 = 8 waves (wave = head), 1 = 16 waves (wave = head x query block): twice the waves per SIMD
+// SAVE = false (inference): att, LSE, r, h2 and the hosted heads' hidden / LayerNorm tensors stay in the workgroup; only y (and the logits) leave
+template <int QB, bool HT = false, bool SAVE = true>     // 16-query blocks per wave: 2 = 8 waves (wave = head), 1 = 16 waves (wave = head x query block): twice the waves per SIMD
 __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs a) {
     constexpr int NT = 1024 / QB, NQ = 1024 / NT;      // threads ; float4 items per thread of a 32 x 128 tile
     __shared__ __attribute__((aligned(16))) float Rs[TILE_M * LDP];          // att, then r = drop(att) + x
@@ -1614,7 +1624,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
         const float inv = 1.0f / lt;
         const float4 ov = make_float4(o[qb][0] * inv, o[qb][1] * inv, o[qb][2] * inv, o[qb][3] * inv);   // lane (qi, g): O[q][4g + reg]
         *reinterpret_cast<float4*>(&Rs[(qoff + 16 * qb + qi) * LDP + h * HD + 4 * g]) = ov;
-        if (q < L) {
+        if (SAVE && q < L) {
             *reinterpret_cast<float4*>(a.att + (rowbase + q) * D + h * HD + 4 * g) = ov;
             if (g == 0) a.lse[((size_t)b * H + h) * L + q] = m[qb] + __logf(lt);
         }
@@ -1631,7 +1641,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
             const uint32_t base = (uint32_t)(r * D + c);
             v.x = v.x * drop_mul(a.d3, base) + xv[q].x; v.y = v.y * drop_mul(a.d3, base + 1) + xv[q].y;
             v.z = v.z * drop_mul(a.d3, base + 2) + xv[q].z; v.w = v.w * drop_mul(a.d3, base + 3) + xv[q].w;
-            *reinterpret_cast<float4*>(a.r_out + (size_t)r * D + c) = v;
+            if constexpr (SAVE) *reinterpret_cast<float4*>(a.r_out + (size_t)r * D + c) = v;
         } else v = make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<float4*>(&Rs[rr * LDP + c]) = v;
     }
@@ -1640,7 +1650,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
     ln_rows512(Rs, Hs, TILE_M, Pn, Pn + 128, a.d4, (int)rowbase + q0);
     __syncthreads();
     ESTAMP(5);
-    if (a.h2_out) {
+    if (SAVE && a.h2_out) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int e = tid + q * NT, rr = e >> 5, c = (e & 31) * 4;
@@ -1675,7 +1685,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
         __syncthreads();
         const int grp = tid >> 8;
         float* tl = Mb + Lp + (grp & 1) * (TILE_M * HEAD_LD + TILE_M * LDP);
-        head_fwd_tile<8>(grp == 0 ? a.hs : a.he, a.head_x, a.head_vmask, tl, tl + TILE_M * HEAD_LD, grp == 1 ? Hs : nullptr,
+        head_fwd_tile<8, SAVE>(grp == 0 ? a.hs : a.he, a.head_x, a.head_vmask, tl, tl + TILE_M * HEAD_LD, grp == 1 ? Hs : nullptr,
                       rowbase + q0, min(TILE_M, L - q0), tid & 255, grp < 2);
     }
 }
@@ -1687,9 +1697,16 @@ void launch_attn_block_fwd(const AttnBlockArgs& a, int B, hipStream_t s) {
     if (a.head_tail) {
         const size_t shm_t = shm + (size_t)2 * (TILE_M * HEAD_LD + TILE_M * LDP) * sizeof(float);
         static size_t ok = 0;
-        ensure_dynamic_lds((const void*)k_attn_block_fwd<1, true>, shm_t, ok, "k_attn_block_fwd");
-        VSL_LAUNCH((k_attn_block_fwd<1, true>), grid, dim3(1024), shm_t, s, a);
-    } else VSL_LAUNCH(k_attn_block_fwd<1>, grid, dim3(1024), shm, s, a);
+        if (a.nosave) {
+            static size_t okn = 0;
+            ensure_dynamic_lds((const void*)k_attn_block_fwd<1, true, false>, shm_t, okn, "k_attn_block_fwd");
+            VSL_LAUNCH((k_attn_block_fwd<1, true, false>), grid, dim3(1024), shm_t, s, a);
+        } else {
+            ensure_dynamic_lds((const void*)k_attn_block_fwd<1, true>, shm_t, ok, "k_attn_block_fwd");
+            VSL_LAUNCH((k_attn_block_fwd<1, true>), grid, dim3(1024), shm_t, s, a);
+        }
+    } else if (a.nosave) VSL_LAUNCH((k_attn_block_fwd<1, false, false>), grid, dim3(1024), shm, s, a);
+    else VSL_LAUNCH(k_attn_block_fwd<1>, grid, dim3(1024), shm, s, a);
     static int left = 3;
     if (edbg_on() && B > 16) edbg_report("attn_block_fwd", 7, s, left);
 }

@@ -370,7 +370,7 @@ __global__ __launch_bounds__(512) void k_embed_fwd(const int64_t* __restrict__ w
                 const int oc = 16 * nt + jl;
                 if (g4 == 0 && oc < 100) {
                     E[(size_t)r * EW + word_dim + oc] = bv;
-                    argpos[(size_t)r * 100 + oc] = (int8_t)bp;
+                    if (argpos) argpos[(size_t)r * 100 + oc] = (int8_t)bp;      // (null in inference mode)
                 }
             }
         }
@@ -611,7 +611,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const float* __restrict__ Q, c
         // lane (qi, g) holds O[q][dd = 4g + reg]
         *reinterpret_cast<float4*>(att + (rowbase + q) * D + h * HD + 4 * g) =
             make_float4((o0[0] + o1[0]) * inv, (o0[1] + o1[1]) * inv, (o0[2] + o1[2]) * inv, (o0[3] + o1[3]) * inv);
-        if (g == 0) lse[((size_t)b * H + h) * L + q] = m * AF_LN2 + __logf(l);
+        if (g == 0 && lse) lse[((size_t)b * H + h) * L + q] = m * AF_LN2 + __logf(l);      // (null in inference mode)
     }
 }
 void launch_attn_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
@@ -668,7 +668,7 @@ __global__ __launch_bounds__(256) void k_attn_out_fwd(const float* __restrict__ 
                 v.y = av[q].y * drop_mul(d3, base + 1) + xv[q].y;
                 v.z = av[q].z * drop_mul(d3, base + 2) + xv[q].z;
                 v.w = av[q].w * drop_mul(d3, base + 3) + xv[q].w;
-                *reinterpret_cast<float4*>(r_out + (size_t)r * D + c) = v;
+                if (r_out) *reinterpret_cast<float4*>(r_out + (size_t)r * D + c) = v;      // (r, h2: null in inference mode)
             }
             *reinterpret_cast<float4*>(&Rs[rr * LDP + c]) = v;
             *reinterpret_cast<float4*>(&Hs[rr * LDP + c]) = v;
@@ -734,8 +734,9 @@ __device__ __forceinline__ void cq_pool_body(const float* __restrict__ Qf, const
         const float mx = wave_max(fmaxf(v0, v1));
         const float e0 = lane < Lq ? __expf(v0 - mx) : 0.f, e1 = lane + 64 < Lq ? __expf(v1 - mx) : 0.f;
         const float inv = 1.0f / wave_sum(e0 + e1);
-        if (lane < Lq) { al[lane] = e0 * inv; alpha[qrow + lane] = e0 * inv; }
-        if (lane + 64 < Lq) { al[lane + 64] = e1 * inv; alpha[qrow + lane + 64] = e1 * inv; }
+        // (alpha, pooled: read by the backward alone -- null in inference mode)
+        if (lane < Lq) { al[lane] = e0 * inv; if (alpha) alpha[qrow + lane] = e0 * inv; }
+        if (lane + 64 < Lq) { al[lane + 64] = e1 * inv; if (alpha) alpha[qrow + lane + 64] = e1 * inv; }
     }
     __syncthreads();
     if (tid < D) {
@@ -748,7 +749,7 @@ __device__ __forceinline__ void cq_pool_body(const float* __restrict__ Qf, const
             for (int u = 0; u < 8; ++u) if (j0 + u < Lq) acc += al[j0 + u] * qv[u];
         }
         pl[tid] = acc;
-        pooled[(size_t)b * D + tid] = acc;
+        if (pooled) pooled[(size_t)b * D + tid] = acc;
     }
     __syncthreads();
     // ---- pb[o] = sum_c Wcat[o][128 + c] * pooled[c] + bcat[o]     (second half of the 2d -> d Conv1D); 8 lanes per row
@@ -1030,7 +1031,7 @@ __global__ __launch_bounds__(256) void k_cq_col(const float* __restrict__ C, con
         if (jj < Lq && t0 + i < T) {
             const size_t o = (crow + t0 + i) * Lq + jj;
             v = __expf(S[o] + (1.f - cmask[crow + t0 + i]) * MASK_VALUE - cmax[jj]) * cinv[jj];
-            Scol[o] = v;
+            if (Scol) Scol[o] = v;         // (null in inference mode)
         }
         Ss[e] = v;
     }
@@ -1151,7 +1152,7 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
                 if (jj < Lq && tt0 + i < T) {
                     const size_t o = (crow + tt0 + i) * Lq + jj;
                     v = __expf(S[o] + (1.f - cmask[crow + tt0 + i]) * MASK_VALUE - cmax[jj]) * cinv[jj];
-                    if (tl == (int)blockIdx.x) cf.Scol[o] = v;       // this workgroup's own tile (saved for the backward)
+                    if (cf.Scol && tl == (int)blockIdx.x) cf.Scol[o] = v;       // this workgroup's own tile (saved for the backward; null in inference mode)
                 }
                 Sc[e] = v;
             }
@@ -1165,7 +1166,7 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
                 const int jj = acc_row(r, lane);
                 if (jj < Lq) {
                     Ms[jj * LDP + colm] = macc[0][r];
-                    if (blockIdx.x == 0) M[(qrow + jj) * D + colm] = macc[0][r];     // saved for the backward
+                    if (M && blockIdx.x == 0) M[(qrow + jj) * D + colm] = macc[0][r];     // saved for the backward (null in inference mode)
                 }
             }
         }
@@ -1179,7 +1180,7 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
             sm.x += v.x; sm.y += v.y; sm.z += v.z; sm.w += v.w;
         }
         *reinterpret_cast<float4*>(Ms + j * LDP + c4) = sm;
-        if (blockIdx.x == 0) *reinterpret_cast<float4*>(M + (qrow + j) * D + c4) = sm;     // saved for the backward
+        if (M && blockIdx.x == 0) *reinterpret_cast<float4*>(M + (qrow + j) * D + c4) = sm;     // saved for the backward
     }
     for (int e = tid; e < TILE_M * LQ1; e += 256) {
         const int rr = e / LQ1, j = e - rr * LQ1;
@@ -1242,7 +1243,7 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
         const int row = acc_row(r, lane);
         const int t = t0 + row;
         const float v = acc[0][r] + bv;
-        if (t < T) out[(crow + t) * D + col] = v;
+        if (out && t < T) out[(crow + t) * D + col] = v;      // (f1: null in inference mode, like f2 below)
         Cs[row * LDP + col] = t < T ? v : 0.f;     // the C tile is dead: A operand of the next GEMM
     }
     __syncthreads();
@@ -1287,7 +1288,7 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
         if (t < T) {
             const float4 v = *reinterpret_cast<const float4*>(&Fs[rr * LDP + c]);
             const float hv = hs[rr];
-            *reinterpret_cast<float4*>(cf.f2 + (crow + t) * D + c) = v;
+            if (cf.f2) *reinterpret_cast<float4*>(cf.f2 + (crow + t) * D + c) = v;
             *reinterpret_cast<float4*>(cf.gated + (crow + t) * D + c) = make_float4(v.x * hv, v.y * hv, v.z * hv, v.w * hv);
         }
     }
@@ -1362,7 +1363,7 @@ __global__ __launch_bounds__(256) void k_head_fwd(HeadArgs a0, HeadArgs a1, cons
         const int gr = r0 + row;
         const float hv = fmaxf(acc[0][r] + bv, 0.f);
         Hd[row * LDP + col] = hv;
-        if (gr < R) a.hid[(size_t)gr * D + col] = hv;
+        if (a.hid && gr < R) a.hid[(size_t)gr * D + col] = hv;      // (null in inference mode: the backward alone reads it)
     }
     __syncthreads();
     {

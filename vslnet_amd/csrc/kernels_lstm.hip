@@ -100,8 +100,10 @@ __global__ __launch_bounds__(512, 2) void k_lstm4_fwd(const float* __restrict__ 
         hs[cur ^ 1][j * L4_HP + u] = hn;
         if (ok) {
             const unsigned base = (unsigned)(row + t);
-            float* gp = gates + base * (4 * D) + u;
-            gp[0] = ig; gp[D] = fg; gp[2 * D] = gg; gp[3 * D] = og;
+            if (gates) {                                  // (null in inference mode: c_t and h_t stay, a later time chunk resumes from them)
+                float* gp = gates + base * (4 * D) + u;
+                gp[0] = ig; gp[D] = fg; gp[2 * D] = gg; gp[3 * D] = og;
+            }
             cseq[base * D + u] = cn;
             out[base * D + u] = hn * Mk;
             if (t == 0) hprev[base * D + u] = 0.f;
@@ -318,7 +320,9 @@ enum { L1_PLAIN = 0, L1_PUBLISH = 1, L1_GRANULES = 2 };    // inputs from memory
 // W_hh[(j ^ (q >> 3)) * 128 + u][32 j + 4 (q & 7) + x] for x = 0 .. 3.
 //   L1_PUBLISH : h_t * mask is also published to gout[(b T + t) 128 + u]
 //   L1_GRANULES: the input projection comes from gin[(b T + t) 512 + granule_gate_index(gate, u)] instead of gi
-template <int MODE>
+// SAVE = false (inference): the masked h_t (`out`) is the only sequence stored; of c_t and h_t only the rows a later time chunk resumes from
+// (t1 < T: cseq[t1 - 1], hprev[t1]).  gates and tseq may be null, and so may cseq and hprev when the launch covers every step.
+template <int MODE, bool SAVE = true>
 __device__ __forceinline__ void lstm1_fwd_body(float (&hs)[2][4 * L1_SEG], int bidx, const float* __restrict__ gi, const u64* gin,
                                                const float* __restrict__ Wimg, const float* __restrict__ bih,
                                                const float* __restrict__ bhh, const float* __restrict__ mask,
@@ -337,7 +341,7 @@ __device__ __forceinline__ void lstm1_fwd_body(float (&hs)[2][4 * L1_SEG], int b
     const float ma = j == 2 ? 2.0f : 1.0f, mb = j == 2 ? -1.0f : 0.0f;
     float cst = t0 > 0 ? cseq[(unsigned)((row + t0 - 1) * D + u)] : 0.f;
     if (j == 0) hs[t0 & 1][hoff] = t0 > 0 ? hprev[(unsigned)((row + t0) * D + u)] : 0.f;     // (h_{-1} = 0: step 0's product is 0)
-    if (j == 3 && t0 == 0) hprev[(unsigned)(row * D + u)] = 0.f;
+    if (SAVE && j == 3 && t0 == 0) hprev[(unsigned)(row * D + u)] = 0.f;
     // per-lane cursors.  One store per step carries the lane's activated gate; a second one the quad's cell results (lane j = 0: c_t,
     // 1: masked h_t, 2: h_t as next step's hprev row, 3: tanh(c_t)).  Step t's stores are issued during step t + 1's LDS reads; the last
     // step's after the loop -- the only place where h_t of t = T - 1 (no hprev row) has to be held back.
@@ -400,12 +404,17 @@ __device__ __forceinline__ void lstm1_fwd_body(float (&hs)[2][4 * L1_SEG], int b
             // the previous step's stores.  The launch's first step has none: it writes placeholders into its own rows, which the next
             // step overwrites (same lanes, same addresses, in order) -- so that BOTH sides of the branch issue two stores: a memory
             // instruction on one side only leaves the compiler's wait counts behind the join at their worst case, vmcnt(0)
-            if (s == 0 && tb == t0) {                     // (uniform)
-                *gtp = st_act;
-                *qfirst = st_q;
-            } else {
-                *gtp = st_act; gtp += 4 * D;
-                *qp = st_q; qp += D;
+            if constexpr (SAVE) {
+                if (s == 0 && tb == t0) {                 // (uniform)
+                    *gtp = st_act;
+                    *qfirst = st_q;
+                } else {
+                    *gtp = st_act; gtp += 4 * D;
+                    *qp = st_q; qp += D;
+                }
+            } else {                                      // lane 1's masked h_t alone (its placeholder target is its own row)
+                if (j == 1) *qp = st_q;
+                if (!(s == 0 && tb == t0)) qp += D;
             }
             if (s == 0) load_blk(tb + L1_NB);             // the next block's inputs
             float o[4];
@@ -430,18 +439,21 @@ __device__ __forceinline__ void lstm1_fwd_body(float (&hs)[2][4 * L1_SEG], int b
         rotate();
     }
     if (t1 > t0) {
-        *gtp = st_act;
-        if (j != 2 || t1 < T) *qp = st_q;
+        if constexpr (SAVE) {
+            *gtp = st_act;
+            if (j != 2 || t1 < T) *qp = st_q;
+        } else if (j == 1 || (t1 < T && (j == 0 || j == 2))) *qp = st_q;      // h_t * mask ; c_t and h_t of the chunk's last step for the next chunk
     }
 }
 
+template <bool SAVE = true>
 __global__ __launch_bounds__(512, 2) void k_lstm1_fwd(const float* __restrict__ gi, const float* __restrict__ Wimg,
                                                       const float* __restrict__ bih, const float* __restrict__ bhh,
                                                       const float* __restrict__ mask, float* __restrict__ gates,
                                                       float* __restrict__ cseq, float* __restrict__ tseq, float* __restrict__ hprev,
                                                       float* __restrict__ out, int T, int t0, int t1) {
     __shared__ __attribute__((aligned(16))) float hs[2][4 * L1_SEG];
-    lstm1_fwd_body<L1_PLAIN>(hs, blockIdx.x, gi, nullptr, Wimg, bih, bhh, mask, gates, cseq, tseq, hprev, out, nullptr, 0u, T, t0, t1);
+    lstm1_fwd_body<L1_PLAIN, SAVE>(hs, blockIdx.x, gi, nullptr, Wimg, bih, bhh, mask, gates, cseq, tseq, hprev, out, nullptr, 0u, T, t0, t1);
 }
 
 // One sample's backward recurrence over the steps [t0, t1) in reverse.  Wimg: PackJob type 10 image of W_hh -- lane m = lane & 15 of row
@@ -709,16 +721,17 @@ __device__ __forceinline__ void lstm1_proj_bwd(float (&dGs)[2][16 * L1_SEG], int
     }
 }
 
+template <bool SAVE = true>
 __global__ __launch_bounds__(512, 2) void k_rnn_fwd(RnnFwdArgs a) {
     __shared__ __attribute__((aligned(16))) float hs[2][4 * L1_SEG];
     const int B = a.B;
     if ((int)blockIdx.x < B)
-        lstm1_fwd_body<L1_PUBLISH>(hs, blockIdx.x, a.gi0, nullptr, a.Whh[0], a.bih[0], a.bhh[0], a.mask, a.gates[0], a.cseq[0], a.tseq[0], a.hprev[0],
+        lstm1_fwd_body<L1_PUBLISH, SAVE>(hs, blockIdx.x, a.gi0, nullptr, a.Whh[0], a.bih[0], a.bhh[0], a.mask, a.gates[0], a.cseq[0], a.tseq[0], a.hprev[0],
                                    a.out[0], a.h_gran, a.epoch, a.T, 0, a.T);
     else if ((int)blockIdx.x < 2 * B)
         lstm1_proj_fwd(hs, blockIdx.x - B, a.h_gran, a.Wih1, a.gi_gran, a.epoch, a.T);
     else
-        lstm1_fwd_body<L1_GRANULES>(hs, blockIdx.x - 2 * B, nullptr, a.gi_gran, a.Whh[1], a.bih[1], a.bhh[1], a.mask, a.gates[1], a.cseq[1], a.tseq[1],
+        lstm1_fwd_body<L1_GRANULES, SAVE>(hs, blockIdx.x - 2 * B, nullptr, a.gi_gran, a.Whh[1], a.bih[1], a.bhh[1], a.mask, a.gates[1], a.cseq[1], a.tseq[1],
                                     a.hprev[1], a.out[1], nullptr, a.epoch, a.T, 0, a.T);
 }
 
@@ -744,13 +757,18 @@ bool rnn_fused_ok(int B) {            // VSL_RNN_FUSED=0 keeps the chunked launc
     static const bool on = !(getenv("VSL_RNN_FUSED") && getenv("VSL_RNN_FUSED")[0] == '0');
     return on && lstm_one_sample(B) && B <= RNN_FUSED_MAX_B;
 }
-void launch_rnn_fwd(const RnnFwdArgs& a, hipStream_t s) { VSL_LAUNCH(k_rnn_fwd, dim3(3 * a.B), dim3(512), 0, s, a); }
+void launch_rnn_fwd(const RnnFwdArgs& a, hipStream_t s) {
+    if (a.nosave) VSL_LAUNCH(k_rnn_fwd<false>, dim3(3 * a.B), dim3(512), 0, s, a);
+    else VSL_LAUNCH(k_rnn_fwd<true>, dim3(3 * a.B), dim3(512), 0, s, a);
+}
 void launch_rnn_bwd(const RnnBwdArgs& a, hipStream_t s) { VSL_LAUNCH(k_rnn_bwd, dim3(3 * a.B), dim3(512), 0, s, a); }
 void launch_lstm_fwd(const float* gi, const float* Whh, const float* Wimg, const float* bih, const float* bhh, const float* mask, float* gates,
                       float* cseq, float* tseq, float* hprev, float* out, int B, int T, hipStream_t s, int t0, int t1) {
     if (t1 < 0) t1 = T;
     if (lstm_one_sample(B)) {
-        VSL_LAUNCH(k_lstm1_fwd, dim3(B), dim3(512), 0, s, gi, Wimg, bih, bhh, mask, gates, cseq, tseq, hprev, out, T, t0, t1);
+        // gates == nullptr (inference): the instantiation that stores `out` and the rows the next time chunk resumes from
+        if (!gates) VSL_LAUNCH(k_lstm1_fwd<false>, dim3(B), dim3(512), 0, s, gi, Wimg, bih, bhh, mask, gates, cseq, tseq, hprev, out, T, t0, t1);
+        else VSL_LAUNCH(k_lstm1_fwd<true>, dim3(B), dim3(512), 0, s, gi, Wimg, bih, bhh, mask, gates, cseq, tseq, hprev, out, T, t0, t1);
         return;
     }
     VSL_LAUNCH(k_lstm4_fwd, dim3((B + 3) / 4), dim3(512), 0, s, gi, Whh, bih, bhh, mask, gates, cseq, hprev, out, B, T, t0, t1);

@@ -232,6 +232,8 @@ __device__ __forceinline__ void row_ln(Row4& x, const Row4& g, const Row4& b, co
 // Saves exactly what the row-tile kernels save (qf, x0, y0..3, u0..3, ReLU bits, h1, q, k, v, LSE, att, r, h2, out): the backward and the
 // weight-gradient launches do not care which forward produced them.
 // =========================================================================================================
+// SAVE = false (inference, QueryFwdArgs::nosave): the encoder output `out` is the only store; same arithmetic
+template <bool SAVE = true>
 __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* T = smem;                            // [32][LDP] fp32 tile: residual stream by rows / by channel columns, V of the attention
@@ -285,7 +287,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] += bv[r];
-        if (a.qf) d2global(acc, a.qf + g0, w, m, h, L);
+        if (SAVE && a.qf) d2global(acc, a.qf + g0, w, m, h, L);
 #pragma unroll
         for (int r = 0; r < 16; ++r) X[r] = acc[r] + pv[r];
     }
@@ -312,7 +314,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
         {
             Row4 x;
             tile_to_row(x, T, rr, sub);
-            row_store(x, (l == 0 ? a.x0 : a.y[max(l - 1, 0)]) + g0, rr, sub, rok);
+            if constexpr (SAVE) row_store(x, (l == 0 ? a.x0 : a.y[max(l - 1, 0)]) + g0, rr, sub, rok);
             row_ln(x, gl, bl, nodrop, 0, sub, rok);
             row_to_tile(x, T, rr, sub);
         }
@@ -334,12 +336,14 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
                 uo[i] = u;
             }
             if (l == 0) QSTAMP(12);
-            float* ug = a.u[l] + g0 + c;
 #pragma unroll
             for (int i = 0; i < 16; i += 2) pair_split_store(P, os + i, c, uo[i], uo[i + 1]);     // GEMM operand: three bf16 planes
+            if constexpr (SAVE) {
+                float* ug = a.u[l] + g0 + c;
 #pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if (os + i < L) ug[(size_t)(os + i) * D] = uo[i];       // saved: A operand of the weight gradient
+                for (int i = 0; i < 16; ++i)
+                    if (os + i < L) ug[(size_t)(os + i) * D] = uo[i];       // saved: A operand of the weight gradient
+            }
         }
         __syncthreads();
         if (l == 0) QSTAMP(13);
@@ -356,9 +360,9 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
             float av = fmaxf(z, 0.f);
             if (dp.thresh) av *= drop_keep_scale(dp, (uint32_t)((row0 + m) * D + 32 * w + nl(r, h)));
             X[r] += av;
-            if (z > 0.f) bits[r >> 3] |= 1u << (nl(r, h) & 15);
+            if (SAVE && z > 0.f) bits[r >> 3] |= 1u << (nl(r, h) & 15);
         }
-        {   // (R, 4) uint32 words seen as uint16: [row][16-channel group]; the two half-waves hold disjoint bits of both groups
+        if constexpr (SAVE) {   // (R, 4) uint32 words seen as uint16: [row][16-channel group]; the two half-waves hold disjoint bits of both groups
             const unsigned u0 = bits[0], u1 = bits[1];
             auto r0 = __builtin_amdgcn_permlane32_swap(u0, u0, false, false);
             auto r1 = __builtin_amdgcn_permlane32_swap(u1, u1, false, false);
@@ -383,9 +387,9 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
         d2tile(X, T, w, m, h);
         __syncthreads();
         tile_to_row(x, T, rr, sub);
-        row_store(x, a.y[3] + g0, rr, sub, rok);
+        if constexpr (SAVE) row_store(x, a.y[3] + g0, rr, sub, rok);
         row_ln(x, gl, bl, a.d1, row0 + rr, sub, rok);
-        if (a.h1) row_store(x, a.h1 + g0, rr, sub, rok);
+        if (SAVE && a.h1) row_store(x, a.h1 + g0, rr, sub, rok);
         row_to_planes(x, P0, rr, sub);
         __syncthreads();
 #pragma unroll
@@ -395,9 +399,11 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
         tgemm<8>(P0, ring, V, wnext(a.Wo3, plane_pw, D, 32 * w, 0, 8));
 #pragma unroll
         for (int r = 0; r < 16; ++r) { Q[r] += bq[r]; K[r] += bk[r]; V[r] += bvv[r]; }
-        d2global(Q, a.q + g0, w, m, h, L);
-        d2global(K, a.k + g0, w, m, h, L);
-        d2global(V, a.v + g0, w, m, h, L);
+        if constexpr (SAVE) {
+            d2global(Q, a.q + g0, w, m, h, L);
+            d2global(K, a.k + g0, w, m, h, L);
+            d2global(V, a.v + g0, w, m, h, L);
+        }
     }
     QSTAMP(6);
     d2tile(V, T, w, m, h);                      // V[key][channel]: each wave reads back its own 32 columns only (the tile's row-phase readers are behind the barrier above)
@@ -421,7 +427,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
         for (int r = 0; r < 16; ++r) { S[r] = __expf(S[r] - mx); ls += S[r]; }
         ls = lane_pair32(ls, [](float p, float q) { return p + q; });
         const int head = 2 * w + hh;
-        if (h == 0 && m < L) a.lse[((size_t)b * 8 + head) * L + m] = mx + __logf(ls);
+        if (SAVE && h == 0 && m < L) a.lse[((size_t)b * 8 + head) * L + m] = mx + __logf(ls);
         if (a.d2.thresh) {
             const uint32_t pbase = (uint32_t)(((size_t)(b + a.b_off) * 8 + head) * L + m) * (uint32_t)L;
 #pragma unroll
@@ -436,7 +442,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
 #pragma unroll
         for (int r = 8 * hh; r < 8 * hh + 8; ++r) att[r] = O[r] * inv;
     }
-    d2global(att, a.att + g0, w, m, h, L);
+    if constexpr (SAVE) d2global(att, a.att + g0, w, m, h, L);
     QSTAMP(7);
     // ---- output block (:183-190): r = drop(att) + x ; h2 = drop(LN2(r)) ; y = drop(h2 Wo^T + b) + r
     {
@@ -451,9 +457,9 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
         d2tile(X, T, w, m, h);
         __syncthreads();
         tile_to_row(x, T, rr, sub);
-        row_store(x, a.r + g0, rr, sub, rok);
+        if constexpr (SAVE) row_store(x, a.r + g0, rr, sub, rok);
         row_ln(x, gl, bl, a.d4, row0 + rr, sub, rok);
-        if (a.h2) row_store(x, a.h2 + g0, rr, sub, rok);
+        if (SAVE && a.h2) row_store(x, a.h2 + g0, rr, sub, rok);
         row_to_planes(x, P1, rr, sub);
         __syncthreads();
         f32x16 acc;
@@ -869,9 +875,14 @@ void launch_query_bwd(const QueryBwdArgs& a, int B, hipStream_t s) {
     }
 }
 void launch_query_fwd(const QueryFwdArgs& a, int B, hipStream_t s) {
-    static size_t ok = 0;
-    ensure_dynamic_lds((const void*)k_query_fwd, query_fwd_lds(), ok, "k_query_fwd");
-    VSL_LAUNCH(k_query_fwd, dim3(B), dim3(QT), query_fwd_lds(), s, a);
+    static size_t ok = 0, okn = 0;
+    if (a.nosave) {
+        ensure_dynamic_lds((const void*)k_query_fwd<false>, query_fwd_lds(), okn, "k_query_fwd");
+        VSL_LAUNCH(k_query_fwd<false>, dim3(B), dim3(QT), query_fwd_lds(), s, a);
+    } else {
+        ensure_dynamic_lds((const void*)k_query_fwd<true>, query_fwd_lds(), ok, "k_query_fwd");
+        VSL_LAUNCH(k_query_fwd<true>, dim3(B), dim3(QT), query_fwd_lds(), s, a);
+    }
     static int left = 2;
     if (qdbg_on() && B > 16 && left > 0) {
         --left;

@@ -34,8 +34,8 @@ struct HeadArgs {
     const float* b0;
     const float* w1;      // (128)
     const float* b1;      // (1)
-    float* hid;           // (R,128) relu output, saved
-    float* lnfeat;        // (R,128) LN(feat), saved for the weight gradient
+    float* hid;           // (R,128) relu output, saved (nullable: an inference forward does not store it)
+    float* lnfeat;        // (R,128) LN(feat), saved for the weight gradient (nullable)
     float* logits;        // (R)
 };
 
@@ -167,6 +167,7 @@ struct CbFwdArgs {
     Drop dp[4];
     QkvFuse qf;
     int R, L;
+    int nosave;                    // inference: the instantiation that stores y[3], q, k, v only (x0_out, y[0..2], u, relu_mask, qf.h1 may be null; no dropout)
 };
 void launch_convblock_fwd(const CbFwdArgs& a, hipStream_t s);
 // the attention-output backward of one encoder application (a8 :183-190 backward; kernels_bwd.hip attn_out_bwd_tile)
@@ -223,6 +224,7 @@ bool convblock_bwd_hosts_tail(int R, int L);      // does launch_convblock_bwd h
 bool convblock_bwd_hosts_linear(int R, int L);    // ... and tail 3 (the Embedding linear's data gradient)?
 bool convblock_bwd_hosts_qkv(int R, int L);       // ... and CbBwdArgs::qkv?  (its LN1 partial slabs are then convblock_slabs(R, L) many)
 int convblock_slabs(int R, int L);        // partial slabs per parameter of launch_convblock_bwd (= its grid)
+// (lse, and r_out / h2_out below, may be null in all the attention launchers: an inference forward does not store them)
 void launch_attn_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
                      int L, int H, int b_off, Drop d2, hipStream_t s);
 void launch_attn_out_fwd(const float* att, const float* x, const float* ln_g, const float* ln_b, const float* Wpack,
@@ -240,6 +242,7 @@ struct AttnBlockArgs {
     int head_tail;
     HeadArgs hs, he;
     const float *head_x, *head_vmask;
+    int nosave;                    // inference: att, lse, r_out, h2_out and the heads' hid / lnfeat are not written (may be null; no dropout)
 };
 void launch_attn_block_fwd(const AttnBlockArgs& a, int B, hipStream_t s);
 inline bool attn_block_fwd_hosts_heads(int L) { return L <= 128; }
@@ -267,6 +270,7 @@ struct QueryFwdArgs {
     float *att, *lse, *r, *h2, *out;
     Drop d2, d3, d4, d5;
     int EW, L, b_off;
+    int nosave;                    // inference: `out` is the only tensor written (every other output pointer may be null; no dropout)
 };
 bool query_fused_ok(int L, int H, int EW);         // does the sample-local path take this query length / embedding width?
 void launch_query_fwd(const QueryFwdArgs& a, int B, hipStream_t s);
@@ -274,6 +278,7 @@ void launch_query_fwd(const QueryFwdArgs& a, int B, hipStream_t s);
 // k_cq_out computes the sample's column softmax and M itself (S_fold / Scol_fold) and launch_cq_col is not called
 struct CqPoolArgs { const float *pool_w, *Wcat, *bcat; float *alpha, *pooled, *pb; };
 bool cq_col_folds(int T, int Lq);
+// (nullable in the three CQ launchers -- read by the backward alone: alpha, pooled, Scol / Scol_fold, M, cat_out, out, f2)
 void launch_cq_score(const float* C, const float* Qf, const float* qmask, const float* w4C, const float* w4Q,
                      const float* w4mlu, float* S, float* Srow, int B, int T, int Lq, int b_off, Drop dc, Drop dq,
                      hipStream_t s, const CqPoolArgs* pool = nullptr);
@@ -298,7 +303,8 @@ void launch_extract_index(const float* sl, const float* el, int64_t* si, int64_t
 void launch_head_bwd(const HeadBwdArgs& a0, const HeadBwdArgs& a1, int R, hipStream_t s, const AttnOutBwdArgs* fuse = nullptr);
 // a15 DynamicRNN (layers_t7.py:302-313): recurrent part of nn.LSTM(128, 128); the input projection x W_ih^T is a plain GEMM
 // (kernels_lstm.hip: one-sample workgroups for B <= 256, which read k_pack's register-order images of W_hh -- PackJob types 9 / 10 -- and
-// save tanh(c_t) in tseq; 4-sample MFMA groups beyond, which read W_hh itself)
+// save tanh(c_t) in tseq; 4-sample MFMA groups beyond, which read W_hh itself).  gates == nullptr (inference): the gates and tseq are not stored, and of
+// cseq / hprev the one-sample kernel writes only the rows the next time chunk resumes from
 void launch_lstm_fwd(const float* gi, const float* Whh, const float* Wimg, const float* bih, const float* bhh, const float* mask, float* gates,
                      float* cseq, float* tseq, float* hprev, float* out, int B, int T, hipStream_t s, int t0 = 0, int t1 = -1);   // steps [t0, t1)
 void launch_lstm_bwd(const float* dout, const float* dout2, const float* mask, const float* gates, const float* cseq, const float* tseq,
@@ -321,6 +327,7 @@ struct RnnFwdArgs {
     unsigned long long* gi_gran;      // (R, 512) W_ih1 (h * mask)
     unsigned epoch;
     int B, T;
+    int nosave;                       // inference: `out` is the only sequence written (gates, cseq, tseq, hprev may be null)
 };
 struct RnnBwdArgs {
     const float* dout[2];             // (R, 128) gradients wrt the LSTM outputs coming from the span heads

@@ -192,7 +192,7 @@ __device__ __forceinline__ void cqcat_bwd_tile(const CqcatBwdArgs& a, const floa
 // As: [32][HEAD_LD] ; Hd: [32][LDP].
 // KB = weight fragments in flight per wave (k blocks of 8): the 16-wave host has 128 registers per lane.
 constexpr int HEAD_LD = 2 * D + 4;
-template <int KB>
+template <int KB, bool SAVE = true>     // SAVE = false (inference): hid and lnfeat are not stored
 __device__ __forceinline__ void head_fwd_tile(const HeadArgs& a, const float* __restrict__ x, const float* __restrict__ vmask, float* As, float* Hd,
                                               const float* lds_feat, size_t grow0, int nvalid, int lt, bool active) {
     const int lw = lt >> 6, lane = lt & 63;
@@ -240,7 +240,7 @@ __device__ __forceinline__ void head_fwd_tile(const HeadArgs& a, const float* __
             o.x = v[j].x * rstd * gv.x + bv.x; o.y = v[j].y * rstd * gv.y + bv.y;
             o.z = v[j].z * rstd * gv.z + bv.z; o.w = v[j].w * rstd * gv.w + bv.w;
             *reinterpret_cast<float4*>(row + 32 * j) = o;
-            if (a.lnfeat && r < nvalid) *reinterpret_cast<float4*>(a.lnfeat + (grow0 + r) * D + sub * 4 + 32 * j) = o;
+            if (SAVE && a.lnfeat && r < nvalid) *reinterpret_cast<float4*>(a.lnfeat + (grow0 + r) * D + sub * 4 + 32 * j) = o;
         }
     }
     __syncthreads();
@@ -255,7 +255,7 @@ __device__ __forceinline__ void head_fwd_tile(const HeadArgs& a, const float* __
             const int row = acc_row(r, lane);
             const float hv = fmaxf(acc[0][r] + bv, 0.f);
             Hd[row * LDP + col] = hv;
-            if (row < nvalid) a.hid[(grow0 + row) * D + col] = hv;
+            if (SAVE && row < nvalid) a.hid[(grow0 + row) * D + col] = hv;
         }
     }
     __syncthreads();

@@ -33,7 +33,8 @@ class vsl_io(C.Structure):
                 ('grads', C.c_void_p), ('sample_offset', C.c_int32), ('video_features_bf16', C.c_void_p),
                 ('early_grads_event', C.c_void_p),
                 ('fused_step', C.c_void_p),        # (NULL unless Engine.backward(fused_step=...): an older build loaded for an A/B run reads zeros here)
-                ('fused_loss', C.c_void_p)]        # (NULL unless the last loss() was lazy=True)
+                ('fused_loss', C.c_void_p),        # (NULL unless the last loss() was lazy=True)
+                ('inference', C.c_int32)]          # (1: Engine.forward(inference=True); an older build loaded for an A/B run never reads it)
 
 
 class vsl_loss_io(C.Structure):
@@ -59,8 +60,8 @@ class VslError(RuntimeError):
 ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count', 'vsl_param_info', 'vsl_param_floats',
                'vsl_workspace_floats', 'vsl_forward', 'vsl_loss', 'vsl_backward', 'vsl_extract_index',
                'vsl_adamw_step', 'vsl_workspace_offset', 'vsl_profile_select', 'vsl_profile_read', 'vsl_profile_launch', 'vsl_abi_version',
-               'vsl_early_grad_offset', 'vsl_debug_rnn_launches']
-ABI_VERSION = 8                                     # include/vslnet_hip.h: VSL_ABI_VERSION
+               'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats']
+ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
 def load_library():
@@ -102,6 +103,8 @@ def load_library():
     lib.vsl_param_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     lib.vsl_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    if hasattr(lib, 'vsl_inference_workspace_floats'):       # (absent from an older build loaded through VSLNET_HIP_LIB for an A/B run)
+        lib.vsl_inference_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
     lib.vsl_loss.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_loss_io), C.c_void_p]
     lib.vsl_backward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -174,6 +177,11 @@ class Engine:
         self.lib = load_library()
         # vsl_io.fused_loss / fused_step (ABI 8): an older build loaded through VSLNET_HIP_LIB for an A/B run takes the separate calls instead
         self.has_fused_io = hasattr(self.lib, 'vsl_abi_version') and self.lib.vsl_abi_version() >= 8
+        # vsl_io.inference (ABI 9): an older build has no forward-only plan; forward(inference=True) then raises and the module's no_grad path
+        # keeps the saved path.  `use_inference = False` forces that on a current build too (A/B runs, tests)
+        self.has_inference = hasattr(self.lib, 'vsl_inference_workspace_floats')
+        self.use_inference = True
+        self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
             raise ValueError('unknown predictor %r' % (configs.predictor,))
@@ -225,13 +233,31 @@ class Engine:
     def views(self, flat):
         return {n: flat[o:o + k].view(shp) for n, o, k, shp in self.layout}
 
-    def workspace(self, B, T, Lq, Lc):
-        """ONE caller-owned workspace, grown to the largest shape seen: its contents only live from a forward to the
-        backward of the same batch, and the collate narrows every batch to its own max T / Lq / Lc, so real-data training
-        visits hundreds of shapes -- a workspace per shape would grow without bound beside the HBM-resident dataset."""
+    def inference_workspace_floats(self, B, T, Lq, Lc):
+        """Floats an inference forward of this shape needs (the forward-only plan; vslnet_hip.h)."""
+        if not self.has_inference:
+            raise VslError('the loaded library has no inference mode (vsl_inference_workspace_floats is missing)')
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._call(self.lib.vsl_inference_workspace_floats(self.h, B, T, Lq, Lc, C.byref(n)))
+        return int(n.value)
+
+    def workspace_floats(self, B, T, Lq, Lc):
+        """Floats a training (or saved-path evaluation) forward + backward of this shape needs."""
         n = C.c_int64()
         with torch.cuda.device(self.device):
             self._call(self.lib.vsl_workspace_floats(self.h, B, T, Lq, Lc, C.byref(n)))
+        return int(n.value)
+
+    def workspace(self, B, T, Lq, Lc, inference=False):
+        """ONE caller-owned workspace, grown to the largest shape seen: its contents only live from a forward to the
+        backward of the same batch, and the collate narrows every batch to its own max T / Lq / Lc, so real-data training
+        visits hundreds of shapes -- a workspace per shape would grow without bound beside the HBM-resident dataset.
+        Inference forwards share it: their plan is a fraction of the training plan of the same shape, so they only ever grow it for a
+        shape training has not seen."""
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._call((self.lib.vsl_inference_workspace_floats if inference else self.lib.vsl_workspace_floats)(self.h, B, T, Lq, Lc, C.byref(n)))
         if self._ws is None or self._ws.numel() < n.value:
             # drop EVERY reference to the old one first (the last forward's io / keep-alive tuple hold it too): old and new must not
             # coexist at the growth peak beside an HBM-resident dataset (ADVICE r2)
@@ -244,6 +270,8 @@ class Engine:
     def ws_view(self, name, shape):
         """Saved activation `name` of the LAST forward as a tensor view (parity tests)."""
         io = self._last
+        if io is not None and io.inference:
+            raise VslError('ws_view(%r): the last forward was an inference forward, which saves nothing' % (name,))
         off = self.lib.vsl_workspace_offset(self.h, io.B, io.T, io.Lq, io.Lc, name.encode())
         if off < 0:
             raise KeyError(name)
@@ -254,12 +282,19 @@ class Engine:
 
     # ---- the three calls ------------------------------------------------------------------------------------
     def forward(self, flat, pad_vec, glove_vec, word_ids, char_ids, vfeats, v_mask, q_mask, training=False, seed=0,
-                sample_offset=0):
-        """`sample_offset`: index of this shard's first sample in the global batch (data parallel; vslnet_hip.h).
+                sample_offset=0, inference=False):
+        """`inference=True`: a forward that will not be differentiated (vsl_io.inference): kernels that save nothing, the forward-only
+        workspace plan, the same bits as `training=False`.  It overwrites the workspace, so the saves of an earlier training forward are gone:
+        backward() and ws_view() raise until the next saved-path forward.  Excludes `training`.
+        `sample_offset`: index of this shard's first sample in the global batch (data parallel; vslnet_hip.h).
         `vfeats` in torch.bfloat16 selects the bf16 THROUGHPUT mode (vsl_io.video_features_bf16): bf16 features in HBM and a
         bf16-MFMA VisualProjection; everything downstream stays fp32.  Not the parity path.
         (Round 6 removed vsl_io.arithmetic, the one-product mode of VisualProjection and the weight gradients: it measured +0.5 % for a 5e-2
         logit tolerance, and its measured ceiling -- every conv-block GEMM as one product too -- was 1.07 x; profiles/r05_notes.md section 9.)"""
+        if inference and training:
+            raise ValueError('inference=True and training=True exclude each other (the inference kernels have no dropout)')
+        if inference and not self.has_inference:
+            raise VslError('the loaded library has no inference mode (vsl_inference_workspace_floats is missing)')
         B, T, Dv = vfeats.shape
         bf16 = vfeats.dtype == torch.bfloat16
         Lq, Lc = char_ids.shape[1], char_ids.shape[2]
@@ -274,7 +309,8 @@ class Engine:
         else:
             _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
             _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
-        ws = self.workspace(B, T, Lq, Lc)
+        self._flush_loss()                              # before anything touches the workspace: a pending lazy loss points into it (loss_scratch)
+        ws = self.workspace(B, T, Lq, Lc, inference=inference)
         out = torch.empty(3, B, T, dtype=torch.float32, device=self.device)
         io = vsl_io()
         io.B, io.T, io.Lq, io.Lc = B, T, Lq, Lc
@@ -285,10 +321,11 @@ class Engine:
         io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
         io.workspace = _ptr(ws)
         io.training, io.seed, io.sample_offset = int(bool(training)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset)
-        self._flush_loss()
+        io.inference = int(bool(inference))
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._call(self.lib.vsl_forward(self.h, C.byref(io), stream))
-        self._last, self._last_ws = io, ws
+        self._last, self._last_ws = io, ws              # (io.inference marks it: backward() and ws_view() raise on an inference forward)
+        self.inference_forwards += int(bool(inference))
         # keep every tensor the io struct points to alive until the backward
         self._keep = (flat, pad_vec, glove_vec, word_ids, char_ids, vfeats, v_mask, q_mask, out, ws)
         return out[0], out[1], out[2]
@@ -353,6 +390,8 @@ class Engine:
         hf_order[, grad_norm_out]) -- this optimizer step is applied inside the backward's last launch (final reduction + clip + AdamW in one
         kernel); equivalent to backward() followed by adamw_step(..., norm_from_backward=True)."""
         io = self._last
+        if io is not None and io.inference:
+            raise VslError('backward(): the last forward was an inference forward, which saved nothing; run forward(inference=False) on the batch')
         B, T = io.B, io.T
         pend = getattr(self, '_pending_loss', None)
         fused_loss = None

@@ -168,7 +168,16 @@ class VSLNet(nn.Module):
 
     # ---- reference API ---------------------------------------------------------------------------------------------
     def forward(self, word_ids, char_ids, video_features, v_mask, q_mask):
-        self._engine_for(video_features.device)
+        eng = self._engine_for(video_features.device)
+        if not self.training and not torch.is_grad_enabled() and eng.has_inference and eng.use_inference:
+            # evaluation that will never be differentiated (runner.eval_test, main.py --mode test): the inference path -- kernels that save
+            # nothing and the forward-only workspace plan; same bits as the saved path.  eval() WITH grad enabled keeps the saved path (a
+            # backward may follow); a library without the mode (an A/B baseline) falls back to it as well
+            self._step += 1                                 # (a graph built on an earlier forward is stale: its saves are overwritten)
+            we = self.embedding_net.word_emb
+            return eng.forward(self._flat, we.pad_vec.data if we.is_pretrained else None, we.glove_vec.data if we.is_pretrained else None,
+                               word_ids.contiguous(), char_ids.contiguous(), video_features.contiguous().float(), v_mask.contiguous().float(),
+                               q_mask.contiguous().float(), inference=True)
         return _ForwardFn.apply(self, word_ids, char_ids, video_features, v_mask, q_mask, *self._flat_params)
 
     def extract_index(self, start_logits, end_logits):
