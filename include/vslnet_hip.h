@@ -150,6 +150,53 @@ int vsl_inference_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, i
 
 /* VSLNet.forward (VSLNet_t7.py:52-62) */
 int vsl_forward(vsl_handle h, const vsl_io* io, void* hip_stream);
+
+/* ONE ENCODING PER VIDEO, MANY QUERIES AGAINST IT (evaluation only: no dropout, nothing saved, no backward; the reference has no counterpart -- it
+ * encodes the video once per query).  VisualProjection and the video pass of the shared feature encoder do not depend on the query, and nothing
+ * behind them reads the raw features: vsl_encode_video runs that half for N videos, vsl_localize runs everything else for B queries, query b against
+ * video video_index[b] of the encoding.  Together they give what vsl_forward (inference = 1) gives on the replicated batch
+ * video_features[video_index], v_mask[video_index]: bit for bit when T is a multiple of 32 or at most 32; at other T within a few 1e-6, because the conv-block
+ * kernel of such T rounds a row differently depending on where its sample sits in the batch -- two vsl_forward calls that hold the
+ * same video at different batch positions differ in the same way.
+ * AN ENCODING BELONGS TO ITS PADDED T (and to the parameter values it was computed with): the conv block's zero padding at the sequence end turns into
+ * pad-row values when T grows and the attention spreads them to every row, so the same video encoded at another T differs on its valid rows too.  One T
+ * serves the encoding, the mask and the logits; a caller re-encodes after the parameters change.
+ * Both calls mark their workspace like an inference forward: vsl_backward in it, and vsl_workspace_offset, are errors until a training forward has run.
+ * The addressing limits of vsl_forward (2^31 workspace floats, N T 128 resp. B T 128 floats below 2 GiB) apply to N here and to B there.
+ * Detect the feature by the presence of the symbols: VSL_ABI_VERSION does not change for an added entry point. */
+typedef struct {                       /* zero-initialise; new fields are appended */
+    int32_t N, T;                      /* videos (>= 1), padded clips (T <= 4096)                                                          */
+    const float* params;               /* flat parameter bucket                                                                            */
+    const float* video_features;       /* (N, T, video_feature_dim), or NULL with the bf16 copy                                            */
+    const uint16_t* video_features_bf16; /* bf16 throughput mode, as vsl_io.video_features_bf16                                            */
+    const float* v_mask;               /* (N, T)                                                                                           */
+    float* video_encoding;             /* out (N, T, 128): the shared feature encoder's output on the projected features                   */
+    float* workspace;                  /* vsl_encode_workspace_floats() floats: the operand packs and one encoder application's scratch    */
+} vsl_encode_io;
+int vsl_encode_workspace_floats(vsl_handle h, int N, int T, int64_t* out);
+int vsl_encode_video(vsl_handle h, const vsl_encode_io* io, void* hip_stream);
+
+typedef struct {                       /* zero-initialise; new fields are appended */
+    int32_t B, T, Lq, Lc, N;           /* queries; T of the encoding; padded query words / chars per word; videos in the encoding          */
+    const float* params;               /* the SAME parameter values the encoding was computed with                                         */
+    const float* pad_vec;              /* as in vsl_io                                                                                     */
+    const float* glove_vec;
+    const int64_t* word_ids;           /* (B, Lq)                                                                                          */
+    const int64_t* char_ids;           /* (B, Lq, Lc)                                                                                      */
+    const float* q_mask;               /* (B, Lq)                                                                                          */
+    const float* video_encoding;       /* (N, T, 128) from vsl_encode_video with the SAME T                                                */
+    const float* v_mask;               /* (N, T): per VIDEO                                                                                */
+    const int32_t* video_index;        /* (B), device: video of query b.  0 <= value < N is the CALLER'S precondition: the library does not */
+                                       /* read it on the host, and an index outside the range reads outside the encoding                   */
+    float* h_score;                    /* out (B, T), as vsl_forward writes them                                                           */
+    float* start_logits;
+    float* end_logits;
+    float* workspace;                  /* vsl_localize_workspace_floats() floats: the inference plan of (B, T, Lq, Lc) without a video pass  */
+                                       /* plus the (B, T) gathered mask; it never holds a (B, T, 128) copy of the encoding                 */
+} vsl_localize_io;
+int vsl_localize_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, int64_t* out);
+int vsl_localize(vsl_handle h, const vsl_localize_io* io, void* hip_stream);
+
 /* compute_loss + compute_highlight_loss (VSLNet_t7.py:67-72) and their gradient seeds */
 int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_stream);
 /* autograd backward of everything in vsl_forward (main_t7.py:110); needs the same io (workspace, seed) */
@@ -205,7 +252,7 @@ typedef struct vsl_fused_step {
 } vsl_fused_step;
 
 /* workspace introspection for the parity tests: float offset of a named saved activation, -1 if unknown, -2 (and vsl_last_error()) when the
- * handle's last forward was an inference forward, which saves nothing.
+ * handle's last forward was an inference forward (or vsl_encode_video / vsl_localize), which saves nothing.
  * names: "video_affine", "embedding_net", "venc", "qenc", "cq_attention", "cq_concat", "gated", "pred_s", "pred_e" */
 int64_t vsl_workspace_offset(vsl_handle h, int B, int T, int Lq, int Lc, const char* name);
 

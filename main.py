@@ -75,6 +75,8 @@ def build_parser():
     p.add_argument('--optimizer', type=str, default='fused', help='[fused | torch]')
     p.add_argument('--data', type=str, default='resident', help='[resident | loader] resident: the whole split lives in HBM and a '
                    'batch is a device gather; loader: host-side collate + H2D copy per step, like the reference')
+    p.add_argument('--share_videos', action='store_true', help='--mode test with --data resident: encode every video once and localise each '
+                   'query against the resident encoding (runner.eval_test_shared); every batch is then padded to the split\'s longest video')
     p.add_argument('--synthetic_train', type=int, default=512)
     p.add_argument('--synthetic_test', type=int, default=128)
     return p
@@ -278,7 +280,12 @@ def test(configs, parser, argv, dataset, features, device, log=print):
         loader = data.ResidentSplit(dataset['test_set'], features, configs, device, train=False)
     else:
         loader = data.get_test_loader(dataset['test_set'], features, configs, pin=True)
-    r1i3, r1i5, r1i7, mi, _ = runner.eval_test(model, loader, device, mode='test')
+    if getattr(configs, 'share_videos', False):
+        if configs.data != 'resident':
+            raise ValueError('--share_videos needs --data resident (the encoding is computed over the split held in device memory)')
+        r1i3, r1i5, r1i7, mi, _ = runner.eval_test_shared(model, loader, device, mode='test')
+    else:
+        r1i3, r1i5, r1i7, mi, _ = runner.eval_test(model, loader, device, mode='test')
     for name, v in (('Rank@1, IoU=0.3', r1i3), ('Rank@1, IoU=0.5', r1i5), ('Rank@1, IoU=0.7', r1i7), ('mean IoU'.ljust(15), mi)):
         log('\x1b[1;31m{}:\t{:.2f}\x1b[0m'.format(name, v))
     return {'r1i3': r1i3, 'r1i5': r1i5, 'r1i7': r1i7, 'mIoU': mi}

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def ledger(recs, out, ms_per_step=None, title=''):
+def ledger(recs, out, ms_per_step=None, title='', what='one training step', unit='step'):
     n = len(recs)
     t0 = min(r['start_us'] for r in recs)
     for r in recs:
@@ -39,9 +39,9 @@ def ledger(recs, out, ms_per_step=None, title=''):
             r['kind'] = 'host'
     span = max(r['stop_us'] for r in recs)
     out.write('# %s\n' % title)
-    out.write('# one training step, %d launches on %d streams, first start -> last stop %.1f us' % (n, len(set(r['stream'] for r in recs)), span))
+    out.write('# %s, %d launches on %d streams, first start -> last stop %.1f us' % (what, n, len(set(r['stream'] for r in recs)), span))
     if ms_per_step:
-        out.write(' ; the same loop un-instrumented: %.1f us per step' % (1e3 * ms_per_step))
+        out.write(' ; the same loop un-instrumented: %.1f us per %s' % (1e3 * ms_per_step, unit))
     out.write('\n# idx  stream   start    stop     dur   released by (idx: name)            gap  kind   host-enqueue (device clock)\n')
     for i, r in enumerate(recs):
         rel = '%3d: %-18s' % (r['rel'], recs[r['rel']]['name'][:18]) if r['rel'] >= 0 else '  -                    '

@@ -65,6 +65,8 @@ struct SlabRec { int dst, n, nslabs, ss, rl, ds, vn; int64_t src; };
 struct Plan {
     int B, T, Lq, Lc;
     int kind = 0;                       // 0: training plan (every save + the whole backward) ; 1: inference plan (build_infer_plan: what the forward keeps live, reused by liveness)
+                                        // 2: vsl_encode_video (build_encode_plan: B = videos, Lq = Lc = 0) ; 3: vsl_localize (build_infer_plan without the video pass)
+    int64_t vmask = -1;                 // kind 3: the (N, T) clip mask gathered to (B, T)
     int64_t pack, vf, E, argpos, qf;
     EncWs ve, qe, p1, p2;
     LstmWs lstm[2];
@@ -102,6 +104,7 @@ struct vsl_handle_s {
     std::vector<PackJob> jobs;
     PackJob* jobs_dev = nullptr;
     int jobs_char = 0, jobs_first = 0, jobs_query = 0;  // jobs_dev = [char: the char-conv image embed_fwd reads | first: the video branch's opening kernels | query: the Embedding linear | everything else]
+    int jobs_va = 0;                     // `first` = [the shared feature encoder's operands | these: VisualProjection's], so that vsl_localize packs [char | encoder] and vsl_encode_video `first` alone
     unsigned* loss_counter = nullptr;    // arrival counter of k_loss_fused (zero between calls)
     uint8_t* decay_dev = nullptr;        // per-element weight-decay flag of the flat bucket (vsl_adamw_step)
     float* opt_scratch = nullptr;        // OPT_BLOCKS partial sums of grads^2
@@ -446,9 +449,16 @@ struct Ctx {
     const vsl_loss_io* pend_loss = nullptr;   // vsl_io.fused_loss off the dependent chain: launched on the weight-gradient stream behind its first ordering point (loss_on_side)
     int pw_rows = 0;                    // rows per chunk of the NEXT enc_bwd's pointwise weight-gradient jobs (0 = WG_ROWS): the step's last batch, run_backward
     bool defer_w = false;
-    bool inf() const { return p->kind == 1; }
+    // run_forward's part: 0 = the whole forward ; 1 = the video half into `venc_out` (vsl_encode_video) ; 2 = everything else, the context read from the
+    // resident encoding `venc_in` through `vidx`, the clip mask gathered from `vmask_nt` (vsl_localize)
+    int stage = 0;
+    float* venc_out = nullptr;
+    const float* venc_in = nullptr;
+    const int* vidx = nullptr;
+    const float* vmask_nt = nullptr;
+    bool inf() const { return p->kind != 0; }
     // a tensor only the backward reads: its address in a training forward, nullptr in an inference forward (the kernels then do not store it)
-    float* SV(int64_t off) const { return p->kind == 1 ? nullptr : ws + off; }
+    float* SV(int64_t off) const { return p->kind != 0 ? nullptr : ws + off; }
     const float* P(int off) const { return io->params + off; }
     const float* PK(int off) const { return ws + p->pack + off; }
     float* W(int64_t off) const { return ws + off; }
@@ -601,8 +611,10 @@ enum { SITE_VIS = 64, SITE_WORD = 65, SITE_CHAR = 66, SITE_CQ_C = 67, SITE_CQ_Q 
 
 // ------------------------------------------------------------------------------------------------ forward
 struct HeadTail { HeadArgs hs, he; const float *x, *vmask; };     // AttnBlockArgs::head_tail
-void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float* xin, const float* mask, int Bn, int app, const HeadTail* ht = nullptr) {
+// `out`: where the application's output goes when that is not the plan's own buffer (vsl_encode_video: the caller's encoding)
+void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float* xin, const float* mask, int Bn, int app, const HeadTail* ht = nullptr, float* out = nullptr) {
     const int R = w.R, L = w.L, H = c.h->cfg.num_heads;
+    float* const yout = out ? out : c.W(w.out);
     {
         // the whole conv block + LN1 / QKV in ONE launch (kernels_enc.hip: 12-row recomputed halo)
         CbFwdArgs a;
@@ -627,7 +639,7 @@ void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
         memset(&ab, 0, sizeof ab);
         if (!c.dry) {
             ab = AttnBlockArgs{c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob),
-                               c.SV(w.att), c.SV(w.lse), c.SV(w.r), c.SV(w.h2), c.W(w.out), L, 0,
+                               c.SV(w.att), c.SV(w.lse), c.SV(w.r), c.SV(w.h2), yout, L, 0,
                                c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8)};
             ab.nosave = c.inf();
             if (ht) { ab.head_tail = 1; ab.hs = ht->hs; ab.he = ht->he; ab.head_x = ht->x; ab.head_vmask = ht->vmask; }
@@ -642,7 +654,7 @@ void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
     else
         LAUNCH("attn_fwd", launch_attn_fwd(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.SV(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
     LAUNCH("attn_out_fwd", launch_attn_out_fwd(c.W(w.att), c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob), c.SV(w.r), c.SV(w.h2),
-                        c.W(w.out), R, c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8), c.s));
+                        yout, R, c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8), c.s));
 }
 
 CharConvPtrs char_ptrs(const Ctx& c) {
@@ -714,13 +726,31 @@ void run_forward(Ctx& c) {
     const bool split3 = sq != c.main && sp != c.main;
     hipEvent_t pack_first_ev = nullptr, pack_q_ev = nullptr;
     int pack_first_rec = -1, pack_q_rec = -1;
+    const int stage = c.stage;
+    const int nva = c.h->jobs_va;
+    if (stage == 1) {
+        // vsl_encode_video: the video half alone -- the shared encoder's and VisualProjection's operands, the projection, encoder application 0
+        // into the caller's buffer.  One stream: there is no query branch to run beside it.
+        LAUNCH("pack", launch_pack(io.params, c.W(p.pack), c.h->jobs_dev + njc, nj0, c.s));
+        if (io.video_features_bf16)
+            LAUNCH("vproj_fwd", launch_vproj_fwd_bf16(io.video_features_bf16, reinterpret_cast<const uint16_t*>(c.PK(K.va_f16)), c.P(P.va_b), c.W(p.vf), R,
+                                                      cf.video_feature_dim, c.drop(SITE_VIS), c.s));
+        else
+            LAUNCH("vproj_fwd", launch_vproj_fwd3(io.video_features, reinterpret_cast<const uint16_t*>(c.PK(K.va_f3)), c.P(P.va_b), c.W(p.vf), R, cf.video_feature_dim,
+                                                  c.drop(SITE_VIS), c.s));
+        enc_fwd(c, P.fe, K.fe, p.ve, c.W(p.vf), io.v_mask, B, 0, nullptr, c.venc_out);
+        return;
+    }
+    // vsl_localize (stage 2) leaves VisualProjection's operands -- the last `nva` jobs of the first class, the largest pack job -- unpacked
+    const int nfirst = njc + nj0 - (stage == 2 ? nva : 0);
     if (split3) {
         // The main stream's pack carries the char-conv image as well, so the query stream's first kernel -- the word + char embedding, 160
         // workgroups x 125 KB of LDS -- starts right behind it and runs beside the remaining packs and VisualProjection, not beside the video
         // pass' conv block (which it kept off 160 CUs: 49 us in the step against 25 alone, profiles/r05_notes.md section 9); the Embedding
         // linear's operand is packed on the third stream meanwhile.
-        LAUNCH("pack", launch_pack(io.params, c.W(p.pack), c.h->jobs_dev, njc + nj0, c.s));
-        c.order2(c.main, sq, sp);
+        LAUNCH("pack", launch_pack(io.params, c.W(p.pack), c.h->jobs_dev, nfirst, c.s));
+        if (stage == 2) c.order(c.main, sp);        // (no video branch: the query branch keeps the main stream, see below)
+        else c.order2(c.main, sq, sp);
         pack_first_ev = nullptr;           // (the side streams already wait for this launch)
         pack_first_rec = c.h->prof_on ? (int)c.h->prof_recs.size() - 1 : -1;
         c.s = sp;
@@ -728,14 +758,23 @@ void run_forward(Ctx& c) {
         pack_q_ev = c.h->last_event(sp);
         pack_q_rec = c.h->prof_on ? (int)c.h->prof_recs.size() - 1 : -1;
         LAUNCH("pack", launch_pack(io.params, c.W(p.pack), c.h->jobs_dev + njc + nj0 + nj1, nj - njc - nj0 - nj1, c.s));
+        // the per-query clip mask, on the side stream beside the query branch; first read by the CQ kernels, behind the join with this stream
+        if (stage == 2) LAUNCH("vmask_gather", launch_vmask_gather(c.vmask_nt, c.vidx, c.W(p.vmask), B, T, c.s));
         c.s = c.main;
+    } else if (stage == 2) {
+        LAUNCH("pack", launch_pack(io.params, c.W(p.pack), c.h->jobs_dev, nfirst, c.s));
+        LAUNCH("pack", launch_pack(io.params, c.W(p.pack), c.h->jobs_dev + njc + nj0, nj - njc - nj0, c.s));
+        LAUNCH("vmask_gather", launch_vmask_gather(c.vmask_nt, c.vidx, c.W(p.vmask), B, T, c.s));
     } else {
         LAUNCH("pack", launch_pack(io.params, c.W(p.pack), c.h->jobs_dev, nj, c.s));
     }
     // fork: the query branch (embedding + query encoder pass) runs beside the video branch
-    if (!split3) c.order(c.main, sq);
+    if (!split3 && stage != 2) c.order(c.main, sq);
     const bool qlong = query_chain_is_longer(p, true);  // the longer branch keeps the main stream (join wait already satisfied)
     c.s = qlong ? sq : c.main;
+    // vsl_localize: the query branch is the ONLY chain in front of the CQ kernels, so it owns the main stream and there is no fork and no join on the
+    // dependent chain (each costs a ~6 - 20 us bubble, see order()); the packs it does not read and the mask gather run beside it on the third stream
+    if (stage != 2) {
     if (io.video_features_bf16)      // bf16 throughput mode
         LAUNCH("vproj_fwd", launch_vproj_fwd_bf16(io.video_features_bf16, reinterpret_cast<const uint16_t*>(c.PK(K.va_f16)), c.P(P.va_b), c.W(p.vf), R,
                                                   cf.video_feature_dim, c.drop(SITE_VIS), c.s));
@@ -743,7 +782,8 @@ void run_forward(Ctx& c) {
         LAUNCH("vproj_fwd", launch_vproj_fwd3(io.video_features, reinterpret_cast<const uint16_t*>(c.PK(K.va_f3)), c.P(P.va_b), c.W(p.vf), R, cf.video_feature_dim,
                                               c.drop(SITE_VIS), c.s));
     enc_fwd(c, P.fe, K.fe, p.ve, c.W(p.vf), io.v_mask, B, 0);
-    c.s = qlong ? c.main : sq;
+    }
+    c.s = stage == 2 ? c.main : qlong ? c.main : sq;
     const bool wt = cf.word_table != 0;       // trainable word table: its rows 0, 1, 2.. are pad, unk, the vocabulary
     LAUNCH("embed_fwd", launch_embed_fwd(io.word_ids, io.char_ids, wt ? c.P(P.unk) : io.pad_vec, c.P(P.unk) + (wt ? cf.word_dim : 0), wt ? c.P(P.unk) + 2 * cf.word_dim : io.glove_vec, c.P(P.char_tab), char_ptrs(c), c.PK(K.ccw_img), c.W(p.E),
                      reinterpret_cast<int8_t*>(c.SV(p.argpos)), Rq, p.Lc, cf.word_dim, cf.char_dim, c.drop(SITE_WORD),
@@ -787,23 +827,26 @@ void run_forward(Ctx& c) {
     enc_fwd(c, P.fe, K.fe, p.qe, c.W(p.qf), io.q_mask, B, 1);
     }
     c.s = c.main;
-    c.order(sq, c.main);                   // join
-    if (split3) c.order(sp, c.main);       // the remaining packs (long done)
+    if (stage != 2) c.order(sq, c.main);   // join
+    if (split3) c.order(sp, c.main);       // the remaining packs (long done) ; vsl_localize: the gathered mask too
     // short videos, short queries: the column kernel (column softmax over the clips, M = S_col^T C, WeightedPool) is folded into its neighbours --
     // one launch and one boundary less on the dependent chain (VSL_CQ_FOLD=0: three launches)
     static const bool fold_on = !(getenv("VSL_CQ_FOLD") && getenv("VSL_CQ_FOLD")[0] == '0');
     const bool cq_fold = fold_on && cq_col_folds(T, Lq);
     const CqPoolArgs pool{c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb)};
-    LAUNCH("cq_score", launch_cq_score(c.W(p.ve.out), c.W(p.qe.out), io.q_mask, c.P(P.w4C), c.P(P.w4Q), c.P(P.w4mlu), c.W(p.S), c.W(p.Srow), B, T,
-                    Lq, 0, c.drop(SITE_CQ_C), c.drop(SITE_CQ_Q), c.s, cq_fold ? &pool : nullptr));
+    // the context: this forward's video pass, or (vsl_localize) the resident encoding read through the per-query video index
+    const float* const Cv = stage == 2 ? c.venc_in : c.W(p.ve.out);
+    const int* const vidx = stage == 2 ? c.vidx : nullptr;
+    LAUNCH("cq_score", launch_cq_score(Cv, c.W(p.qe.out), io.q_mask, c.P(P.w4C), c.P(P.w4Q), c.P(P.w4mlu), c.W(p.S), c.W(p.Srow), B, T,
+                    Lq, 0, c.drop(SITE_CQ_C), c.drop(SITE_CQ_Q), c.s, cq_fold ? &pool : nullptr, vidx));
     // M = S_col^T C is produced as per-tile partials (the backward's cqP1 arena is free until then) and summed by cq_out
     if (!cq_fold)
-        LAUNCH("cq_col", launch_cq_col(c.W(p.ve.out), c.W(p.qe.out), c.W(p.S), io.v_mask, io.q_mask, c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b),
-                      c.SV(p.Scol), c.W(p.cqP1), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb), B, T, Lq, c.s));
+        LAUNCH("cq_col", launch_cq_col(Cv, c.W(p.qe.out), c.W(p.S), io.v_mask, io.q_mask, c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b),
+                      c.SV(p.Scol), c.W(p.cqP1), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb), B, T, Lq, c.s, vidx));
     // cq_out also carries CQConcatenate + HighLightLayer + gating (row-local on the tile it produces)
-    LAUNCH("cq_out", launch_cq_out(c.W(p.ve.out), c.W(p.qe.out), c.W(p.Srow), c.W(p.cqP1), c.SV(p.M), c.PK(K.cqa_f), c.P(P.cqa_b), c.SV(p.cat),
+    LAUNCH("cq_out", launch_cq_out(Cv, c.W(p.qe.out), c.W(p.Srow), c.W(p.cqP1), c.SV(p.M), c.PK(K.cqa_f), c.P(P.cqa_b), c.SV(p.cat),
                   c.SV(p.f1), c.PK(K.cat1_f), c.W(p.pb), c.P(P.hl_w), c.P(P.hl_b), io.v_mask, c.SV(p.f2), io.h_score, c.W(p.gated), B, T, Lq,
-                  c.s, cq_fold ? c.W(p.S) : nullptr, cq_fold ? c.SV(p.Scol) : nullptr));
+                  c.s, cq_fold ? c.W(p.S) : nullptr, cq_fold ? c.SV(p.Scol) : nullptr, vidx));
     if (cf.predictor == 0) {
         // rnn head (:341-343): start = LSTM_s(x) * mask ; end = LSTM_e(start) * mask ; no LayerNorm in front of the span blocks
         // The recurrence is latency bound (one sample per CU, 0.6 us per step).  Up to RNN_FUSED_MAX_B samples the whole head is ONE launch: start
@@ -1457,11 +1500,14 @@ int check_shape(vsl_handle_s* h, int B, int T, int Lq, int Lc) {
 // The query branch runs beside the video pass on its own stream and has its own (B Lq)-row scratch.  The rnn head keeps the second gate projection
 // and its hand-off granules (B <= 80) or, for the chunked launches, the c_t / h_t sequences a later time chunk resumes from.
 // Every offset a forward does not use is -1 (Ctx::SV hands the kernels nullptr for those).
-int build_infer_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
+// kind 3 (vsl_localize): the same plan without a video pass -- the context is the caller's resident encoding, so `a` serves the second predictor
+// pass / the end LSTM alone and nothing here ever holds a (B, T, 128) copy of the encoding; the (B, T) gathered clip mask is added and vsl_loss's
+// scratch (there is no vsl_io to call it with) left out, so the plan never exceeds the inference plan of the shape by more than B T floats.
+int build_infer_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, int kind = 1) {
     if (int rc = check_shape(h, B, T, Lq, Lc)) return rc;
     const vsl_config& cf = h->cfg;
     Plan* p = new Plan();
-    p->kind = 1;
+    p->kind = kind;
     p->B = B; p->T = T; p->Lq = Lq; p->Lc = Lc;
     const int64_t R = (int64_t)B * T, Rq = (int64_t)B * Lq, RD = ((R * D) + 3) & ~int64_t(3);
     const int EW = cf.word_dim + 100;
@@ -1478,7 +1524,7 @@ int build_infer_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) 
     for (LstmWs& w : p->lstm) w.gi = w.gates = w.cseq = w.tseq = w.hprev = w.out = w.dG = w.carry = -1;
     Bump al;
     p->pack = al(h->pack_floats);
-    p->loss_scratch = al(5 * (int64_t)B + 8);          // (vsl_loss on the outputs of an inference forward)
+    p->loss_scratch = kind == 3 ? -1 : al(5 * (int64_t)B + 8);          // (vsl_loss on the outputs of an inference forward)
     // the query branch's own scratch (beside the video pass on another stream)
     p->E = al(Rq * EW); p->qf = al(Rq * D);
     p->qe.y[3] = al(Rq * D); p->qe.q = al(Rq * D); p->qe.k = al(Rq * D); p->qe.v = al(Rq * D); p->qe.att = al(Rq * D); p->qe.out = al(Rq * D);
@@ -1489,13 +1535,15 @@ int build_infer_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) 
     const int64_t cq_need = 2 * SL + (((int64_t)B * nt * Lq * D + 3) & ~int64_t(3));
     const int64_t region = al(std::max(5 * RD, cq_need));
     EncWs* seq[3] = {&p->ve, &p->p1, &p->p2};
-    for (EncWs* w : seq) { w->y[3] = region; w->q = region + RD; w->k = region + 2 * RD; w->v = region + 3 * RD; w->att = region + 4 * RD; }
-    p->vf = region + 4 * RD;
+    for (EncWs* w : seq) { if (kind == 3 && w == &p->ve) continue; w->y[3] = region; w->q = region + RD; w->k = region + 2 * RD; w->v = region + 3 * RD; w->att = region + 4 * RD; }
+    p->vf = kind == 3 ? -1 : region + 4 * RD;
     p->S = region; p->Srow = region + SL; p->cqP1 = region + 2 * SL;
-    p->ve.out = al(R * D);
+    const int64_t a = al(R * D);
+    if (kind != 3) p->ve.out = a;
     p->gated = al(R * D);
     p->p1.out = al(R * D);
-    p->p2.out = p->ve.out;
+    p->p2.out = a;
+    if (kind == 3) p->vmask = al(R);
     if (cf.predictor == 0) {
         for (int l = 0; l < 2; ++l) {
             LstmWs& w = p->lstm[l];
@@ -1511,6 +1559,36 @@ int build_infer_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) 
     p->partial = al(0); p->partial_floats = 0;
     p->total = al.cur;
     if (p->total >= (int64_t(1) << 31)) { delete p; return fail("inference workspace of %lld floats exceeds the 2^31 offset range", (long long)p->total); }
+    *out = p;
+    return 0;
+}
+
+// vsl_encode_video: the operand packs and ONE encoder application's scratch (y3, q, k, v, att; VisualProjection's output in the att slot, as in the
+// inference plan).  The output goes to the caller's buffer.  B = videos; the plan has no query side (Lq = Lc = 0 in its key).
+int build_encode_plan(vsl_handle_s* h, int N, int T, Plan** out) {
+    const vsl_config& cf = h->cfg;
+    if (N < 1 || T < 1) return fail("vsl_encode_video: empty call (N=%d videos, T=%d clips)", N, T);
+    if (T > cf.max_pos_len)
+        return fail("sequence length (T=%d) exceeds max_pos_len=%d: the positional table has no such row (layers_t7.py:196 -- IndexError in the reference)", T, cf.max_pos_len);
+    if (T > MAX_L) return fail("T=%d > %d clips not supported by the attention kernels", T, MAX_L);
+    if ((int64_t)N * T * D * 4 >= (int64_t(1) << 31))
+        return fail("N*T = %lld rows: an (R, 128) fp32 activation must stay below 2 GiB for the 32-bit buffer offsets of the conv-block kernels (encode the videos in chunks)", (long long)N * T);
+    Plan* p = new Plan();
+    p->kind = 2;
+    p->B = N; p->T = T; p->Lq = 0; p->Lc = 0;
+    const int64_t R = (int64_t)N * T, RD = ((R * D) + 3) & ~int64_t(3);
+    EncWs& w = p->ve;
+    w.x0 = w.h1 = w.lse = w.r = w.h2 = w.out = -1;
+    for (int i = 0; i < 4; ++i) w.y[i] = w.u[i] = w.mask[i] = -1;
+    w.R = (int)R; w.L = T;
+    Bump al;
+    p->pack = al(h->pack_floats);
+    const int64_t region = al(5 * RD);
+    w.y[3] = region; w.q = region + RD; w.k = region + 2 * RD; w.v = region + 3 * RD; w.att = region + 4 * RD;
+    p->vf = region + 4 * RD;
+    p->partial = al(0); p->partial_floats = 0;
+    p->total = al.cur;
+    if (p->total >= (int64_t(1) << 31)) { delete p; return fail("encode workspace of %lld floats exceeds the 2^31 offset range", (long long)p->total); }
     *out = p;
     return 0;
 }
@@ -1662,7 +1740,7 @@ int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, int kind
     auto it = h->plans.find(key);
     if (it != h->plans.end()) { it->second->last_use = ++h->plan_clock; *out = it->second; return 0; }
     Plan* p = nullptr;
-    if (int rc = kind ? build_infer_plan(h, B, T, Lq, Lc, &p) : build_plan(h, B, T, Lq, Lc, &p)) return rc;
+    if (int rc = kind == 2 ? build_encode_plan(h, B, T, &p) : kind ? build_infer_plan(h, B, T, Lq, Lc, &p, kind) : build_plan(h, B, T, Lq, Lc, &p)) return rc;
     if (h->plans.size() >= MAX_PLANS) {
         auto victim = h->plans.begin();
         for (auto jt = h->plans.begin(); jt != h->plans.end(); ++jt)
@@ -1791,13 +1869,16 @@ int vsl_create(const vsl_config* cfg, vsl_handle* out) {
         auto cls = [&](const PackJob& j) {
             const EncPk& f = K.fe;
             if (j.dst == K.ccw_img) return 0;
-            if (in(j.dst, {K.va_f, K.va_f16, K.va_f3, f.pw_f[0], f.pw_f[1], f.pw_f[2], f.pw_f[3], f.qkv_f, f.o_f, f.pw_f3[0], f.pw_f3[1], f.pw_f3[2], f.pw_f3[3],
-                           f.qkv_f3, f.o_f3})) return 1;
-            if (in(j.dst, {K.emb_f, K.emb_f3})) return 2;
-            return 3;
+            if (in(j.dst, {f.pw_f[0], f.pw_f[1], f.pw_f[2], f.pw_f[3], f.qkv_f, f.o_f, f.pw_f3[0], f.pw_f3[1], f.pw_f3[2], f.pw_f3[3], f.qkv_f3, f.o_f3})) return 1;
+            if (in(j.dst, {K.va_f, K.va_f16, K.va_f3})) return 2;      // (last of the first launch: vsl_localize leaves these out, vsl_encode_video packs 1 and 2)
+            if (in(j.dst, {K.emb_f, K.emb_f3})) return 3;
+            return 4;
         };
         std::stable_sort(h->jobs.begin(), h->jobs.end(), [&](const PackJob& a, const PackJob& b) { return cls(a) < cls(b); });
-        for (const PackJob& j : h->jobs) { h->jobs_char += cls(j) == 0; h->jobs_first += cls(j) == 1; h->jobs_query += cls(j) == 2; }
+        for (const PackJob& j : h->jobs) {
+            const int k = cls(j);
+            h->jobs_char += k == 0; h->jobs_first += k == 1 || k == 2; h->jobs_va += k == 2; h->jobs_query += k == 3;
+        }
     }
     if (hipMalloc(&h->jobs_dev, h->jobs.size() * sizeof(PackJob)) != hipSuccess ||
         hipMemcpy(h->jobs_dev, h->jobs.data(), h->jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice) != hipSuccess) {
@@ -1921,6 +2002,79 @@ int vsl_forward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     h->last_infer = io->inference != 0;
     if (io->inference) h->infer_ws = io->workspace;
     else if (h->infer_ws == io->workspace) h->infer_ws = nullptr;
+    return 0;
+}
+
+// ---- one encoding per video, many queries against it (evaluation only: no dropout, nothing saved, no backward)
+int vsl_encode_workspace_floats(vsl_handle h, int N, int T, int64_t* out) {
+    if (!h || !out) return fail("null argument");
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, N, T, 0, 0, &p, 2)) return rc;
+    *out = p->total;
+    return 0;
+}
+
+int vsl_localize_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, int64_t* out) {
+    if (!h || !out) return fail("null argument");
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, B, T, Lq, Lc, &p, 3)) return rc;
+    *out = p->total;
+    return 0;
+}
+
+int vsl_encode_video(vsl_handle h, const vsl_encode_io* e, void* hip_stream) {
+    if (!h || !e) return fail("null handle / io");
+    if (e->N < 1) return fail("vsl_encode_video: N=%d videos (at least one)", e->N);
+    if (!e->params || (!e->video_features && !e->video_features_bf16) || !e->v_mask || !e->video_encoding || !e->workspace)
+        return fail("vsl_encode_io has a null device pointer");
+    if (e->video_features_bf16 && (h->cfg.video_feature_dim % 8 != 0))
+        return fail("bf16 features need video_feature_dim %% 8 == 0 (got %d)", h->cfg.video_feature_dim);
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, e->N, e->T, 0, 0, &p, 2)) return rc;
+    vsl_io io;
+    memset(&io, 0, sizeof io);
+    io.B = e->N; io.T = e->T;
+    io.params = e->params; io.video_features = e->video_features; io.video_features_bf16 = e->video_features_bf16; io.v_mask = e->v_mask;
+    io.workspace = e->workspace; io.inference = 1;
+    Ctx c{h, p, &io, (hipStream_t)hip_stream, false, io.workspace};
+    c.main = c.s;
+    c.stage = 1; c.venc_out = e->video_encoding;
+    CallScope scope(h);
+    run_forward(c);
+    HIP_OK(hipGetLastError());
+    h->last_infer = true;            // (nothing saved: vsl_backward in this workspace and vsl_workspace_offset are refused as after an inference forward)
+    h->infer_ws = e->workspace;
+    return 0;
+}
+
+int vsl_localize(vsl_handle h, const vsl_localize_io* l, void* hip_stream) {
+    if (!h || !l) return fail("null handle / io");
+    if (l->B < 1) return fail("vsl_localize: B=%d queries (at least one)", l->B);
+    if (l->N < 1) return fail("vsl_localize: N=%d videos in the encoding (at least one)", l->N);
+    if (!l->video_encoding) return fail("vsl_localize: video_encoding is NULL (the output of vsl_encode_video for the same T and params)");
+    if (!l->video_index) return fail("vsl_localize: video_index is NULL (the video of each query)");
+    if (!l->v_mask) return fail("vsl_localize: v_mask is NULL (the (N, T) clip mask of the encoding)");
+    if (!l->params || (!h->cfg.word_table && (!l->pad_vec || !l->glove_vec)) || !l->word_ids || !l->char_ids || !l->q_mask || !l->h_score || !l->start_logits ||
+        !l->end_logits || !l->workspace)
+        return fail("vsl_localize_io has a null device pointer");
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, l->B, l->T, l->Lq, l->Lc, &p, 3)) return rc;
+    vsl_io io;
+    memset(&io, 0, sizeof io);
+    io.B = l->B; io.T = l->T; io.Lq = l->Lq; io.Lc = l->Lc;
+    io.params = l->params; io.pad_vec = l->pad_vec; io.glove_vec = l->glove_vec;
+    io.word_ids = l->word_ids; io.char_ids = l->char_ids; io.q_mask = l->q_mask;
+    io.v_mask = l->workspace + p->vmask;          // every kernel behind the join reads the gathered (B, T) mask
+    io.h_score = l->h_score; io.start_logits = l->start_logits; io.end_logits = l->end_logits;
+    io.workspace = l->workspace; io.inference = 1;
+    Ctx c{h, p, &io, (hipStream_t)hip_stream, false, io.workspace};
+    c.main = c.s;
+    c.stage = 2; c.venc_in = l->video_encoding; c.vidx = l->video_index; c.vmask_nt = l->v_mask;
+    CallScope scope(h);
+    run_forward(c);
+    HIP_OK(hipGetLastError());
+    h->last_infer = true;
+    h->infer_ws = l->workspace;
     return 0;
 }
 

@@ -768,12 +768,14 @@ __device__ __forceinline__ void cq_pool_body(const float* __restrict__ Qf, const
     }
 }
 
-template <int NU>   // words per lane of the row softmax: 8 (Lq <= 64), 12 (<= 96) or 16 (<= MAX_LQ = 128)
+// VIDX (the three CQAttention kernels): the context of sample b is video vidx[b] of a resident (N, T, 128) encoding (vsl_localize) -- the READS of C
+// go through the index, one scalar load per workgroup; everything written stays at sample b.  VIDX = false: C is (B, T, 128), `vidx` is not read.
+template <int NU, bool VIDX>   // NU: words per lane of the row softmax: 8 (Lq <= 64), 12 (<= 96) or 16 (<= MAX_LQ = 128)
 __global__ __launch_bounds__(256) void k_cq_score(const float* __restrict__ C, const float* __restrict__ Qf,
                                                   const float* __restrict__ qmask, const float* __restrict__ w4C,
                                                   const float* __restrict__ w4Q, const float* __restrict__ w4mlu,
                                                   float* __restrict__ S, float* __restrict__ Srow, int T, int Lq, int b_off,
-                                                  Drop dc, Drop dq, CqPool cp) {
+                                                  Drop dc, Drop dq, CqPool cp, const int* __restrict__ vidx) {
     // cp.pool_w != nullptr: ONE extra workgroup per sample (blockIdx.x = number of tiles) runs the WeightedPool / pooled-bias path (the column kernel
     // is folded into k_cq_out then: launch_cq_out)
     if (cp.pool_w && blockIdx.x == gridDim.x - 1) {          // (block-uniform)
@@ -794,13 +796,14 @@ __global__ __launch_bounds__(256) void k_cq_score(const float* __restrict__ C, c
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, hh = lane >> 5;
     const int b = blockIdx.y, t0 = blockIdx.x * TILE_M;
     const size_t crow = (size_t)b * T, qrow = (size_t)b * Lq;
+    const size_t vrow = VIDX ? (size_t)vidx[b] * T : crow;      // first row of this sample's context in C
     {   // one batch of 16-byte loads for both tiles, dropout applied on the way into LDS
         float4 cv[4], qv[8];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int e = tid + q * 256, rr = e >> 5, c = (e & 31) * 4;
             const int t = min(t0 + rr, T - 1);
-            cv[q] = *reinterpret_cast<const float4*>(C + (crow + t) * D + c);
+            cv[q] = *reinterpret_cast<const float4*>(C + (vrow + t) * D + c);
         }
         auto load_q = [&](int q0) {               // query rows 8 q0 .. : 8 float4 per thread (64 words) per pass
 #pragma unroll
@@ -939,31 +942,30 @@ __global__ __launch_bounds__(256) void k_cq_score(const float* __restrict__ C, c
 }
 void launch_cq_score(const float* C, const float* Qf, const float* qmask, const float* w4C, const float* w4Q,
                      const float* w4mlu, float* S, float* Srow, int B, int T, int Lq, int b_off, Drop dc, Drop dq,
-                     hipStream_t s, const CqPoolArgs* pool) {
+                     hipStream_t s, const CqPoolArgs* pool, const int* vidx) {
     CqPool cp{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (pool) cp = CqPool{pool->pool_w, pool->Wcat, pool->bcat, pool->alpha, pool->pooled, pool->pb};
     const int NTJ = (Lq + 31) / 32;
     const size_t shm = (size_t)((TILE_M + 32 * NTJ) * LDP + TILE_M + 32 * NTJ + 4 * TILE_M * (32 * NTJ + 1)) * sizeof(float);
-    static size_t ok8 = 0, ok12 = 0, ok16 = 0;
     const dim3 grid((T + TILE_M - 1) / TILE_M + (pool ? 1 : 0), B);
-    if (Lq <= 64) {
-        ensure_dynamic_lds((const void*)k_cq_score<8>, shm, ok8, "k_cq_score<8>");
-        VSL_LAUNCH(k_cq_score<8>, grid, dim3(256), shm, s, C, Qf, qmask, w4C, w4Q, w4mlu, S, Srow, T, Lq, b_off, dc, dq, cp);
-    } else if (Lq <= 96) {
-        ensure_dynamic_lds((const void*)k_cq_score<12>, shm, ok12, "k_cq_score<12>");
-        VSL_LAUNCH(k_cq_score<12>, grid, dim3(256), shm, s, C, Qf, qmask, w4C, w4Q, w4mlu, S, Srow, T, Lq, b_off, dc, dq, cp);
-    } else {
-        ensure_dynamic_lds((const void*)k_cq_score<16>, shm, ok16, "k_cq_score<16>");
-        VSL_LAUNCH(k_cq_score<16>, grid, dim3(256), shm, s, C, Qf, qmask, w4C, w4Q, w4mlu, S, Srow, T, Lq, b_off, dc, dq, cp);
-    }
+    static size_t ok[6] = {0, 0, 0, 0, 0, 0};
+    auto go = [&](auto kern, size_t& granted, const char* name) {
+        ensure_dynamic_lds((const void*)kern, shm, granted, name);
+        VSL_LAUNCH(kern, grid, dim3(256), shm, s, C, Qf, qmask, w4C, w4Q, w4mlu, S, Srow, T, Lq, b_off, dc, dq, cp, vidx);
+    };
+    if (Lq <= 64) { if (vidx) go(k_cq_score<8, true>, ok[3], "k_cq_score<8, true>"); else go(k_cq_score<8, false>, ok[0], "k_cq_score<8>"); }
+    else if (Lq <= 96) { if (vidx) go(k_cq_score<12, true>, ok[4], "k_cq_score<12, true>"); else go(k_cq_score<12, false>, ok[1], "k_cq_score<12>"); }
+    else { if (vidx) go(k_cq_score<16, true>, ok[5], "k_cq_score<16, true>"); else go(k_cq_score<16, false>, ok[2], "k_cq_score<16>"); }
 }
 
+template <bool VIDX>
 __global__ __launch_bounds__(256) void k_cq_col(const float* __restrict__ C, const float* __restrict__ Qf,
                                                 const float* __restrict__ S, const float* __restrict__ cmask,
                                                 const float* __restrict__ qmask, const float* __restrict__ pool_w,
                                                 const float* __restrict__ Wcat, const float* __restrict__ bcat,
                                                 float* __restrict__ Scol, float* __restrict__ Mpart, float* __restrict__ alpha,
-                                                float* __restrict__ pooled, float* __restrict__ pb, int T, int Lq) {
+                                                float* __restrict__ pooled, float* __restrict__ pb, int T, int Lq,
+                                                const int* __restrict__ vidx) {
     // Tile-parallel: workgroup = (32-clip tile, sample).  The column-softmax statistics need every clip of the sample, so
     // each workgroup recomputes them from the sample's whole score matrix (T x Lq floats, L2-resident, all 256 threads);
     // it then writes its S_col tile and the per-tile partial of M = S_col^T C (MFMA, gemm_tn); k_cq_out adds the partials.
@@ -984,7 +986,7 @@ __global__ __launch_bounds__(256) void k_cq_col(const float* __restrict__ C, con
     const int b = blockIdx.y, tl = blockIdx.x, t0 = tl * TILE_M, ntile = gridDim.x - 1;
     const size_t crow = (size_t)b * T, qrow = (size_t)b * Lq;
     if (tl < ntile) {                           // block-uniform
-    load_tile128(Cs, C + crow * D, t0, TILE_M, T);
+    load_tile128(Cs, C + (VIDX ? (size_t)vidx[b] * T : crow) * D, t0, TILE_M, T);
     // ---- column statistics over all T clips: thread = (word j, part); a part walks clips part, part + np, ... -- eight loads in
     //      flight at a time (one load per trip of a data-dependent loop costs a full memory latency per clip)
     const int JW = Lq <= 32 ? 32 : Lq <= 64 ? 64 : 128, np = 256 / JW;
@@ -1059,10 +1061,11 @@ __global__ __launch_bounds__(256) void k_cq_col(const float* __restrict__ C, con
 bool cq_col_folds(int T, int Lq) { return T <= 4 * TILE_M && Lq <= 32; }      // (k_cq_out's fold: at most four tiles per sample, one 32-word tile of M)
 void launch_cq_col(const float* C, const float* Qf, const float* S, const float* cmask, const float* qmask,
                    const float* pool_w, const float* Wcat, const float* bcat, float* Scol, float* Mpart, float* alpha,
-                   float* pooled, float* pb, int B, int T, int Lq, hipStream_t s) {
+                   float* pooled, float* pb, int B, int T, int Lq, hipStream_t s, const int* vidx) {
     const size_t shm = (size_t)(TILE_M * LDP + TILE_M * (Lq + 1) + 72 + 2 * 8 * 128 + 3 * 128 + D) * sizeof(float);
-    VSL_LAUNCH(k_cq_col, dim3((T + TILE_M - 1) / TILE_M + 1, B), dim3(256), shm, s, C, Qf, S, cmask, qmask, pool_w, Wcat, bcat, Scol,
-                       Mpart, alpha, pooled, pb, T, Lq);
+    const dim3 grid((T + TILE_M - 1) / TILE_M + 1, B);
+    if (vidx) VSL_LAUNCH(k_cq_col<true>, grid, dim3(256), shm, s, C, Qf, S, cmask, qmask, pool_w, Wcat, bcat, Scol, Mpart, alpha, pooled, pb, T, Lq, vidx);
+    else VSL_LAUNCH(k_cq_col<false>, grid, dim3(256), shm, s, C, Qf, S, cmask, qmask, pool_w, Wcat, bcat, Scol, Mpart, alpha, pooled, pb, T, Lq, vidx);
 }
 
 // CQConcatenate + HighLightLayer + gating (a11 / a12, VSLNet_t7.py:60) ride on the same kernel (row-local on the tile just produced)
@@ -1075,11 +1078,13 @@ struct CqCatFuse {
     const float *S, *cmask;
     float* Scol;
 };
+template <bool VIDX>
 __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, const float* __restrict__ Qf,
                                                 const float* __restrict__ Srow, const float* __restrict__ Mpart,
                                                 float* __restrict__ M, const float* __restrict__ Wpack,
                                                 const float* __restrict__ bias, float* __restrict__ cat_out,
-                                                float* __restrict__ out, int T, int Lq, CqCatFuse cf) {
+                                                float* __restrict__ out, int T, int Lq, CqCatFuse cf,
+                                                const int* __restrict__ vidx) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int LQ1 = Lq + 1;
     // Lq > CQ_BIG_LQ: M lives where the concat tile will be written (it is dead by then, behind one extra barrier): 101 instead of 167 KB
@@ -1092,8 +1097,9 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, hh = lane >> 5;
     const int b = blockIdx.y, t0 = blockIdx.x * TILE_M, ntile = gridDim.x;
     const size_t crow = (size_t)b * T, qrow = (size_t)b * Lq;
+    const size_t vrow = VIDX ? (size_t)vidx[b] * T : crow;      // first row of this sample's context in C
     BFrag<1, 16> bf;
-    load_tile128(Cs, C + crow * D, t0, TILE_M, T);
+    load_tile128(Cs, C + vrow * D, t0, TILE_M, T);
     if (cf.S) {                                // (block-uniform) k_cq_col's work for the whole sample, in the concat tile's LDS (dead until the concat)
         constexpr int JS = 128;
         float* Ct = Cat;                       // [32][LDP]   C tile of the pass
@@ -1145,7 +1151,7 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
         for (int tl = 0; tl < ntile; ++tl) {                 // M[j][c] = sum over ALL clips of the sample, tile by tile (k_cq_col's order within a tile)
             const int tt0 = tl * TILE_M;
             __syncthreads();                                 // the previous pass' product is done with Ct / Sc ; cmax / cinv are written
-            load_tile128(Ct, C + crow * D, tt0, TILE_M, T);
+            load_tile128(Ct, C + vrow * D, tt0, TILE_M, T);
             for (int e = tid; e < TILE_M * LQ1; e += 256) {
                 const int i = e / LQ1, jj = e - i * LQ1;
                 float v = 0.f;
@@ -1296,13 +1302,29 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
 void launch_cq_out(const float* C, const float* Qf, const float* Srow, const float* Mpart, float* M, const float* Wpack,
                    const float* bias, float* cat_out, float* out, const float* W1pack, const float* pb, const float* wh,
                    const float* bh, const float* vmask, float* f2, float* hscore, float* gated, int B, int T, int Lq, hipStream_t s,
-                   const float* S_fold, float* Scol_fold) {
+                   const float* S_fold, float* Scol_fold, const int* vidx) {
     const size_t shm = (Lq > CQ_BIG_LQ ? (size_t)(std::max(TILE_M * CATP, Lq * LDP) + TILE_M * LDP + TILE_M * (Lq + 1) + 32)
                                        : (size_t)(TILE_M * CATP + TILE_M * LDP + Lq * LDP + TILE_M * (Lq + 1) + 32)) * sizeof(float);
-    static size_t lds_ok = 0;
-    ensure_dynamic_lds((const void*)k_cq_out, shm, lds_ok, "k_cq_out");
-    VSL_LAUNCH(k_cq_out, dim3((T + TILE_M - 1) / TILE_M, B), dim3(256), shm, s, C, Qf, Srow, Mpart, M, Wpack, bias, cat_out, out,
-                       T, Lq, CqCatFuse{W1pack, pb, wh, bh, vmask, f2, hscore, gated, S_fold, S_fold ? vmask : nullptr, Scol_fold});
+    static size_t lds_ok = 0, lds_ok_v = 0;
+    const dim3 grid((T + TILE_M - 1) / TILE_M, B);
+    const CqCatFuse cf{W1pack, pb, wh, bh, vmask, f2, hscore, gated, S_fold, S_fold ? vmask : nullptr, Scol_fold};
+    if (vidx) {
+        ensure_dynamic_lds((const void*)k_cq_out<true>, shm, lds_ok_v, "k_cq_out<true>");
+        VSL_LAUNCH(k_cq_out<true>, grid, dim3(256), shm, s, C, Qf, Srow, Mpart, M, Wpack, bias, cat_out, out, T, Lq, cf, vidx);
+    } else {
+        ensure_dynamic_lds((const void*)k_cq_out<false>, shm, lds_ok, "k_cq_out");
+        VSL_LAUNCH(k_cq_out<false>, grid, dim3(256), shm, s, C, Qf, Srow, Mpart, M, Wpack, bias, cat_out, out, T, Lq, cf, vidx);
+    }
+}
+
+// the (N, T) clip mask of a resident encoding expanded to one row per query: out[b][t] = vmask[vidx[b]][t] (vsl_localize; the predictor, head and
+// LSTM kernels index their mask by sample)
+__global__ __launch_bounds__(256) void k_vmask_gather(const float* __restrict__ vmask, const int* __restrict__ vidx, float* __restrict__ out, int T) {
+    const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    if (t < T) out[(size_t)b * T + t] = vmask[(size_t)vidx[b] * T + t];
+}
+void launch_vmask_gather(const float* vmask, const int* vidx, float* out, int B, int T, hipStream_t s) {
+    VSL_LAUNCH(k_vmask_gather, dim3((T + 255) / 256, B), dim3(256), 0, s, vmask, vidx, out, T);
 }
 
 

@@ -279,16 +279,20 @@ void launch_query_fwd(const QueryFwdArgs& a, int B, hipStream_t s);
 struct CqPoolArgs { const float *pool_w, *Wcat, *bcat; float *alpha, *pooled, *pb; };
 bool cq_col_folds(int T, int Lq);
 // (nullable in the three CQ launchers -- read by the backward alone: alpha, pooled, Scol / Scol_fold, M, cat_out, out, f2)
+// vidx (nullable, device, B ints; vsl_localize): C is a resident (N, T, 128) encoding and sample b reads the rows of video vidx[b] (0 <= vidx[b] < N is the
+// caller's precondition); every output stays per sample.  nullptr: C is (B, T, 128) -- the instantiations of the training / inference forward.
 void launch_cq_score(const float* C, const float* Qf, const float* qmask, const float* w4C, const float* w4Q,
                      const float* w4mlu, float* S, float* Srow, int B, int T, int Lq, int b_off, Drop dc, Drop dq,
-                     hipStream_t s, const CqPoolArgs* pool = nullptr);
+                     hipStream_t s, const CqPoolArgs* pool = nullptr, const int* vidx = nullptr);
 void launch_cq_col(const float* C, const float* Qf, const float* S, const float* cmask, const float* qmask,
                    const float* pool_w, const float* Wcat, const float* bcat, float* Scol, float* Mpart /*[B][ntile][Lq][128]*/,
-                   float* alpha, float* pooled, float* pb, int B, int T, int Lq, hipStream_t s);
+                   float* alpha, float* pooled, float* pb, int B, int T, int Lq, hipStream_t s, const int* vidx = nullptr);
 void launch_cq_out(const float* C, const float* Qf, const float* Srow, const float* Mpart, float* M, const float* Wpack,
                    const float* bias, float* cat_out, float* out, const float* W1pack, const float* pb, const float* wh,
                    const float* bh, const float* vmask, float* f2, float* hscore, float* gated, int B, int T, int Lq, hipStream_t s,
-                   const float* S_fold = nullptr, float* Scol_fold = nullptr);
+                   const float* S_fold = nullptr, float* Scol_fold = nullptr, const int* vidx = nullptr);
+// out (B, T) = vmask (N, T) rows vidx[b]: the per-query copy of a resident encoding's clip mask (vsl_localize)
+void launch_vmask_gather(const float* vmask, const int* vidx, float* out, int B, int T, hipStream_t s);
 void launch_head_fwd(const HeadArgs& a0, const HeadArgs& a1, const float* x, const float* vmask, int R, hipStream_t s);
 
 // ---------------------------------------------------------------- losses / eval

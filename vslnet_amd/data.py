@@ -234,6 +234,22 @@ class ResidentSplit:
             out += [self.d_s[idx_dev], self.d_e[idx_dev], torch.index_select(self.d_h[:, :T], 0, idx_dev)]
         return out
 
+    def encode(self, model, videos_per_call=64):
+        """Every video of the split through `model.encode_video`, once, at the split's Tmax: -> VideoEncoding over `self.feats` (row i = video i,
+        the values of `d_vid`), for `model.localize(enc, split.d_vid[idx], ...)`.  `videos_per_call` videos go through the encoder at a time (its
+        scratch is five (videos, Tmax, 128) tensors); the result is one (n_videos, Tmax, 128) tensor.  eval() + no_grad(), like encode_video."""
+        from .engine import VideoEncoding
+        nv, tmax = int(self.feats.shape[0]), int(self.feats.shape[1])
+        vlen = np.zeros(nv, dtype=np.int64)
+        vlen[self.vid_of] = self.lens
+        v_mask = (torch.arange(tmax, device=self.device)[None, :] < torch.from_numpy(vlen).to(self.device)[:, None]).float()
+        full, part = torch.empty((nv, tmax, 128), dtype=torch.float32, device=self.device), None
+        step = max(1, int(videos_per_call))
+        for a in range(0, nv, step):
+            part = model.encode_video(self.feats[a:a + step], v_mask[a:a + step])
+            full[a:a + step] = part.encoding
+        return VideoEncoding(full, v_mask, owner=part.owner, epoch=part.epoch)
+
     def shards(self, rank=0, world=1, order=None):
         """One dict per GLOBAL batch: this rank's rows on the device + what the losses need about the whole batch."""
         order = self._order(order)

@@ -37,6 +37,31 @@ class vsl_io(C.Structure):
                 ('inference', C.c_int32)]          # (1: Engine.forward(inference=True); an older build loaded for an A/B run never reads it)
 
 
+class vsl_encode_io(C.Structure):
+    _fields_ = [('N', C.c_int32), ('T', C.c_int32), ('params', C.c_void_p), ('video_features', C.c_void_p), ('video_features_bf16', C.c_void_p),
+                ('v_mask', C.c_void_p), ('video_encoding', C.c_void_p), ('workspace', C.c_void_p)]
+
+
+class vsl_localize_io(C.Structure):
+    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('Lq', C.c_int32), ('Lc', C.c_int32), ('N', C.c_int32),
+                ('params', C.c_void_p), ('pad_vec', C.c_void_p), ('glove_vec', C.c_void_p),
+                ('word_ids', C.c_void_p), ('char_ids', C.c_void_p), ('q_mask', C.c_void_p),
+                ('video_encoding', C.c_void_p), ('v_mask', C.c_void_p), ('video_index', C.c_void_p),
+                ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('workspace', C.c_void_p)]
+
+
+class VideoEncoding:
+    """What Engine.encode_video returns and Engine.localize reads: the shared feature encoder's output for N videos padded to T clips, and their
+    clip masks.  It belongs to its T and to the parameter values it was computed with (include/vslnet_hip.h).  `owner` / `epoch` are set by
+    VSLNet.encode_video: the module refuses a handle of another module or of parameters that may have changed since."""
+    __slots__ = ('encoding', 'v_mask', 'N', 'T', 'owner', 'epoch')
+
+    def __init__(self, encoding, v_mask, owner=None, epoch=None):
+        self.encoding, self.v_mask = encoding, v_mask
+        self.N, self.T = int(encoding.shape[0]), int(encoding.shape[1])
+        self.owner, self.epoch = owner, epoch
+
+
 class vsl_loss_io(C.Structure):
     _fields_ = [('start_labels', C.c_void_p), ('end_labels', C.c_void_p), ('h_labels', C.c_void_p),
                 ('w_loc', C.c_float), ('w_highlight', C.c_float), ('inv_batch', C.c_float), ('mask_sum', C.c_float),
@@ -60,7 +85,8 @@ class VslError(RuntimeError):
 ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count', 'vsl_param_info', 'vsl_param_floats',
                'vsl_workspace_floats', 'vsl_forward', 'vsl_loss', 'vsl_backward', 'vsl_extract_index',
                'vsl_adamw_step', 'vsl_workspace_offset', 'vsl_profile_select', 'vsl_profile_read', 'vsl_profile_launch', 'vsl_abi_version',
-               'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats']
+               'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats',
+               'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -105,6 +131,11 @@ def load_library():
     lib.vsl_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
     if hasattr(lib, 'vsl_inference_workspace_floats'):       # (absent from an older build loaded through VSLNET_HIP_LIB for an A/B run)
         lib.vsl_inference_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    if hasattr(lib, 'vsl_localize'):                         # (likewise: one encoding per video, many queries)
+        lib.vsl_encode_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        lib.vsl_localize_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        lib.vsl_encode_video.argtypes = [C.c_void_p, C.POINTER(vsl_encode_io), C.c_void_p]
+        lib.vsl_localize.argtypes = [C.c_void_p, C.POINTER(vsl_localize_io), C.c_void_p]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
     lib.vsl_loss.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_loss_io), C.c_void_p]
     lib.vsl_backward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -181,6 +212,8 @@ class Engine:
         # keeps the saved path.  `use_inference = False` forces that on a current build too (A/B runs, tests)
         self.has_inference = hasattr(self.lib, 'vsl_inference_workspace_floats')
         self.use_inference = True
+        # vsl_encode_video / vsl_localize: one encoding per video, many queries against it.  An older build has neither; both methods then raise
+        self.has_shared_video = hasattr(self.lib, 'vsl_encode_video') and hasattr(self.lib, 'vsl_localize')
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -249,6 +282,37 @@ class Engine:
             self._call(self.lib.vsl_workspace_floats(self.h, B, T, Lq, Lc, C.byref(n)))
         return int(n.value)
 
+    def _need_shared_video(self):
+        if not self.has_shared_video:
+            raise VslError('the loaded library has no shared-video entry points (vsl_encode_video / vsl_localize are missing)')
+
+    def encode_workspace_floats(self, N, T):
+        """Floats an encode_video call of N videos padded to T clips needs (operand packs + one encoder application's scratch)."""
+        self._need_shared_video()
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._call(self.lib.vsl_encode_workspace_floats(self.h, N, T, C.byref(n)))
+        return int(n.value)
+
+    def localize_workspace_floats(self, B, T, Lq, Lc):
+        """Floats a localize call of this shape needs (the inference plan without a video pass + the (B, T) gathered mask)."""
+        self._need_shared_video()
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._call(self.lib.vsl_localize_workspace_floats(self.h, B, T, Lq, Lc, C.byref(n)))
+        return int(n.value)
+
+    def _grow_ws(self, n):
+        """The one shared workspace (see workspace()), grown to at least `n` floats."""
+        if self._ws is None or self._ws.numel() < n:
+            # drop EVERY reference to the old one first (the last forward's io / keep-alive tuple hold it too): old and new must not
+            # coexist at the growth peak beside an HBM-resident dataset (ADVICE r2)
+            self._ws = None
+            self._last = self._last_ws = self._keep = None
+            self._ws = torch.empty(int(n * 1.25) if self._grown else n, dtype=torch.float32, device=self.device)
+            self._grown = True
+        return self._ws
+
     def workspace(self, B, T, Lq, Lc, inference=False):
         """ONE caller-owned workspace, grown to the largest shape seen: its contents only live from a forward to the
         backward of the same batch, and the collate narrows every batch to its own max T / Lq / Lc, so real-data training
@@ -258,20 +322,13 @@ class Engine:
         n = C.c_int64()
         with torch.cuda.device(self.device):
             self._call((self.lib.vsl_inference_workspace_floats if inference else self.lib.vsl_workspace_floats)(self.h, B, T, Lq, Lc, C.byref(n)))
-        if self._ws is None or self._ws.numel() < n.value:
-            # drop EVERY reference to the old one first (the last forward's io / keep-alive tuple hold it too): old and new must not
-            # coexist at the growth peak beside an HBM-resident dataset
-            self._ws = None
-            self._last = self._last_ws = self._keep = None
-            self._ws = torch.empty(int(n.value * 1.25) if self._grown else n.value, dtype=torch.float32, device=self.device)
-            self._grown = True
-        return self._ws
+        return self._grow_ws(n.value)
 
     def ws_view(self, name, shape):
         """Saved activation `name` of the LAST forward as a tensor view (parity tests)."""
         io = self._last
         if io is not None and io.inference:
-            raise VslError('ws_view(%r): the last forward was an inference forward, which saves nothing' % (name,))
+            raise VslError('ws_view(%r): the last forward was an inference forward (or encode_video / localize), which saves nothing' % (name,))
         off = self.lib.vsl_workspace_offset(self.h, io.B, io.T, io.Lq, io.Lc, name.encode())
         if off < 0:
             raise KeyError(name)
@@ -328,6 +385,87 @@ class Engine:
         self.inference_forwards += int(bool(inference))
         # keep every tensor the io struct points to alive until the backward
         self._keep = (flat, pad_vec, glove_vec, word_ids, char_ids, vfeats, v_mask, q_mask, out, ws)
+        return out[0], out[1], out[2]
+
+    # ---- one encoding per video, many queries against it (evaluation only) ---------------------------------
+    def _no_saves(self, keep):
+        """encode_video / localize ran in the shared workspace: whatever an earlier training forward saved there is gone, so backward() and
+        ws_view() raise until the next saved-path forward (a marker in place of that forward's io, as after forward(inference=True))."""
+        mark = vsl_io()
+        mark.inference = 1
+        self._last, self._last_ws, self._keep = mark, None, keep
+
+    def encode_video(self, flat, vfeats, v_mask):
+        """VisualProjection + the video pass of the shared feature encoder for N videos, once: -> VideoEncoding (encoding (N, T, 128), v_mask (N, T)).
+        No dropout, nothing saved.  `vfeats` in torch.bfloat16 selects the bf16 throughput mode, as in forward().  The encoding is the `venc`
+        of forward() on these videos, bit for bit, and belongs to this T and to these parameter values."""
+        self._need_shared_video()
+        if vfeats.dim() != 3 or vfeats.shape[0] < 1:
+            raise ValueError('encode_video: video_features must be (N, T, video_feature_dim) with N >= 1 videos, got %s' % (tuple(vfeats.shape),))
+        N, T, Dv = vfeats.shape
+        bf16 = vfeats.dtype == torch.bfloat16
+        _chk(flat, torch.float32, (self.param_floats,), 'params')
+        _chk(vfeats, torch.bfloat16 if bf16 else torch.float32, (N, T, self.cfg.video_feature_dim), 'video_features')
+        _chk(v_mask, torch.float32, (N, T), 'v_mask')
+        self._flush_loss()
+        ws = self._grow_ws(self.encode_workspace_floats(N, T))
+        enc = torch.empty(N, T, 128, dtype=torch.float32, device=self.device)
+        io = vsl_encode_io()
+        io.N, io.T = N, T
+        io.params = _ptr(flat)
+        io.video_features, io.video_features_bf16 = (None, _ptr(vfeats)) if bf16 else (_ptr(vfeats), None)
+        io.v_mask, io.video_encoding, io.workspace = _ptr(v_mask), _ptr(enc), _ptr(ws)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_encode_video(self.h, C.byref(io), stream))
+        self._no_saves((flat, vfeats, v_mask, enc, ws))
+        return VideoEncoding(enc, v_mask)
+
+    def localize(self, flat, pad_vec, glove_vec, enc, video_index, word_ids, char_ids, q_mask):
+        """Everything of forward() behind the video pass, for B queries against the resident encoding `enc`: query b is localised in video
+        video_index[b].  -> (h_score, start_logits, end_logits), each (B, enc.T): the bits of forward(inference=True) on the replicated batch
+        (at a T off the 32-row tile: within a few 1e-6 of it, include/vslnet_hip.h).
+        `video_index` as a list / numpy array / CPU tensor is range-checked here and uploaded as int32; a DEVICE tensor (int32 or int64) is
+        trusted -- no synchronising read -- and an index outside [0, enc.N) then reads outside the encoding.
+        `flat` must hold the parameter values `enc` was computed with (VSLNet.localize checks that through the handle's epoch)."""
+        self._need_shared_video()
+        if not isinstance(enc, VideoEncoding):
+            raise TypeError('localize: enc must be the VideoEncoding that encode_video returned')
+        N, T = enc.N, enc.T
+        B, Lq, Lc = char_ids.shape
+        if isinstance(video_index, torch.Tensor) and video_index.is_cuda:
+            vidx = video_index.to(torch.int32).contiguous()
+        else:
+            host = torch.as_tensor(video_index).to(torch.int64).reshape(-1)
+            if host.numel() and (int(host.min()) < 0 or int(host.max()) >= N):
+                raise ValueError('localize: video_index out of range: values in [%d, %d], the encoding holds %d videos' % (int(host.min()), int(host.max()), N))
+            vidx = host.to(torch.int32).to(self.device)
+        if B < 1:
+            raise ValueError('localize: empty query batch')
+        _chk(vidx, torch.int32, (B,), 'video_index')
+        _chk(flat, torch.float32, (self.param_floats,), 'params')
+        _chk(enc.encoding, torch.float32, (N, T, 128), 'encoding')
+        _chk(enc.v_mask, torch.float32, (N, T), 'v_mask')
+        _chk(word_ids, torch.int64, (B, Lq), 'word_ids')
+        _chk(char_ids, torch.int64, (B, Lq, Lc), 'char_ids')
+        _chk(q_mask, torch.float32, (B, Lq), 'q_mask')
+        if self.cfg.word_table:
+            pad_vec = glove_vec = None
+        else:
+            _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
+            _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
+        self._flush_loss()
+        ws = self._grow_ws(self.localize_workspace_floats(B, T, Lq, Lc))
+        out = torch.empty(3, B, T, dtype=torch.float32, device=self.device)
+        io = vsl_localize_io()
+        io.B, io.T, io.Lq, io.Lc, io.N = B, T, Lq, Lc, N
+        io.params, io.pad_vec, io.glove_vec = _ptr(flat), _ptr(pad_vec), _ptr(glove_vec)
+        io.word_ids, io.char_ids, io.q_mask = _ptr(word_ids), _ptr(char_ids), _ptr(q_mask)
+        io.video_encoding, io.v_mask, io.video_index = _ptr(enc.encoding), _ptr(enc.v_mask), _ptr(vidx)
+        io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
+        io.workspace = _ptr(ws)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_localize(self.h, C.byref(io), stream))
+        self._no_saves((flat, pad_vec, glove_vec, enc, vidx, word_ids, char_ids, q_mask, out, ws))
         return out[0], out[1], out[2]
 
     def loss(self, start_labels, end_labels, h_labels, w_loc=1.0, w_highlight=5.0, inv_batch=None, mask_sum=0.0,

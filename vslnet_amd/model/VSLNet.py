@@ -107,6 +107,7 @@ class VSLNet(nn.Module):
         self._flat_names = None
         self._step = 0
         self._seed = int(getattr(configs, 'seed', 12345))
+        self._param_epoch = 0          # bumped whenever the parameters may change (train(True), load_state_dict, a move): a VideoEncoding of an older epoch is stale
 
     def init_parameters(self):
         """VSLNet_t7.py:42-50: Xavier-uniform conv/linear weights, zero biases, nn.LSTM.reset_parameters() for the rnn head.
@@ -126,7 +127,17 @@ class VSLNet(nn.Module):
         out = super()._apply(fn, *a, **k)
         self._engine = None            # device / dtype may have changed: rebuild lazily
         self._flat = None
+        self._param_epoch = getattr(self, '_param_epoch', 0) + 1
         return out
+
+    def train(self, mode=True):
+        if mode:
+            self._param_epoch += 1     # training may update the parameters: encodings computed before it are stale
+        return super().train(mode)
+
+    def load_state_dict(self, *a, **k):
+        self._param_epoch += 1
+        return super().load_state_dict(*a, **k)
 
     def _engine_for(self, device):
         if self._engine is not None and self._flat is not None:
@@ -179,6 +190,43 @@ class VSLNet(nn.Module):
                                word_ids.contiguous(), char_ids.contiguous(), video_features.contiguous().float(), v_mask.contiguous().float(),
                                q_mask.contiguous().float(), inference=True)
         return _ForwardFn.apply(self, word_ids, char_ids, video_features, v_mask, q_mask, *self._flat_params)
+
+    # ---- one encoding per video, many queries against it (no reference counterpart: the reference encodes the video once per query) ----
+    def _shared_video_mode(self, what):
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError('VSLNet.%s is evaluation only (nothing is saved for a backward): call it under model.eval() and torch.no_grad()%s'
+                               % (what, ' -- the module is in train mode' if self.training else ' -- grad is enabled'))
+
+    def encode_video(self, video_features, v_mask):
+        """VisualProjection + the shared feature encoder over N videos, once: -> VideoEncoding for `localize`.  (N, T, video_feature_dim)
+        features (fp32, or bfloat16 for the bf16 throughput mode) and the (N, T) clip mask.  The handle belongs to this module, this T and
+        the parameters as they are now: `train()`, `load_state_dict` or moving the module make it stale."""
+        self._shared_video_mode('encode_video')
+        eng = self._engine_for(video_features.device)
+        vf = video_features.contiguous()
+        enc = eng.encode_video(self._flat, vf if vf.dtype == torch.bfloat16 else vf.float(), v_mask.contiguous().float())
+        enc.owner, enc.epoch = self, self._param_epoch
+        return enc
+
+    def localize(self, enc, video_index, word_ids, char_ids, q_mask, T=None):
+        """forward() for B queries against videos that `encode_video` has already encoded: query b is localised in video video_index[b].
+        -> (h_score, start_logits, end_logits), each (B, enc.T): what forward(word_ids, char_ids, features[video_index], v_mask[video_index], q_mask)
+        returns under eval() + no_grad() -- bit for bit at T % 32 == 0 or T <= 32, within a few 1e-6 at other T.  `T` (optional): the padded length the caller expects; an encoding of
+        another T is refused (an encoding belongs to its T: the same video padded to another length encodes differently).
+        `video_index`: list / numpy / CPU tensor (range-checked) or a device tensor (trusted)."""
+        self._shared_video_mode('localize')
+        if getattr(enc, 'owner', None) is not self:
+            raise ValueError('VSLNet.localize: this VideoEncoding was made by another module (or not by VSLNet.encode_video)')
+        if enc.epoch != self._param_epoch:
+            raise ValueError('VSLNet.localize: stale VideoEncoding -- the parameters may have changed since it was computed (train(), load_state_dict '
+                             'or a move ran in between): call encode_video again')
+        if T is not None and int(T) != enc.T:
+            raise ValueError('VSLNet.localize: the encoding was computed at T=%d, not T=%d: an encoding belongs to its padded T, encode again at that T' % (enc.T, int(T)))
+        eng = self._engine_for(enc.encoding.device)
+        self._step += 1                                     # (a graph built on an earlier forward is stale: its saves are overwritten)
+        we = self.embedding_net.word_emb
+        return eng.localize(self._flat, we.pad_vec.data if we.is_pretrained else None, we.glove_vec.data if we.is_pretrained else None, enc,
+                            video_index, word_ids.contiguous(), char_ids.contiguous(), q_mask.contiguous().float())
 
     def extract_index(self, start_logits, end_logits):
         self._engine_for(start_logits.device)

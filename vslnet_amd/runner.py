@@ -194,3 +194,33 @@ def eval_test(model, data_loader, device, mode='test', epoch=None, global_step=N
                 st, et = index_to_time(int(si), int(ei), r['v_len'], r['duration'])
                 ious.append(calculate_iou([st, et], [r['s_time'], r['e_time']]))
     return summarise(ious, epoch, global_step)
+
+
+def eval_test_shared(model, split, device, mode='test', epoch=None, global_step=None, videos_per_call=64):
+    """eval_test over a `data.ResidentSplit` with every video encoded ONCE (split.encode -> VSLNet.encode_video) and each batch of records
+    localised against that resident encoding (VSLNet.localize with the records' video indices): no (B, T, Dv) feature block is gathered and
+    VisualProjection + the video pass of the feature encoder run once per video instead of once per record.  Returns what eval_test returns.
+    An encoding belongs to its padded T, so every batch runs at the split's Tmax: the numbers are those of evaluating with every batch padded to
+    Tmax -- what `model(...)` gives on `split.feats[:, :Tmax][vid]` -- not to the batch maximum as eval_test pads; the two differ, because the
+    conv block's zero padding at the sequence end turns into pad-row values that the attention spreads to every row."""
+    del mode, device
+    ious = []
+    bs, n = split.batch_size, len(split.records)
+    with torch.no_grad():
+        enc = split.encode(model, videos_per_call=videos_per_call)
+        d_order = torch.arange(n, device=split.device)
+        for a in range(0, n, bs):
+            idx = np.arange(a, min(n, a + bs))
+            idx_dev = d_order[a:a + bs]
+            Lq, Lc = int(split.nwords[idx].max()), int(split.nchars[idx].max())
+            word_ids = torch.index_select(split.d_words[:, :Lq], 0, idx_dev)
+            char_ids = torch.index_select(split.d_chars[:, :Lq, :Lc], 0, idx_dev)
+            query_mask = (word_ids != 0).float()
+            _, start_logits, end_logits = model.localize(enc, split.vid_of[idx], word_ids, char_ids, query_mask, T=enc.T)
+            s_idx, e_idx = model.extract_index(start_logits, end_logits)
+            out = torch.stack([s_idx, e_idx]).cpu().numpy()
+            for i, si, ei in zip(idx, out[0], out[1]):
+                r = split.records[i]
+                st, et = index_to_time(int(si), int(ei), r['v_len'], r['duration'])
+                ious.append(calculate_iou([st, et], [r['s_time'], r['e_time']]))
+    return summarise(ious, epoch, global_step)
