@@ -100,7 +100,7 @@ def hip_relu_masks(eng, B, T, Lq, predictor='transformer'):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the HIP path's dropout masks, recomputed on the host (vslnet_amd/csrc/common.hpp: drop_keep_scale, api.hip: Ctx::drop)
+# the HIP path's dropout masks, recomputed on the host (vslnet_amd/csrc/common.hpp: drop_keep_scale, host.hpp: Ctx::drop)
 # ---------------------------------------------------------------------------------------------------------------------------
 _M32 = np.uint64(0xFFFFFFFF)
 
@@ -122,7 +122,7 @@ def hip_site_seed(seed, site):
 
 
 def hip_site_key(seed, site):
-    """second per-site word (api.hip Ctx::drop): xor-ed in between the two multiply rounds of the element hash"""
+    """second per-site word (host.hpp Ctx::drop): xor-ed in between the two multiply rounds of the element hash"""
     k = np.array([hip_site_seed(seed, site) ^ 0x68E31DA4], dtype=np.uint64)
     k ^= k >> np.uint64(15)
     k = (k * np.uint64(0x2C1B3C6D)) & _M32
@@ -142,7 +142,7 @@ def _drop_hash(idx, seed, key):
     return h                                             # (no final xor-shift: the decision is a compare against p * 2^32)
 
 
-# site ids in the order the oracle reaches its dropout calls (api.hip: SITE_* = 64.., encoder pass `app` * 16 + 0..8)
+# site ids in the order the oracle reaches its dropout calls (host.hpp: SITE_* = 64.., encoder pass `app` * 16 + 0..8)
 HIP_DROP_SITES = [64, 65, 66] + list(range(0, 9)) + list(range(16, 25)) + [67, 68] + list(range(32, 41)) + list(range(48, 57))
 
 

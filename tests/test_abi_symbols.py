@@ -24,6 +24,20 @@ def test_library_exports_every_declared_symbol():
     assert sorted(ABI_SYMBOLS) == names
 
 
+def test_build_finds_every_source_and_header():
+    """every translation unit under csrc/ is compiled, and editing any header there (or the public one) makes the library stale"""
+    from vslnet_amd import build
+    csrc = os.path.join(ROOT, 'vslnet_amd', 'csrc')
+    on_disk = sorted(os.listdir(csrc))
+    assert sorted(build.SOURCES) == [f for f in on_disk if f.endswith('.hip')] and len(build.SOURCES) >= 2
+    deps = {os.path.realpath(d) for d in build.dependencies()}
+    for f in on_disk:
+        if f.endswith(('.hip', '.hpp')):
+            assert os.path.realpath(os.path.join(csrc, f)) in deps, f
+    assert os.path.realpath(os.path.join(ROOT, 'include', 'vslnet_hip.h')) in deps
+    assert build.MAX_JOBS <= 16
+
+
 def test_last_error_is_callable_without_gpu():
     from vslnet_amd import build
     lib = ctypes.CDLL(build.build())

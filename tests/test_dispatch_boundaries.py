@@ -13,16 +13,16 @@ import pytest
 
 from tests.helpers import check_training_against_oracle, extreme_ragged
 
-# the ledger labels a row makes a statement about (api.hip LAUNCH names)
+# the ledger labels a row makes a statement about (forward.hip / backward.hip LAUNCH names)
 ROUTE_LABELS = ('attn_block_fwd', 'attn_fwd', 'attn_out_fwd', 'head_fwd', 'qkv_bwd', 'cq_col', 'query_fwd', 'query_bwd', 'linear_fwd',
                 'rnn_fwd', 'rnn_bwd', 'lstm_fwd', 'lstm_bwd')
 
 
 def predicted_routes(B, T, Lq, num_heads=8, predictor='transformer', lazy=True):
     """-> (labels the step launches among ROUTE_LABELS, whether the loss seeds are computed inside the heads' backward), from the predicates:
-    query_fused_ok (kernels_query.hip), enc_fwd's attention choice and attn_block_fwd_hosts_heads (api.hip, launch.hpp), cq_col_folds
+    query_fused_ok (kernels_query.hip), enc_fwd's attention choice and attn_block_fwd_hosts_heads (forward.hip, launch.hpp), cq_col_folds
     (kernels_fwd.hip), convblock_bwd_hosts_qkv + attn_bwd_dq_slabs (kernels_enc.hip, kernels_bwd.hip), rnn_fused_ok (kernels_lstm.hip) and
-    run_backward's seeds_inline (api.hip)."""
+    run_backward's seeds_inline (backward.hip)."""
     h8 = num_heads == 8
     query_local = h8 and Lq <= 32
     enc_L = [T] + ([] if query_local else [Lq]) + ([T, T] if predictor == 'transformer' else [])      # the encoder applications' lengths

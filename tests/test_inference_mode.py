@@ -17,7 +17,7 @@ from oracle import vslnet_oracle as O
 from tests.helpers import ROOT, check_routes, extreme_ragged, load_golden
 from tests.test_dispatch_boundaries import ROUTE_LABELS, predicted_routes
 
-# the labels of ROUTE_LABELS that are forward launches (api.hip run_forward / enc_fwd)
+# the labels of ROUTE_LABELS that are forward launches (forward.hip forward_full / enc_fwd)
 FWD_LABELS = tuple(n for n in ROUTE_LABELS if not n.endswith('_bwd'))
 
 

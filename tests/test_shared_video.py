@@ -183,7 +183,7 @@ def _fwd_routes(r):
 
 
 def _video_pass_labels(r):
-    """launches of ONE feature-encoder application over T clips (api.hip enc_fwd)"""
+    """launches of ONE feature-encoder application over T clips (forward.hip enc_fwd)"""
     return ['convblock_fwd'] + (['attn_block_fwd'] if r['heads'] == 8 and r['T'] <= 128 else ['attn_fwd', 'attn_out_fwd'])
 
 

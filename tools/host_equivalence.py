@@ -1,0 +1,201 @@
+"""Did a change of the HOST code (vslnet_amd/csrc: api / layout / plan / streams / forward / backward) change anything a caller can observe?
+
+    VSLNET_HIP_LIB=vslnet_amd/lib/libvslnet_hip_base.so python tools/host_equivalence.py dump base.json      # tools/build_base.py <rev> base
+    python tools/host_equivalence.py dump new.json
+    python tools/host_equivalence.py diff base.json new.json          # prints every difference; exit status 1 on any
+
+`dump` runs seeded synthetic batches against whichever library VSLNET_HIP_LIB selects and records per case
+  * the launch ledger of the call(s) as (name, stream index, dependencies) from Engine.profile_launches() -- timestamps dropped;
+  * the four workspace sizes of the shape and vsl_workspace_offset of every name it knows;
+  * SHA-256 of every output: h_score, both logits, the extracted indices, the losses, the gradient bucket, and parameters + both moments
+    after the fused optimizer step of that backward.
+Cases: every row of tests/test_dispatch_boundaries.py::ROWS as one training step (dropout on, fixed seed, fused optimizer step) and as an
+inference forward; encode_video + localize with a repeated and permuted video index, both predictors, fp32 and bf16 features; the headline
+bench shape; one B > 80 rnn shape (chunked LSTM launches over three streams).  The whole set runs three times, each in a fresh child process
+(the switches are read once per process): default, VSL_MULTI_STREAM=0, and every fusion switch off.  The children run one after the other,
+each under its own time limit; the tool stops at the first one that does not exit with 0."""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MODES = {
+    'default': {},
+    'single_stream': {'VSL_MULTI_STREAM': '0'},
+    'unfused': {'VSL_QKV_FUSED': '0', 'VSL_HEADS_FUSED': '0', 'VSL_QUERY_FUSED': '0', 'VSL_CQ_FOLD': '0', 'VSL_LOSS_INLINE': '0'},
+}
+ENC = ('venc', 'qenc', 'p1', 'p2')
+OFFSET_NAMES = ['video_affine', 'embedding_net', 'emb_concat', 'venc', 'qenc', 'venc_x0', 'venc_conv0', 'venc_conv3', 'venc_q', 'venc_k', 'venc_v', 'venc_att',
+                'venc_r', 'qenc_conv3', 'qenc_att', 'cq_score', 'cq_srow', 'cq_scol', 'cq_M', 'cq_attention', 'cq_concat', 'gated', 'pred_s', 'pred_e',
+                'd_gated_enc', 'd_gated_hs', 'd_gated_he', 'd_venc', 'd_qenc', 'd_video_affine', 'd_embedding_net', 'd_pred_s', 'd_pred_s_head',
+                'd_cq_concat', 'd_cq_attention', 'd_emb_concat', 'hid_s', 'hid_e', 'no_such_name'] + \
+               ['relu_%s_%d' % (e, i) for e in ENC for i in range(4)] + ['%s_y%d' % (e, i) for e in ENC for i in range(4)] + ['%s_x0' % e for e in ENC]
+STEP_SEED = (5 << 33) + 2024
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def ledger(eng):
+    return [[r['name'], r['stream'], r['deps']] for r in eng.profile_launches()]
+
+
+def setup(cfgkw, B, T, Lq, Lc, ragged_extreme=False):
+    import torch  # noqa: F401
+    from oracle import vslnet_oracle as O
+    from tests.helpers import extreme_ragged
+    from vslnet_amd.engine import Engine, flat_from_state_dict
+    kw = dict(max_pos_len=max(T, Lq), word_size=102, drop_rate=0.2)
+    kw.update(cfgkw)
+    cfg = O.make_cfg(**kw)
+    P = O.random_params(cfg, seed=301)
+    b = O.synthetic_batch(cfg, B, T, Lq, Lc, seed=302, ragged=True)
+    if ragged_extreme:
+        b = extreme_ragged(b)
+    d = {k: v.cuda().contiguous() for k, v in b.items()}
+    eng = Engine(cfg)
+    flat = flat_from_state_dict(eng, P)
+    pad, glove = P['embedding_net.word_emb.pad_vec'].cuda(), P['embedding_net.word_emb.glove_vec'].cuda()
+    return eng, flat, pad, glove, b, d
+
+
+def sizes_and_offsets(eng, B, T, Lq, Lc):
+    """(after a training forward: vsl_workspace_offset refuses everything after an inference forward)"""
+    import ctypes as C
+    eng.lib.vsl_workspace_offset.restype = C.c_int64
+    out = {'workspace_floats': eng.workspace_floats(B, T, Lq, Lc), 'inference_workspace_floats': eng.inference_workspace_floats(B, T, Lq, Lc),
+           'encode_workspace_floats': eng.encode_workspace_floats(B, T), 'localize_workspace_floats': eng.localize_workspace_floats(B, T, Lq, Lc)}
+    out['offsets'] = {n: int(eng.lib.vsl_workspace_offset(eng.h, B, T, Lq, Lc, n.encode())) for n in OFFSET_NAMES}
+    return out
+
+
+def train_and_infer(cfgkw, B, T, Lq, Lc=6, lazy=True, ragged_extreme=False):
+    import torch
+    eng, flat, pad, glove, b, d = setup(cfgkw, B, T, Lq, Lc, ragged_extreme)
+    rec = {}
+    eng.profile_select('*')
+    h, sl, el = eng.forward(flat, pad, glove, d['word_ids'], d['char_ids'], d['vfeats'], d['v_mask'], d['q_mask'], training=True, seed=STEP_SEED)
+    rec.update(sizes_and_offsets(eng, B, T, Lq, Lc))
+    if lazy:
+        losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0, inv_batch=1.0 / B, mask_sum=float(b['v_mask'].sum()), lazy=True)
+    else:
+        losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0)
+    m, v = torch.zeros_like(flat), torch.zeros_like(flat)
+    g = eng.backward(d_h, d_sl, d_el, eng.new_flat(), fused_step=dict(flat=flat, exp_avg=m, exp_avg_sq=v, lr=1e-3, step=1, clip_norm=1.0))
+    si, ei = eng.extract_index(sl, el)
+    torch.cuda.synchronize()
+    rec['train_ledger'] = ledger(eng)
+    rec['train'] = {'h_score': sha(h), 'start_logits': sha(sl), 'end_logits': sha(el), 'start_index': sha(si), 'end_index': sha(ei), 'losses': sha(losses),
+                    'seeds': sha(torch.stack([d_h, d_sl, d_el])), 'grads': sha(g), 'params_after_step': sha(flat), 'exp_avg': sha(m), 'exp_avg_sq': sha(v)}
+    eng.profile_select('*')
+    h, sl, el = eng.forward(flat, pad, glove, d['word_ids'], d['char_ids'], d['vfeats'], d['v_mask'], d['q_mask'], inference=True)
+    si, ei = eng.extract_index(sl, el)
+    torch.cuda.synchronize()
+    rec['infer_ledger'] = ledger(eng)
+    rec['infer'] = {'h_score': sha(h), 'start_logits': sha(sl), 'end_logits': sha(el), 'start_index': sha(si), 'end_index': sha(ei)}
+    eng.profile_select(None)
+    return rec
+
+
+def shared_video(cfgkw, N, B, T, Lq, bf16, Lc=6):
+    import torch
+    eng, flat, pad, glove, b, d = setup(dict(cfgkw, drop_rate=0.0), B, T, Lq, Lc)
+    vf = d['vfeats'][:N].contiguous()
+    if bf16:
+        vf = vf.to(torch.bfloat16)
+    idx = [(7 * i + 3) % N for i in range(B)]          # repeated and permuted
+    rec = {'encode_workspace_floats': eng.encode_workspace_floats(N, T), 'localize_workspace_floats': eng.localize_workspace_floats(B, T, Lq, Lc)}
+    eng.profile_select('*')
+    enc = eng.encode_video(flat, vf, d['v_mask'][:N].contiguous())
+    torch.cuda.synchronize()
+    rec['encode_ledger'] = ledger(eng)
+    eng.profile_select('*')
+    h, sl, el = eng.localize(flat, pad, glove, enc, idx, d['word_ids'], d['char_ids'], d['q_mask'])
+    si, ei = eng.extract_index(sl, el)
+    torch.cuda.synchronize()
+    rec['localize_ledger'] = ledger(eng)
+    eng.profile_select(None)
+    rec['out'] = {'encoding': sha(enc.encoding), 'h_score': sha(h), 'start_logits': sha(sl), 'end_logits': sha(el), 'start_index': sha(si), 'end_index': sha(ei)}
+    return rec
+
+
+def child(out_path):
+    from tests.test_dispatch_boundaries import ROWS
+    cases = {}
+    for p in ROWS:
+        r = p.values[0]
+        cases['row:' + p.id] = train_and_infer(dict(num_heads=r['heads'], predictor=r['predictor'], video_feature_dim=r['Dv'], word_dim=r['word_dim']),
+                                               r['B'], r['T'], r['Lq'], lazy=r['lazy'], ragged_extreme=r['ragged'])
+    cases['headline:B64-T128-Dv1024-Lq20'] = train_and_infer(dict(video_feature_dim=1024), 64, 128, 20, Lc=10)
+    cases['rnn:B96-T128-chunked'] = train_and_infer(dict(video_feature_dim=64, predictor='rnn'), 96, 128, 9)
+    for pred in ('transformer', 'rnn'):
+        for bf16 in (False, True):
+            for (N, B, T, Lq) in ((3, 8, 64, 9), (2, 5, 160, 33)):
+                cases['shared:%s-%s-N%d-B%d-T%d-Lq%d' % (pred, 'bf16' if bf16 else 'fp32', N, B, T, Lq)] = \
+                    shared_video(dict(video_feature_dim=64, predictor=pred), N, B, T, Lq, bf16)
+    with open(out_path, 'w') as f:
+        json.dump(cases, f)
+
+
+def dump(out_path, timeout=900):
+    lib = os.environ.get('VSLNET_HIP_LIB') or os.path.join(ROOT, 'vslnet_amd', 'lib', 'libvslnet_hip.so')
+    res = {'library': lib, 'library_sha256': hashlib.sha256(open(lib, 'rb').read()).hexdigest() if os.path.exists(lib) else None, 'modes': {}}
+    for mode, env in MODES.items():
+        part = '%s.%s.part' % (out_path, mode)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', part], env=dict(os.environ, **env), timeout=timeout)
+        if r.returncode != 0:
+            print('STOPPED: child of mode %s exited with status %d' % (mode, r.returncode))
+            return 1
+        res['modes'][mode] = json.load(open(part))
+        os.remove(part)
+        print('mode %s: %d cases' % (mode, len(res['modes'][mode])))
+        sys.stdout.flush()
+    with open(out_path, 'w') as f:
+        json.dump(res, f)
+    print('%s: %d cases, library %s sha256 %s' % (out_path, sum(len(m) for m in res['modes'].values()), lib, res['library_sha256']))
+    return 0
+
+
+def walk(a, b, path, out):
+    if isinstance(a, dict) and isinstance(b, dict):
+        for k in sorted(set(a) | set(b)):
+            if k not in a or k not in b:
+                out.append('%s/%s: only in %s' % (path, k, 'A' if k in a else 'B'))
+            else:
+                walk(a[k], b[k], path + '/' + k, out)
+    elif isinstance(a, list) and isinstance(b, list) and path.endswith('_ledger'):
+        if len(a) != len(b):
+            out.append('%s: %d launches against %d' % (path, len(a), len(b)))
+        for i, (x, y) in enumerate(zip(a, b)):
+            if x != y:
+                out.append('%s[%d]: %s against %s' % (path, i, x, y))
+    elif a != b:
+        out.append('%s: %s against %s' % (path, a, b))
+
+
+def diff(pa, pb):
+    A, B = json.load(open(pa)), json.load(open(pb))
+    out = []
+    walk(A['modes'], B['modes'], '', out)
+    for line in out:
+        print(line)
+    n = sum(len(m) for m in A['modes'].values())
+    print('A: %s sha256 %s\nB: %s sha256 %s' % (A['library'], A['library_sha256'], B['library'], B['library_sha256']))
+    print('%d cases in %d modes compared: %s' % (n, len(A['modes']), '%d DIFFERENCES' % len(out) if out else 'no difference'))
+    return 1 if out else 0
+
+
+if __name__ == '__main__':
+    if len(sys.argv) == 3 and sys.argv[1] == '--child':
+        child(sys.argv[2])
+        sys.exit(0)
+    if len(sys.argv) == 3 and sys.argv[1] == 'dump':
+        sys.exit(dump(sys.argv[2]))
+    if len(sys.argv) == 4 and sys.argv[1] == 'diff':
+        sys.exit(diff(sys.argv[2], sys.argv[3]))
+    sys.exit(__doc__)

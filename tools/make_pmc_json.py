@@ -5,7 +5,7 @@ import json
 import sqlite3
 import sys
 
-GROUP = {  # kernel function -> launcher group of vsl_profile_* (api.hip LAUNCH names)
+GROUP = {  # kernel function -> launcher group of vsl_profile_* (forward.hip / backward.hip LAUNCH names)
     'k_attn_bwd_fused': 'attn_bwd', 'k_attn_bwd_dq': 'attn_bwd', 'k_attn_bwd_dkv': 'attn_bwd',
     'k_cq_bwd_a': 'cq_bwd', 'k_cq_bwd_b': 'cq_bwd', 'k_cq_bwd_c': 'cq_bwd', 'k_cq_bwd_d': 'cq_bwd',
     'k_loss_a': 'loss', 'k_loss_b': 'loss', 'k_loss_c': 'loss',

@@ -8,8 +8,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libvslnet_hip.so')
-SOURCES = ['kernels_fwd.hip', 'kernels_bwd.hip', 'kernels_enc.hip', 'kernels_wgrad.hip', 'kernels_split.hip', 'kernels_lstm.hip', 'kernels_query.hip', 'kernels_attn_hd.hip', 'kernels_attn_long.hip', 'kernels_attn_wide.hip', 'api.hip']
-HEADERS = ['common.hpp', 'launch.hpp', os.path.join('..', '..', 'include', 'vslnet_hip.h')]
+MAX_JOBS = 16       # hipcc processes at a time
+
+
+def sources(src_dir=CSRC):
+    """every translation unit of a source directory"""
+    return sorted(f for f in os.listdir(src_dir) if f.endswith('.hip'))
+
+
+def dependencies(src_dir=CSRC):
+    """what the library is stale against: every translation unit and header of the source directory + the public header"""
+    return [os.path.join(src_dir, f) for f in sorted(os.listdir(src_dir)) if f.endswith(('.hip', '.hpp'))] + \
+        [os.path.join(src_dir, '..', '..', 'include', 'vslnet_hip.h')]
+
+
+SOURCES = sources()
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '-Wno-pass-failed']
 # per-file flags.  kernels_wgrad.hip: the split-bf16 loop is hand-scheduled scalar fp32 code; SLP vectorisation turns its subtractions into
 # v_pk_add_f32 + v_mov packing, which is slower beside MFMAs (MI355X_MICROARCH.md, price of fillers)
@@ -27,7 +40,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = dependencies() + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -55,8 +68,8 @@ def build(force=False, verbose=False, csrc=None, out=None, stamps=False):
             sys.stderr.write(r.stderr)
         return obj
 
-    srcs = [s for s in SOURCES if os.path.exists(os.path.join(src_dir, s))]      # (a baseline revision may predate a translation unit)
-    with ThreadPoolExecutor(len(srcs)) as ex:
+    srcs = sources(src_dir)      # (a baseline revision has its own set of translation units)
+    with ThreadPoolExecutor(min(len(srcs), MAX_JOBS)) as ex:
         objs = list(ex.map(cc, srcs))
     r = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC'] + objs + ['-o', lib], capture_output=True, text=True)
     if r.returncode != 0:

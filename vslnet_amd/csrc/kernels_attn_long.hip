@@ -183,6 +183,13 @@ bool attn_dq_query_major(int L) {
 }
 int attn_dq_slabs(int L) { return attn_dq_query_major(L) ? 1 : attn_bwd_dq_slabs(L); }
 
+void launch_attn_fwd_any(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B, int L, int H, int b_off,
+                         Drop d2, hipStream_t s) {
+    if (H <= 2) launch_attn_wide_fwd(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);        // head sizes 128 / 64 (kernels_attn_wide.hip)
+    else if (H != 8) launch_attn_hd_fwd(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);     // head sizes 32 / 8 (kernels_attn_hd.hip)
+    else launch_attn_fwd(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
+}
+
 void launch_attn_bwd_any(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
                          const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2, Drop d3, hipStream_t s) {
     const bool qmaj = attn_dq_query_major(L);

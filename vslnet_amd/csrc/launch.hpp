@@ -1,4 +1,4 @@
-// Host-side launcher prototypes + small POD argument structs shared by kernels_fwd.hip, kernels_bwd.hip, api.hip.
+// Host-side launcher prototypes + small POD argument structs shared by the kernel units (kernels_*.hip) and the host units (host.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -112,7 +112,7 @@ struct ReduceSeg {        // grads[dst + (i / rl) * ds + i % rl] = sum over sour
 // Every kernel of a multi-stream step is launched with a STOP EVENT on its own dispatch packet (hipExtLaunchKernelGGL): a cross-stream
 // ordering point is then a bare hipStreamWaitEvent on the producer's last kernel.  hipEventRecord puts a marker packet into the producer
 // stream instead, which costs it 4-5 us per fork and 7 us more per join (tools/ubench/event_fork.hip: chain 21.6 / fork by record 26.9 /
-// fork by stop event 23.3 / stop event on every dispatch, no waiter 21.6 us per link).  api.hip hands out the events (none = plain launch).
+// fork by stop event 23.3 / stop event on every dispatch, no waiter 21.6 us per link).  streams.hip hands out the events (none = plain launch).
 // The same hook serves the built-in profiler (vsl_profile_select): a profiled launch gets a timing START and STOP event on its own packet, so
 // the measured interval is the kernel's execution and the stream carries no extra marker packets.
 void vsl_launch_events(hipStream_t s, hipEvent_t* start, hipEvent_t* stop);
@@ -224,7 +224,11 @@ bool convblock_bwd_hosts_tail(int R, int L);      // does launch_convblock_bwd h
 bool convblock_bwd_hosts_linear(int R, int L);    // ... and tail 3 (the Embedding linear's data gradient)?
 bool convblock_bwd_hosts_qkv(int R, int L);       // ... and CbBwdArgs::qkv?  (its LN1 partial slabs are then convblock_slabs(R, L) many)
 int convblock_slabs(int R, int L);        // partial slabs per parameter of launch_convblock_bwd (= its grid)
+// The attention core of one encoder application, every head count and every L (kernels_attn_long.hip): what the host units call.  The per-head-size
+// launchers further down (launch_attn_fwd / _bwd: 8 heads, launch_attn_hd_*: 4 / 16, launch_attn_wide_*: 1 / 2) are their implementation.
 // (lse, and r_out / h2_out below, may be null in all the attention launchers: an inference forward does not store them)
+void launch_attn_fwd_any(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B, int L, int H, int b_off,
+                         Drop d2, hipStream_t s);
 void launch_attn_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
                      int L, int H, int b_off, Drop d2, hipStream_t s);
 void launch_attn_out_fwd(const float* att, const float* x, const float* ln_g, const float* ln_b, const float* Wpack,
@@ -317,7 +321,7 @@ void launch_lstm_bwd(const float* dout, const float* dout2, const float* mask, c
 constexpr int LSTM_IMG_FLOATS = 4 * D * D;
 // The rnn head as one launch per direction: three workgroups per sample (start LSTM, W_ih projection, end LSTM) handing steps over through
 // {tag, value} granules.  B <= RNN_FUSED_MAX_B keeps all 3 B workgroups resident beside the side streams' kernels; beyond it the chunked
-// launches above.  `epoch` is new for every launch (a NaN-patterned 21-bit counter); api.hip clears a plan's granule buffers once per
+// launches above.  `epoch` is new for every launch (a NaN-patterned 21-bit counter); forward.hip clears a plan's granule buffers once per
 // workspace and once more whenever the counter has wrapped (rnn_granules_fresh), so a stale word never carries the live tag.
 constexpr int RNN_FUSED_MAX_B = 80;
 struct RnnFwdArgs {

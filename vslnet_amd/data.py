@@ -338,7 +338,7 @@ def synthetic_dataset(configs, n_train=512, n_test=128, n_words=200, n_chars=30,
     return dataset, feats
 
 
-# limits of the HIP engine (vslnet_amd/csrc/common.hpp: MAX_LQ, MAX_LC; api.hip vsl_create): checked against the WHOLE dataset
+# limits of the HIP engine (vslnet_amd/csrc/common.hpp: MAX_LQ, MAX_LC; api.hip vsl_create, plan.hip check_shape): checked against the WHOLE dataset
 # before the first step, so that one long query or token cannot abort a run in the middle of an epoch
 ENGINE_MAX_WORDS, ENGINE_MAX_CHARS, ENGINE_MAX_CHAR_DIM = 128, 40, 128
 ENGINE_MAX_CLIPS = 4096             # common.hpp MAX_L: clips per video the attention kernels serve
