@@ -1,4 +1,4 @@
-"""num_heads 4 and 16 (head sizes 32 and 8): the attention core of kernels_attn_hd.hip, through every layer above it.
+"""num_heads 4 and 16 (head sizes 32 and 8): the attention core of kernels_attn_hd.hip (shared parts: attn.hpp; dispatch: kernels_attn.hip), through every layer above it.
 
 CPU-only tests: vsl_create's head-count validation (it runs before the device query) and the oracle against fixtures the reference
 itself produced with 4 and 16 heads (tools/make_golden_heads.py; each fixture is split into files under 1 MiB).

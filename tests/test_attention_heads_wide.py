@@ -1,4 +1,4 @@
-"""num_heads 1 and 2 (head sizes 128 and 64): the attention core of kernels_attn_wide.hip, through every layer above it.
+"""num_heads 1 and 2 (head sizes 128 and 64): the attention core of kernels_attn_wide.hip (shared parts: attn.hpp; dispatch: kernels_attn.hip), through every layer above it.
 
 CPU-only tests: vsl_create's head-count validation (it runs before the device query) and the oracle against fixtures the reference
 itself produced with 1 and 2 heads (tools/make_golden_heads.py; each fixture is split into files under 1 MiB).

@@ -1,4 +1,4 @@
-"""Long videos: 1024 < T <= 4096 clips (kernels_attn_long.hip: the attention backward's dQ query-major, one dQ slab).
+"""Long videos: 1024 < T <= 4096 clips (k_attn_dq of kernels_attn.hip: the attention backward's dQ query-major, one dQ slab).
 
 CPU-only: validate_dataset refuses a record with more clips than the engine serves.
 GPU: eval-mode parity with the oracle (both predictors, 4 / 8 / 16 heads, ragged lengths), training mode on the same dropout masks (the

@@ -10,7 +10,8 @@
   * SHA-256 of every output: h_score, both logits, the extracted indices, the losses, the gradient bucket, and parameters + both moments
     after the fused optimizer step of that backward.
 Cases: every row of tests/test_dispatch_boundaries.py::ROWS as one training step (dropout on, fixed seed, fused optimizer step) and as an
-inference forward; encode_video + localize with a repeated and permuted video index, both predictors, fp32 and bf16 features; the headline
+inference forward; the smallest shapes that reach the attention kernels those rows do not (1 and 2 heads with the element hash, the pair hash
+over two dQ slabs and query-major dQ; 4 and 16 heads with query-major dQ); encode_video + localize with a repeated and permuted video index, both predictors, fp32 and bf16 features; the headline
 bench shape; one B > 80 rnn shape (chunked LSTM launches over three streams).  The whole set runs three times, each in a fresh child process
 (the switches are read once per process): default, VSL_MULTI_STREAM=0, and every fusion switch off.  The children run one after the other,
 each under its own time limit; the tool stops at the first one that does not exit with 0."""
@@ -35,6 +36,9 @@ OFFSET_NAMES = ['video_affine', 'embedding_net', 'emb_concat', 'venc', 'qenc', '
                 'd_cq_concat', 'd_cq_attention', 'd_emb_concat', 'hid_s', 'hid_e', 'no_such_name'] + \
                ['relu_%s_%d' % (e, i) for e in ENC for i in range(4)] + ['%s_y%d' % (e, i) for e in ENC for i in range(4)] + ['%s_x0' % e for e in ENC]
 STEP_SEED = (5 << 33) + 2024
+# (B, T, Lq) beyond test_dispatch_boundaries.ROWS: T = 129 element hash, 257 pair hash + two dQ slabs, 1025 query-major dQ (the DQ = false instantiations)
+ATTN_SHAPES_LONG = ((1, 1025, 9),)
+ATTN_SHAPES_WIDE = ((2, 129, 9), (2, 257, 9)) + ATTN_SHAPES_LONG
 
 
 def sha(t):
@@ -131,6 +135,9 @@ def child(out_path):
         r = p.values[0]
         cases['row:' + p.id] = train_and_infer(dict(num_heads=r['heads'], predictor=r['predictor'], video_feature_dim=r['Dv'], word_dim=r['word_dim']),
                                                r['B'], r['T'], r['Lq'], lazy=r['lazy'], ragged_extreme=r['ragged'])
+    for H, shapes in ((1, ATTN_SHAPES_WIDE), (2, ATTN_SHAPES_WIDE), (4, ATTN_SHAPES_LONG), (16, ATTN_SHAPES_LONG)):
+        for (B, T, Lq) in shapes:
+            cases['attn:H%d-B%d-T%d-Lq%d' % (H, B, T, Lq)] = train_and_infer(dict(num_heads=H, video_feature_dim=64), B, T, Lq)
     cases['headline:B64-T128-Dv1024-Lq20'] = train_and_infer(dict(video_feature_dim=1024), 64, 128, 20, Lc=10)
     cases['rnn:B96-T128-chunked'] = train_and_infer(dict(video_feature_dim=64, predictor='rnn'), 96, 128, 9)
     for pred in ('transformer', 'rnn'):

@@ -113,9 +113,9 @@ void enc_bwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const float*
         const AttnOutBwdArgs ao = attn_out_bwd_args(c, P, K, w, dy, dy2, app);
         LAUNCH("attn_out_bwd", launch_attn_out_bwd(ao.dy, ao.dy2, ao.r_in, ao.ln_g, ao.WTpack, ao.g_o, ao.dr, ao.p_lng, ao.p_lnb, R, ao.d4, ao.d5, c.s));
     }
-    // every head count, every L: key-major dK / dV; dQ as attn_dq_slabs(L) slabs (L > ATTN_SLAB_MAX_L: query-major into slab 0, kernels_attn_long.hip)
-    LAUNCH("attn_bwd", launch_attn_bwd_any(c.W(w.q), c.W(w.k), c.W(w.v), c.W(w.att), c.W(t.dr), c.W(w.lse), mask, c.W(t.dq), c.W(t.dk),
-                               c.W(t.dv), Bn, L, H, 0, c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.s));
+    // every head count, every L: key-major dK / dV; dQ as attn_dq_slabs(L) slabs (L > ATTN_SLAB_MAX_L: query-major into slab 0, kernels_attn.hip)
+    LAUNCH("attn_bwd", launch_attn_bwd(AttnArgs{c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.W(w.lse), c.W(t.dr), c.W(t.dq), c.W(t.dk), c.W(t.dv),
+                                                Bn, L, H, 0, c.drop(app * 16 + 5), c.drop(app * 16 + 6)}, c.s));
     // whole tiles / sample tiles (and one dQ slab): the conv block's backward kernel computes its own incoming gradient from dq / dk / dv (CbBwdArgs::qk).
     // The gate stays on the key-major slab count: L > 256 never fuses, the one-slab dQ of L > ATTN_SLAB_MAX_L included (k_qkv_bwd adds nothing there)
     static const bool fuse_on = !(getenv("VSL_QKV_FUSED") && getenv("VSL_QKV_FUSED")[0] == '0');

@@ -36,7 +36,7 @@ constexpr int MAX_LQ = 128;     // max query words = the reference's own bound (
 constexpr int CQ_BIG_LQ = 96;   // Lq > CQ_BIG_LQ: one wave per 32-word tile instead of four K-partial tiles, aliased / unstaged buffers
 constexpr int MAX_L = 4096;     // max clips per video (tested limit; the attention kernels stream K/V in blocks, LDS independent of L)
 constexpr int ATTN_SLAB_MAX_L = 1024;  // up to this L the attention backward's dQ leaves the key-major kernels as ceil(L / 256) partial slabs;
-                                       // above it k_attn_dq (kernels_attn_long.hip) writes it once
+                                       // above it k_attn_dq (kernels_attn.hip) writes it once
 
 // ---------------------------------------------------------------------------------------------------------
 // dropout

@@ -42,7 +42,8 @@ static void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const
         return;
     }
     // every other head count, and longer sequences (K / V staged in LDS per 64 queries): the attention core, then the output block
-    LAUNCH("attn_fwd", launch_attn_fwd_any(c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.SV(w.lse), Bn, L, H, 0, c.drop(app * 16 + 5), c.s));
+    LAUNCH("attn_fwd", launch_attn_fwd(AttnArgs{c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.SV(w.lse), nullptr, nullptr, nullptr, nullptr, Bn, L, H, 0,
+                                                c.drop(app * 16 + 5), Drop{}}, c.s));
     LAUNCH("attn_out_fwd", launch_attn_out_fwd(c.W(w.att), c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob), c.SV(w.r), c.SV(w.h2),
                         yout, R, c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8), c.s));
 }

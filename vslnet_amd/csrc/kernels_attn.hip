@@ -1,42 +1,20 @@
-// Attention backward of long videos (1024 < L <= MAX_L): dQ query-major, for every head size (16, 32 and 8: num_heads 8, 4 and 16 here;
-// 128 and 64, num_heads 1 and 2, with the query-major dQ kernel of kernels_attn_wide.hip, which launch_attn_bwd_any hands them to).
+// The attention core's dispatch (launch_attn_fwd / launch_attn_bwd of launch.hpp: head count -> unit, attn.hpp) and the query-major dQ kernel of
+// long videos (1024 < L <= MAX_L) for head sizes 16, 32 and 8 (num_heads 8, 4 and 16; 128 and 64: k_attn_wide_dq of kernels_attn_wide.hip).
 //   a8 (:174-182)  S = Q K^T / sqrt(hd) + (1 - mask[key]) * -1e30 ; P = softmax ; O = drop(P) V
 // The key-major kernels (k_attn_bwd_long, k_attn_hd_bwd) run one workgroup per 256-key block; their dQ is a partial over that block, so up to
 // L = 1024 it leaves them as attn_bwd_dq_slabs(L) (R, 128) slabs that k_qkv_bwd adds.  That workspace and the extra reads grow as L^2 / 256.
 // Above 1024 the key-major kernels compute dK / dV only (their DQ = false instantiation) and k_attn_dq computes dQ in full, once, into slab 0:
 // the dQ workspace is one (R, 128) tensor whatever L is.  VSL_ATTN_DQ_SLABS=1 keeps the slab scheme at every L (comparison only).
-#include "common.hpp"
-#include "launch.hpp"
+#include "attn.hpp"
 
 namespace vsl {
 
 constexpr int ADQ_KB = 128;         // keys staged per block
-template <int HDV> struct AttnDq {
+template <int HDV> struct AttnDq : AttnHead<HDV> {
     static_assert(HDV == 8 || HDV == 16 || HDV == 32, "head sizes 8, 16 and 32");
-    static constexpr int NC = HDV / 4;                  // head dims a lane contributes to an S tile: k group g owns dims g NC .. g NC + NC - 1
-    static constexpr int NT = HDV >= 16 ? HDV / 16 : 1; // 16-row tiles of the head dims in dQ^T (hd 8: half a tile)
-    static constexpr int KST = HDV + 4;                 // LDS row stride of a head slice
-    static constexpr int F4 = HDV / 4;                  // float4 per head-slice row
-    static constexpr int NJ = ADQ_KB * F4 / 256;        // float4 per thread and tensor of a staged block
+    static constexpr int NJ = ADQ_KB * AttnHead<HDV>::F4 / 256;      // float4 per thread and tensor of a staged block
 };
 template <int HDV> constexpr size_t attn_dq_lds() { return (size_t)(2 * ADQ_KB * AttnDq<HDV>::KST + ADQ_KB) * sizeof(float); }
-template <int HDV> __device__ __forceinline__ constexpr float attn_dq_scale() {
-    return HDV == 32 ? 0.17677669529663687f : HDV == 16 ? 0.25f : 0.35355339059327373f;
-}
-
-template <int N> __device__ __forceinline__ void dq_load(const float* p, float* out) {     // N consecutive floats (16-byte aligned for N >= 4)
-    if constexpr (N % 4 == 0) {
-#pragma unroll
-        for (int i = 0; i < N; i += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(p + i);
-            out[i] = v.x; out[i + 1] = v.y; out[i + 2] = v.z; out[i + 3] = v.w;
-        }
-    } else {
-        static_assert(N == 2, "");
-        const float2 v = *reinterpret_cast<const float2*>(p);
-        out[0] = v.x; out[1] = v.y;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // k_attn_dq.  Workgroup = (64 queries, head, sample), wave = 16 queries; lane (qi, g) owns query column qi of the transposed tiles
@@ -68,7 +46,7 @@ __global__ __launch_bounds__(256) void k_attn_dq(const float* __restrict__ Q, co
     const int qi = lane & 15, g = lane >> 4;
     const int q = qbk * 64 + w * 16 + qi;
     const bool qok = q < L;
-    const float scale = attn_dq_scale<HDV>();
+    const float scale = C::scale;
     // B operands of S^T and dP^T: Q[q][g NC + c] and dA[q][g NC + c]
     float qa[NC], aa[NC], oa[NC];
 #pragma unroll
@@ -76,9 +54,9 @@ __global__ __launch_bounds__(256) void k_attn_dq(const float* __restrict__ Q, co
     float lq = 0.f;
     if (qok) {
         const size_t off = (rowbase + q) * D + h * HDV + g * NC;
-        dq_load<NC>(Q + off, qa);
-        dq_load<NC>(dr + off, aa);
-        dq_load<NC>(att + off, oa);
+        load_nc<NC>(Q + off, qa);
+        load_nc<NC>(dr + off, aa);
+        load_nc<NC>(att + off, oa);
         if (d3.thresh) {                           // r = drop3(att) + x  (:183-184): element-keyed, as the key-major kernels stage it
 #pragma unroll
             for (int c = 0; c < NC; ++c) aa[c] *= drop_mul(d3, (uint32_t)(off + c));
@@ -90,8 +68,8 @@ __global__ __launch_bounds__(256) void k_attn_dq(const float* __restrict__ Q, co
     for (int c = 0; c < NC; ++c) dl = fmaf(aa[c], oa[c], dl);
     dl += __shfl_xor(dl, 16);
     dl += __shfl_xor(dl, 32);
-    // dropout of the probabilities as the forward drew it: decision of (row, key) = half (key & 1) of drop_hash(row * ceil(L / 2) + key / 2)
-    const uint32_t prow = (uint32_t)(((size_t)(b + b_off) * H + h) * L + q) * (uint32_t)((L + 1) >> 1);
+    const uint32_t qrow = (uint32_t)(((size_t)(b + b_off) * H + h) * L + q);       // dropout of the probabilities as the forward drew it: key pairs (L > 1024)
+    const uint32_t prow = attn_drop_pair_row(qrow, L);
     const bool dropon = d2.thresh != 0u;
     f32x4 dq[NT];
 #pragma unroll
@@ -108,7 +86,7 @@ __global__ __launch_bounds__(256) void k_attn_dq(const float* __restrict__ Q, co
                 pv[j] = *reinterpret_cast<const float4*>(V + (rowbase + key) * D + h * HDV + c4);
             }
         }
-        if (tid < ADQ_KB) pm = k0 + tid < L ? (1.0f - mask[rowbase + k0 + tid]) * MASK_VALUE : MASK_VALUE;
+        if (tid < ADQ_KB) pm = attn_key_bias(mask, rowbase, k0, tid, L);
     };
     fetch(0);
     for (int k0 = 0; k0 < Lp; k0 += ADQ_KB) {
@@ -126,8 +104,8 @@ __global__ __launch_bounds__(256) void k_attn_dq(const float* __restrict__ Q, co
         for (int kt = 0; kt < nk; kt += 16) {
             // S^T = K Q^T and dP^T = V dA^T: A[i = key][k = g] = K[key][g NC + c] (resp. V), B[k = g][j = query] = Q[q][g NC + c] (resp. dA)
             float ka[NC], va[NC];
-            dq_load<NC>(&Ks[(kt + qi) * KST + g * NC], ka);
-            dq_load<NC>(&Vs[(kt + qi) * KST + g * NC], va);
+            load_nc<NC>(&Ks[(kt + qi) * KST + g * NC], ka);
+            load_nc<NC>(&Vs[(kt + qi) * KST + g * NC], va);
             f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -137,14 +115,7 @@ __global__ __launch_bounds__(256) void k_attn_dq(const float* __restrict__ Q, co
             const float4 mb = *reinterpret_cast<const float4*>(&Mb[kt + 4 * g]);
             const float mbr[4] = {mb.x, mb.y, mb.z, mb.w};
             float m2v[4] = {1.f, 1.f, 1.f, 1.f};
-            if (dropon) {                          // keys 4 g, 4 g + 1 and 4 g + 2, 4 g + 3 of the tile: two pairs, one hash each
-                const uint32_t pi = prow + (uint32_t)((k0 + kt + 4 * g) >> 1);
-                const uint32_t h0 = drop_hash(pi, d2.seed, d2.key), h1 = drop_hash(pi + 1u, d2.seed, d2.key);
-                m2v[0] = h0 >= d2.thresh ? d2.scale : 0.f;
-                m2v[1] = drop_hash_odd(h0) >= d2.thresh ? d2.scale : 0.f;
-                m2v[2] = h1 >= d2.thresh ? d2.scale : 0.f;
-                m2v[3] = drop_hash_odd(h1) >= d2.thresh ? d2.scale : 0.f;
-            }
+            if (dropon) attn_drop_pair4(d2, prow, k0 + kt + 4 * g, m2v);
             float ds[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -170,43 +141,30 @@ __global__ __launch_bounds__(256) void k_attn_dq(const float* __restrict__ Q, co
     }
 }
 
-template <int HDV> static void attn_dq_go(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
-                                          const float* mask, float* dQ, int B, int L, int H, int b_off, Drop d2, Drop d3, hipStream_t s) {
-    static size_t ok = 0;
-    ensure_dynamic_lds((const void*)k_attn_dq<HDV>, attn_dq_lds<HDV>(), ok, "k_attn_dq");
-    VSL_LAUNCH(k_attn_dq<HDV>, dim3((L + 63) / 64, H, B), dim3(256), attn_dq_lds<HDV>(), s, Q, K, V, att, dr, lse, mask, dQ, L, H, b_off, d2, d3);
-}
-
 bool attn_dq_query_major(int L) {
     static const bool slabs = getenv("VSL_ATTN_DQ_SLABS") && getenv("VSL_ATTN_DQ_SLABS")[0] == '1';
     return L > ATTN_SLAB_MAX_L && !slabs;
 }
 int attn_dq_slabs(int L) { return attn_dq_query_major(L) ? 1 : attn_bwd_dq_slabs(L); }
 
-void launch_attn_fwd_any(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B, int L, int H, int b_off,
-                         Drop d2, hipStream_t s) {
-    if (H <= 2) launch_attn_wide_fwd(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);        // head sizes 128 / 64 (kernels_attn_wide.hip)
-    else if (H != 8) launch_attn_hd_fwd(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);     // head sizes 32 / 8 (kernels_attn_hd.hip)
-    else launch_attn_fwd(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
+void launch_attn_fwd(const AttnArgs& a, hipStream_t s) {
+    if (a.H <= 2) launch_attn_wide_fwd(a, s);          // head sizes 128 / 64 (kernels_attn_wide.hip)
+    else if (a.H != 8) launch_attn_hd_fwd(a, s);       // head sizes 32 / 8 (kernels_attn_hd.hip)
+    else launch_attn_h16_fwd(a, s);                    // head size 16 (kernels_attn_h16.hip)
 }
 
-void launch_attn_bwd_any(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
-                         const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2, Drop d3, hipStream_t s) {
-    const bool qmaj = attn_dq_query_major(L);
-    if (H <= 2) {   // head sizes 128 / 64: their own dK / dV and query-major dQ kernels (kernels_attn_wide.hip)
-        launch_attn_wide_bwd(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, qmaj);
-        return;
-    }
-    if (H != 8) launch_attn_hd_bwd(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, !qmaj);
-    else launch_attn_bwd(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, !qmaj);
+void launch_attn_bwd(const AttnArgs& a, hipStream_t s) {
+    const bool qmaj = attn_dq_query_major(a.L);
+    if (a.H <= 2) return launch_attn_wide_bwd(a, qmaj, s);     // their own dK / dV and query-major dQ kernels
+    if (a.H != 8) launch_attn_hd_bwd(a, !qmaj, s);
+    else launch_attn_h16_bwd(a, !qmaj, s);
     if (!qmaj) return;
-    if (H == 8) attn_dq_go<16>(Q, K, V, att, dr, lse, mask, dQ, B, L, H, b_off, d2, d3, s);
-    else if (H == 4) attn_dq_go<32>(Q, K, V, att, dr, lse, mask, dQ, B, L, H, b_off, d2, d3, s);
-    else if (H == 16) attn_dq_go<8>(Q, K, V, att, dr, lse, mask, dQ, B, L, H, b_off, d2, d3, s);
-    else {
-        fprintf(stderr, "launch_attn_bwd_any: num_heads=%d has no attention kernel\n", H);
-        abort();
-    }
+    attn_for_head_size<16, 32, 8>(a.H, [&](auto hd) {
+        constexpr int HDV = decltype(hd)::value;
+        dynamic_lds_optin<k_attn_dq<HDV>>(attn_dq_lds<HDV>(), "k_attn_dq");
+        VSL_LAUNCH(k_attn_dq<HDV>, dim3((a.L + 63) / 64, a.H, a.B), dim3(256), attn_dq_lds<HDV>(), s, a.Q, a.K, a.V, a.att, a.dr, a.lse, a.mask, a.dQ,
+                   a.L, a.H, a.b_off, a.d2, a.d3);
+    });
 }
 
 }  // namespace vsl

@@ -1,5 +1,5 @@
-// Attention core of num_heads 4 and 16 (head sizes 32 and 8), forward and backward.  The 16-wide kernels of 8 heads (k_attn_fwd,
-// k_attn_bwd_fused, k_attn_bwd_long, k_attn_block_fwd) are untouched; api.hip routes every H = 4 / 16 shape here, L <= 128 included
+// Attention core of num_heads 4 and 16 (head sizes 32 and 8), forward and backward.  The 16-wide kernels of 8 heads: kernels_attn_h16.hip and
+// k_attn_block_fwd; kernels_attn.hip routes every H = 4 / 16 shape here, L <= 128 included
 // (num_heads 1 / 2, head sizes 128 / 64: kernels_attn_wide.hip).
 //   a8 (:174-182)  S = Q K^T / sqrt(hd) + (1 - mask[key]) * -1e30 ; P = softmax ; O = drop(P) V
 // Same contracts as the 16-wide pair: Q / K / V / att are (R, 128) rows with head h at columns h hd .. h hd + hd - 1, LSE is saved per
@@ -8,36 +8,14 @@
 // ceil(L / 2) hashes per row) above.
 // Both contractions over the head dims (S = Q K^T, dP = dA V^T) and every other product run on the fp32-input MFMA (v_mfma_f32_16x16x4_f32):
 // exact fp32 products, no split planes.
-#include "common.hpp"
-#include "launch.hpp"
+#include "attn.hpp"
 
 namespace vsl {
 
-template <int HDV> struct AttnHd {
+template <int HDV> struct AttnHd : AttnHead<HDV> {
     static_assert(HDV == 8 || HDV == 32, "head sizes 8 and 32 (16 has its own kernels)");
-    static constexpr int NC = HDV / 4;                  // head dims a lane contributes to an S tile: k group g owns dims g NC .. g NC + NC - 1
-    static constexpr int NT = HDV >= 16 ? HDV / 16 : 1; // 16-row tiles of the head dims in the PV / dK / dV / dQ products (hd 8: half a tile)
-    static constexpr int KST = HDV + 4;                 // LDS row stride of a head slice
     static constexpr int FKB = HDV == 32 ? 128 : 256;   // forward: keys staged per block (37 KB / 25 KB of LDS)
-    static constexpr int F4 = HDV / 4;                  // float4 per head-slice row
 };
-constexpr float AH_LOG2E = 1.4426950408889634f, AH_LN2 = 0.6931471805599453f;
-template <int HDV> __device__ __forceinline__ constexpr float attn_hd_scale() { return HDV == 32 ? 0.17677669529663687f : 0.35355339059327373f; }
-
-// NC consecutive floats (16-byte aligned for NC >= 4, 8-byte for NC = 2)
-template <int N> __device__ __forceinline__ void load_nc(const float* p, float* out) {
-    if constexpr (N % 4 == 0) {
-#pragma unroll
-        for (int i = 0; i < N; i += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(p + i);
-            out[i] = v.x; out[i + 1] = v.y; out[i + 2] = v.z; out[i + 3] = v.w;
-        }
-    } else {
-        static_assert(N == 2, "");
-        const float2 v = *reinterpret_cast<const float2*>(p);
-        out[0] = v.x; out[1] = v.y;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // forward.  Workgroup = (64 queries, head, sample), wave = 16 queries; lane (qi, g) owns query column qi of the transposed score tiles
@@ -68,13 +46,13 @@ __global__ __launch_bounds__(256) void k_attn_hd_fwd(const float* __restrict__ Q
 #pragma unroll
     for (int c = 0; c < NC; ++c) qr[c] = 0.f;
     if (qok) load_nc<NC>(Q + (rowbase + q) * D + h * HDV + g * NC, qr);
-    const float c2 = attn_hd_scale<HDV>() * AH_LOG2E;      // 1 / sqrt(hd) AFTER QK^T (:175), times log2(e)
+    const float c2 = C::scale * ATTN_LOG2E;      // 1 / sqrt(hd) AFTER QK^T (:175), times log2(e)
     float m = -3.0e38f, l = 0.f;
     f32x4 o[NT][2];
 #pragma unroll
     for (int j = 0; j < NT; ++j) o[j][0] = o[j][1] = f32x4{0.f, 0.f, 0.f, 0.f};
     const uint32_t qrow = (uint32_t)(((size_t)(b + b_off) * H + h) * L + q);
-    const uint32_t prow = qrow * (uint32_t)((L + 1) >> 1);
+    const uint32_t prow = attn_drop_pair_row(qrow, L);
     const bool dropon = d2.thresh != 0u;
     float4 pk[NJ], pv[NJ];
     float pm = 0.f;
@@ -88,7 +66,7 @@ __global__ __launch_bounds__(256) void k_attn_hd_fwd(const float* __restrict__ Q
                 pv[j] = *reinterpret_cast<const float4*>(V + (rowbase + key) * D + h * HDV + c4);
             }
         }
-        pm = kb0 + tid < L ? (1.0f - mask[rowbase + kb0 + tid]) * MASK_VALUE : MASK_VALUE;
+        pm = attn_key_bias(mask, rowbase, kb0, tid, L);
     };
     fetch(0);
     for (int kb0 = 0; kb0 < Lp; kb0 += KB) {
@@ -100,7 +78,7 @@ __global__ __launch_bounds__(256) void k_attn_hd_fwd(const float* __restrict__ Q
             *reinterpret_cast<float4*>(&Ks[kl * KST + c4]) = pk[j];
             *reinterpret_cast<float4*>(&Vs[kl * KST + c4]) = pv[j];
         }
-        if (tid < KB) Mb[tid] = pm * AH_LOG2E;
+        if (tid < KB) Mb[tid] = pm * ATTN_LOG2E;
         __syncthreads();
         if (kb0 + KB < Lp) fetch(kb0 + KB);
         for (int kt = 0; kt < nk; kt += 64) {
@@ -140,17 +118,14 @@ __global__ __launch_bounds__(256) void k_attn_hd_fwd(const float* __restrict__ Q
                 float pr[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { pr[r] = __builtin_amdgcn_exp2f(x[t][r] - mn); l += pr[r]; }
-                if (dropon && !PAIR) {
-                    const uint32_t ei = qrow * (uint32_t)L + (uint32_t)k4;
+                if constexpr (!PAIR) {
+                    if (dropon) {
+                        const uint32_t ei = attn_drop_elem(qrow, L, k4);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) pr[r] = drop_hash(ei + r, d2.seed, d2.key) >= d2.thresh ? pr[r] * d2.scale : 0.f;
+                        for (int r = 0; r < 4; ++r) pr[r] = drop_hash(ei + r, d2.seed, d2.key) >= d2.thresh ? pr[r] * d2.scale : 0.f;
+                    }
                 } else if (dropon) {
-                    const uint32_t pi = prow + (uint32_t)(k4 >> 1);
-                    const uint32_t h0 = drop_hash(pi, d2.seed, d2.key), h1 = drop_hash(pi + 1u, d2.seed, d2.key);
-                    pr[0] = h0 >= d2.thresh ? pr[0] * d2.scale : 0.f;
-                    pr[1] = drop_hash_odd(h0) >= d2.thresh ? pr[1] * d2.scale : 0.f;
-                    pr[2] = h1 >= d2.thresh ? pr[2] * d2.scale : 0.f;
-                    pr[3] = drop_hash_odd(h1) >= d2.thresh ? pr[3] * d2.scale : 0.f;
+                    attn_drop_pair4(d2, prow, k4, pr);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -175,31 +150,19 @@ __global__ __launch_bounds__(256) void k_attn_hd_fwd(const float* __restrict__ Q
                 *reinterpret_cast<float4*>(att + (rowbase + q) * D + h * HDV + 16 * j + 4 * g) =
                     make_float4((o[j][0][0] + o[j][1][0]) * inv, (o[j][0][1] + o[j][1][1]) * inv,
                                 (o[j][0][2] + o[j][1][2]) * inv, (o[j][0][3] + o[j][1][3]) * inv);
-        if (g == 0 && lse) lse[((size_t)b * H + h) * L + q] = m * AH_LN2 + __logf(l);
+        if (g == 0 && lse) lse[((size_t)b * H + h) * L + q] = m * ATTN_LN2 + __logf(l);
     }
 }
 
 template <int HDV> constexpr size_t attn_hd_fwd_lds() { return (size_t)(2 * AttnHd<HDV>::FKB * AttnHd<HDV>::KST + AttnHd<HDV>::FKB) * sizeof(float); }
 
-template <int HDV, bool PAIR> static void attn_hd_fwd_go(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse,
-                                                         int B, int L, int H, int b_off, Drop d2, hipStream_t s) {
-    static size_t ok = 0;
-    ensure_dynamic_lds((const void*)k_attn_hd_fwd<HDV, PAIR>, attn_hd_fwd_lds<HDV>(), ok, "k_attn_hd_fwd");
-    VSL_LAUNCH((k_attn_hd_fwd<HDV, PAIR>), dim3((L + 63) / 64, H, B), dim3(256), attn_hd_fwd_lds<HDV>(), s, Q, K, V, mask, att, lse, L, H, b_off, d2);
-}
-void launch_attn_hd_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
-                        int L, int H, int b_off, Drop d2, hipStream_t s) {
-    const bool pair = L > 256;
-    if (H == 4) {
-        if (pair) attn_hd_fwd_go<32, true>(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
-        else attn_hd_fwd_go<32, false>(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
-    } else if (H == 16) {
-        if (pair) attn_hd_fwd_go<8, true>(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
-        else attn_hd_fwd_go<8, false>(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
-    } else {
-        fprintf(stderr, "launch_attn_hd_fwd: num_heads=%d has no attention kernel\n", H);
-        abort();
-    }
+void launch_attn_hd_fwd(const AttnArgs& a, hipStream_t s) {
+    attn_for_head_size<32, 8>(a.H, [&](auto hd) { attn_for_bool(attn_pair_hash(a.L), [&](auto pair) {
+        constexpr int HDV = decltype(hd)::value;
+        dynamic_lds_optin<k_attn_hd_fwd<HDV, decltype(pair)::value>>(attn_hd_fwd_lds<HDV>(), "k_attn_hd_fwd");
+        VSL_LAUNCH((k_attn_hd_fwd<HDV, decltype(pair)::value>), dim3((a.L + 63) / 64, a.H, a.B), dim3(256), attn_hd_fwd_lds<HDV>(), s, a.Q, a.K, a.V, a.mask,
+                   a.att, a.lse, a.L, a.H, a.b_off, a.d2);
+    }); });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -245,9 +208,9 @@ __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ 
         if (k0 + row < L) kv = *reinterpret_cast<const float4*>(K + (rowbase + k0 + row) * D + h * HDV + c4);
         *reinterpret_cast<float4*>(&Ks[row * KST + c4]) = kv;
     }
-    if (tid < AHB_KB) Mb[tid] = k0 + tid < L ? (1.0f - mask[rowbase + k0 + tid]) * MASK_VALUE : MASK_VALUE;
+    if (tid < AHB_KB) Mb[tid] = attn_key_bias(mask, rowbase, k0, tid, L);
     const int ki = lane & 15, g = lane >> 4;
-    const float scale = attn_hd_scale<HDV>();
+    const float scale = C::scale;
     f32x4 dk[NT], dv[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) dk[j] = dv[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -315,14 +278,12 @@ __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ 
                     sc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[c], kr[c], sc, 0, 0, 0);
                     dp = __builtin_amdgcn_mfma_f32_16x16x4f32(aa[c], vr[c], dp, 0, 0, 0);
                 }
-                // dropout of the probabilities as the forward drew it.  PAIR: keys 2 j, 2 j + 1 of a query row share one hash; the lane and its
-                // neighbour (the other key of the pair, same four queries) hash two queries each and exchange the words (as k_attn_bwd_long)
-                float m2v[4] = {1.f, 1.f, 1.f, 1.f};
+                float m2v[4] = {1.f, 1.f, 1.f, 1.f};    // dropout of the probabilities as the forward drew it
                 if (!PAIR) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) m2v[r] = drop_mul(d2, (hb + (uint32_t)(qb + ql0 + 4 * g + r)) * (uint32_t)L + (uint32_t)(k0 + keyl));
+                    for (int r = 0; r < 4; ++r) m2v[r] = drop_mul(d2, attn_drop_elem(hb + (uint32_t)(qb + ql0 + 4 * g + r), L, k0 + keyl));
                 } else if (d2.thresh != 0u) {
-                    const uint32_t Lh = (uint32_t)((L + 1) >> 1), kp = (uint32_t)((k0 + keyl) >> 1);
+                    const uint32_t Lh = attn_drop_pair_stride(L), kp = (uint32_t)((k0 + keyl) >> 1);
                     const int odd = ki & 1;
                     uint32_t hm[2], hp[2];
 #pragma unroll
@@ -331,10 +292,7 @@ __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ 
                         hp[jj] = __float_as_uint(lane_xor1(__uint_as_float(hm[jj])));
                     }
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const uint32_t hr = (r >> 1) == odd ? hm[r & 1] : hp[r & 1];
-                        m2v[r] = (odd ? drop_hash_odd(hr) : hr) >= d2.thresh ? d2.scale : 0.f;
-                    }
+                    for (int r = 0; r < 4; ++r) m2v[r] = attn_drop_pair_mul(d2, odd, (r >> 1) == odd ? hm[r & 1] : hp[r & 1]);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -419,38 +377,18 @@ __global__ __launch_bounds__(1024) void k_attn_hd_bwd(const float* __restrict__ 
     }
 }
 
-template <int HDV, bool PAIR, bool DQ = true> static void attn_hd_bwd_go(const float* Q, const float* K, const float* V, const float* att, const float* dr,
-                                                         const float* lse, const float* mask, float* dQ, float* dK, float* dV, int B, int L,
-                                                         int H, int b_off, Drop d2, Drop d3, hipStream_t s) {
-    static size_t ok = 0;
-    const int Lp = (L + 15) & ~15;
-    ensure_dynamic_lds((const void*)k_attn_hd_bwd<HDV, PAIR, DQ>, attn_hd_bwd_lds<HDV>(), ok, "k_attn_hd_bwd");
-    VSL_LAUNCH((k_attn_hd_bwd<HDV, PAIR, DQ>), dim3((Lp + AHB_KB - 1) / AHB_KB, H, B), dim3(1024), attn_hd_bwd_lds<HDV>(), s, Q, K, V, att, dr, lse,
-               mask, dQ, dK, dV, L, H, b_off, (size_t)B * L * D, d2, d3);
+template <int HDV, bool PAIR, bool DQ> static void attn_hd_bwd_go(const AttnArgs& a, hipStream_t s) {
+    const int Lp = (a.L + 15) & ~15;
+    dynamic_lds_optin<k_attn_hd_bwd<HDV, PAIR, DQ>>(attn_hd_bwd_lds<HDV>(), "k_attn_hd_bwd");
+    VSL_LAUNCH((k_attn_hd_bwd<HDV, PAIR, DQ>), dim3((Lp + AHB_KB - 1) / AHB_KB, a.H, a.B), dim3(1024), attn_hd_bwd_lds<HDV>(), s, a.Q, a.K, a.V, a.att, a.dr,
+               a.lse, a.mask, a.dQ, a.dK, a.dV, a.L, a.H, a.b_off, (size_t)a.B * a.L * D, a.d2, a.d3);
 }
-void launch_attn_hd_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
-                        const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                        Drop d3, hipStream_t s, bool dq) {
-    const bool pair = L > 256;
-    if (!dq) {      // L > ATTN_SLAB_MAX_L (key pairs): dK / dV per key block, dQ from k_attn_dq (launch_attn_bwd_any)
-        if (H == 4) attn_hd_bwd_go<32, true, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
-        else if (H == 16) attn_hd_bwd_go<8, true, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
-        else {
-            fprintf(stderr, "launch_attn_hd_bwd: num_heads=%d has no attention kernel\n", H);
-            abort();
-        }
-        return;
-    }
-    if (H == 4) {
-        if (pair) attn_hd_bwd_go<32, true>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
-        else attn_hd_bwd_go<32, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
-    } else if (H == 16) {
-        if (pair) attn_hd_bwd_go<8, true>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
-        else attn_hd_bwd_go<8, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s);
-    } else {
-        fprintf(stderr, "launch_attn_hd_bwd: num_heads=%d has no attention kernel\n", H);
-        abort();
-    }
+void launch_attn_hd_bwd(const AttnArgs& a, bool dq, hipStream_t s) {
+    attn_for_head_size<32, 8>(a.H, [&](auto hd) {
+        constexpr int HDV = decltype(hd)::value;
+        if (!dq) attn_hd_bwd_go<HDV, true, false>(a, s);       // L > ATTN_SLAB_MAX_L (key pairs): dK / dV per key block, dQ from k_attn_dq
+        else attn_for_bool(attn_pair_hash(a.L), [&](auto pair) { attn_hd_bwd_go<HDV, decltype(pair)::value, true>(a, s); });
+    });
 }
 
 }  // namespace vsl

@@ -1,5 +1,5 @@
 // Attention core of num_heads 1 and 2 (head sizes 128 and 64), forward and backward, every L up to MAX_L.  The kernels of the other head
-// counts (kernels_attn_hd.hip, the 16-wide kernels of 8 heads, k_attn_dq) are untouched; api.hip routes H <= 2 here, L <= 128 included.
+// counts: kernels_attn_hd.hip, kernels_attn_h16.hip, k_attn_dq; kernels_attn.hip routes H <= 2 here, L <= 128 included.
 //   a8 (:174-182)  S = Q K^T / sqrt(hd) + (1 - mask[key]) * -1e30 ; P = softmax ; O = drop(P) V
 // Same contracts as the other head counts: Q / K / V / att are (R, 128) rows with head h at columns h hd .. h hd + hd - 1, LSE is saved per
 // (b, h, q) in natural-log units, and dQ leaves the backward as attn_dq_slabs(L) (R, 128) slabs that k_qkv_bwd adds: one partial per 256-key
@@ -16,32 +16,16 @@
 // The value-side products map row i of 16-row tile j to head dim NT i + j (NT = hd / 16), which makes a lane's operands NT consecutive floats
 // (float4 loads) and its results NT consecutive dims of one row (float4 stores).  Registers: the head-dim accumulators (NT f32x4 = 32 at
 // hd 128, two sets in dK / dV) and the NC-wide score operands (32 each), far below the 128-per-lane wall of the 1024-thread kernels.
-#include "common.hpp"
-#include "launch.hpp"
+#include "attn.hpp"
 
 namespace vsl {
 
-template <int HDV> struct AttnWide {
+template <int HDV> struct AttnWide : AttnHead<HDV> {
     static_assert(HDV == 64 || HDV == 128, "head sizes 64 and 128");
-    static constexpr int NC = HDV / 4;      // head dims a lane contributes to a score tile: k group g owns dims g NC .. g NC + NC - 1
-    static constexpr int NT = HDV / 16;     // 16-row tiles of the head dims; row i of tile j = head dim NT i + j
-    static constexpr int N4 = NT / 4;       // float4 per lane of those NT dims
-    static constexpr int ST = HDV + 4;      // LDS row stride of the wave partials
+    static constexpr int N4 = AttnHead<HDV>::NT / 4;    // float4 per lane of the NT dims of a value-side row (row i of tile j = head dim NT i + j)
+    static constexpr int ST = AttnHead<HDV>::KST;       // LDS row stride of the wave partials
 };
-constexpr float AW_LOG2E = 1.4426950408889634f, AW_LN2 = 0.6931471805599453f;
-template <int HDV> __device__ __forceinline__ constexpr float attn_wide_scale() { return HDV == 128 ? 0.08838834764831845f : 0.125f; }
 
-template <int N> __device__ __forceinline__ void aw_load(const float* p, float* out) {     // N consecutive floats, 16-byte aligned
-#pragma unroll
-    for (int i = 0; i < N; i += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(p + i);
-        out[i] = v.x; out[i + 1] = v.y; out[i + 2] = v.z; out[i + 3] = v.w;
-    }
-}
-template <int N> __device__ __forceinline__ void aw_zero(float* out) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) out[i] = 0.f;
-}
 // the lane's accumulator rows 4 g + r of NT head-dim tiles -> row `dst` of an LDS partial: dims NT (4 g + r) + j
 template <int NT> __device__ __forceinline__ void aw_park(const f32x4* acc, float* dst, int g) {
 #pragma unroll
@@ -50,26 +34,6 @@ template <int NT> __device__ __forceinline__ void aw_park(const f32x4* acc, floa
         for (int f = 0; f < NT / 4; ++f)
             *reinterpret_cast<float4*>(dst + NT * (4 * g + r) + 4 * f) = make_float4(acc[4 * f][r], acc[4 * f + 1][r], acc[4 * f + 2][r], acc[4 * f + 3][r]);
 }
-// dropout decisions of the probabilities as the forward draws them, for one query row and the four keys k4 .. k4 + 3 (k4 a multiple of 4)
-template <bool PAIR> __device__ __forceinline__ void aw_drop4(const Drop& d2, uint32_t qrow, int L, int k4, float* m2) {
-    if (d2.thresh == 0u) { m2[0] = m2[1] = m2[2] = m2[3] = 1.f; return; }
-    if (!PAIR) {
-        const uint32_t ei = qrow * (uint32_t)L + (uint32_t)k4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) m2[r] = drop_keep_scale(d2, ei + r);
-    } else {
-        const uint32_t pi = qrow * (uint32_t)((L + 1) >> 1) + (uint32_t)(k4 >> 1);
-        const uint32_t h0 = drop_hash(pi, d2.seed, d2.key), h1 = drop_hash(pi + 1u, d2.seed, d2.key);
-        m2[0] = h0 >= d2.thresh ? d2.scale : 0.f;
-        m2[1] = drop_hash_odd(h0) >= d2.thresh ? d2.scale : 0.f;
-        m2[2] = h1 >= d2.thresh ? d2.scale : 0.f;
-        m2[3] = drop_hash_odd(h1) >= d2.thresh ? d2.scale : 0.f;
-    }
-}
-__device__ __forceinline__ float aw_bias(const float* mask, size_t rowbase, int key, int L) {     // additive key bias (natural-log units)
-    return key < L ? (1.0f - mask[rowbase + key]) * MASK_VALUE : MASK_VALUE;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // forward.  Workgroup = (16 queries, head, sample); wave w takes the key tiles 16 (4 i + w).  Lane (qi, g) owns query column qi of the
 // transposed score tile S^T = K Q^T (keys 16 t + 4 g + r): the online softmax is lane-local up to two cross-group exchanges, in the log2 domain
@@ -93,9 +57,9 @@ __global__ __launch_bounds__(256) void k_attn_wide_fwd(const float* __restrict__
     const int q = qb * 16 + qi;
     const int Lp = (L + 15) & ~15;
     float qr[NC];                                  // B operand of S^T: Q[q][g NC + c]
-    aw_zero<NC>(qr);
-    if (q < L) aw_load<NC>(Q + (rowbase + q) * D + h * HDV + g * NC, qr);
-    const float c2 = attn_wide_scale<HDV>() * AW_LOG2E;
+    zero_nc<NC>(qr);
+    if (q < L) load_nc<NC>(Q + (rowbase + q) * D + h * HDV + g * NC, qr);
+    const float c2 = C::scale * ATTN_LOG2E;
     const uint32_t qrow = (uint32_t)(((size_t)(b + b_off) * H + h) * L + q);
     float m = -3.0e38f, l = 0.f;
     f32x4 o[NT];
@@ -103,15 +67,15 @@ __global__ __launch_bounds__(256) void k_attn_wide_fwd(const float* __restrict__
     for (int j = 0; j < NT; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kt = 16 * w; kt < Lp; kt += 64) {
         float kr[NC];                              // A operand of S^T: K[kt + qi][g NC + c]
-        aw_zero<NC>(kr);
-        if (kt + qi < L) aw_load<NC>(K + (rowbase + kt + qi) * D + h * HDV + g * NC, kr);
+        zero_nc<NC>(kr);
+        if (kt + qi < L) load_nc<NC>(K + (rowbase + kt + qi) * D + h * HDV + g * NC, kr);
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < NC; ++c) s = __builtin_amdgcn_mfma_f32_16x16x4f32(kr[c], qr[c], s, 0, 0, 0);
         const int k4 = kt + 4 * g;                 // the lane's keys k4 .. k4 + 3
         float x[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) x[r] = fmaf(s[r], c2, aw_bias(mask, rowbase, k4 + r, L) * AW_LOG2E);
+        for (int r = 0; r < 4; ++r) x[r] = fmaf(s[r], c2, attn_key_bias(mask, rowbase, 0, k4 + r, L) * ATTN_LOG2E);
         float tmax = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
         tmax = lane_pair16(tmax, [](float a, float bb) { return fmaxf(a, bb); });
         tmax = lane_pair32(tmax, [](float a, float bb) { return fmaxf(a, bb); });
@@ -126,12 +90,12 @@ __global__ __launch_bounds__(256) void k_attn_wide_fwd(const float* __restrict__
         float pr[4], m2[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) { pr[r] = __builtin_amdgcn_exp2f(x[r] - mn); l += pr[r]; }
-        aw_drop4<PAIR>(d2, qrow, L, k4, m2);
+        attn_drop_q4<PAIR>(d2, qrow, L, k4, m2);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float vv[NT];                          // A operand: V[k4 + r][NT qi + j]
-            aw_zero<NT>(vv);
-            if (k4 + r < L) aw_load<NT>(V + (rowbase + k4 + r) * D + h * HDV + NT * qi, vv);
+            zero_nc<NT>(vv);
+            if (k4 + r < L) load_nc<NT>(V + (rowbase + k4 + r) * D + h * HDV + NT * qi, vv);
             const float pd = pr[r] * m2[r];
 #pragma unroll
             for (int j = 0; j < NT; ++j) o[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[j], pd, o[j], 0, 0, 0);
@@ -160,7 +124,7 @@ __global__ __launch_bounds__(256) void k_attn_wide_fwd(const float* __restrict__
             }
             *reinterpret_cast<float4*>(att + (rowbase + qo) * D + h * HDV + NT * cc + 4 * f) = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
         }
-        if (cc == 0 && lse) lse[((size_t)b * H + h) * L + qo] = M * AW_LN2 + __logf(sum);
+        if (cc == 0 && lse) lse[((size_t)b * H + h) * L + qo] = M * ATTN_LN2 + __logf(sum);
     }
 }
 
@@ -194,13 +158,13 @@ __global__ __launch_bounds__(256) void k_attn_wide_dkv(const float* __restrict__
     const int key = kb * 16 + ki;
     const int Lp = (L + 15) & ~15;
     float kr[NC], vr[NC];                          // B operands of S and dP: K[key][g NC + c], V[key][g NC + c]
-    aw_zero<NC>(kr); aw_zero<NC>(vr);
+    zero_nc<NC>(kr); zero_nc<NC>(vr);
     if (key < L) {
-        aw_load<NC>(K + (rowbase + key) * D + h * HDV + g * NC, kr);
-        aw_load<NC>(V + (rowbase + key) * D + h * HDV + g * NC, vr);
+        load_nc<NC>(K + (rowbase + key) * D + h * HDV + g * NC, kr);
+        load_nc<NC>(V + (rowbase + key) * D + h * HDV + g * NC, vr);
     }
-    const float mbk = aw_bias(mask, rowbase, key, L);
-    const float scale = attn_wide_scale<HDV>();
+    const float mbk = attn_key_bias(mask, rowbase, 0, key, L);
+    const float scale = C::scale;
     const uint32_t hb = (uint32_t)(((size_t)(b + b_off) * H + h) * L);
     f32x4 dk[NT], dv[NT];
 #pragma unroll
@@ -215,14 +179,14 @@ __global__ __launch_bounds__(256) void k_attn_wide_dkv(const float* __restrict__
         const bool act = qt < Lp;
         const int qrow = qt + ki;
         float qa[NC], aa[NC];                      // A operands of S and dP: Q[qt + ki][g NC + c], dA[qt + ki][g NC + c]
-        aw_zero<NC>(qa); aw_zero<NC>(aa);
+        zero_nc<NC>(qa); zero_nc<NC>(aa);
         float dl = 0.f, lq = 0.f;
         if (act && qrow < L) {
             const size_t off = (rowbase + qrow) * D + h * HDV + g * NC;
             float oa[NC];
-            aw_load<NC>(Q + off, qa);
-            aw_load<NC>(dr + off, aa);
-            aw_load<NC>(att + off, oa);
+            load_nc<NC>(Q + off, qa);
+            load_nc<NC>(dr + off, aa);
+            load_nc<NC>(att + off, oa);
             if (d3.thresh) {                       // r = drop3(att) + x  (:183-184): element-keyed
 #pragma unroll
                 for (int c = 0; c < NC; ++c) aa[c] *= drop_keep_scale(d3, (uint32_t)(off + c));
@@ -253,9 +217,9 @@ __global__ __launch_bounds__(256) void k_attn_wide_dkv(const float* __restrict__
             float m2v[4] = {1.f, 1.f, 1.f, 1.f};
             if (!PAIR) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) m2v[r] = drop_mul(d2, (hb + (uint32_t)(qt + 4 * g + r)) * (uint32_t)L + (uint32_t)key);
+                for (int r = 0; r < 4; ++r) m2v[r] = drop_mul(d2, attn_drop_elem(hb + (uint32_t)(qt + 4 * g + r), L, key));
             } else if (d2.thresh != 0u) {          // keys 2 j, 2 j + 1 share a hash: this lane hashes two of the four queries, its neighbour the other two
-                const uint32_t Lh = (uint32_t)((L + 1) >> 1), kp = (uint32_t)(key >> 1);
+                const uint32_t Lh = attn_drop_pair_stride(L), kp = (uint32_t)(key >> 1);
                 const int odd = ki & 1;
                 uint32_t hm[2], hp[2];
 #pragma unroll
@@ -264,10 +228,7 @@ __global__ __launch_bounds__(256) void k_attn_wide_dkv(const float* __restrict__
                     hp[jj] = __float_as_uint(lane_xor1(__uint_as_float(hm[jj])));
                 }
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const uint32_t hr = (r >> 1) == odd ? hm[r & 1] : hp[r & 1];
-                    m2v[r] = (odd ? drop_hash_odd(hr) : hr) >= d2.thresh ? d2.scale : 0.f;
-                }
+                for (int r = 0; r < 4; ++r) m2v[r] = attn_drop_pair_mul(d2, odd, (r >> 1) == odd ? hm[r & 1] : hp[r & 1]);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -276,8 +237,8 @@ __global__ __launch_bounds__(256) void k_attn_wide_dkv(const float* __restrict__
                 const float pd = p * m2v[r];
                 const float ds = p * (dp[r] * m2v[r] - Dw[ql]) * scale;
                 float av[NT], qv[NT];
-                aw_load<NT>(&Aw[ql * ST + NT * ki], av);
-                aw_load<NT>(&Qw[ql * ST + NT * ki], qv);
+                load_nc<NT>(&Aw[ql * ST + NT * ki], av);
+                load_nc<NT>(&Qw[ql * ST + NT * ki], qv);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     dv[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], pd, dv[j], 0, 0, 0);
@@ -335,16 +296,16 @@ __global__ __launch_bounds__(256) void k_attn_wide_dq(const float* __restrict__ 
     const int q = qb * 16 + qi;
     const int Lp = (L + 15) & ~15;
     const int klo = sp * span, khi = min(klo + span, Lp);
-    const float scale = attn_wide_scale<HDV>();
+    const float scale = C::scale;
     float qa[NC], aa[NC];                          // B operands of S^T and dP^T: Q[q][g NC + c], dA[q][g NC + c]
-    aw_zero<NC>(qa); aw_zero<NC>(aa);
+    zero_nc<NC>(qa); zero_nc<NC>(aa);
     float dl = 0.f, lq = 0.f;
     if (q < L) {
         const size_t off = (rowbase + q) * D + h * HDV + g * NC;
         float oa[NC];
-        aw_load<NC>(Q + off, qa);
-        aw_load<NC>(dr + off, aa);
-        aw_load<NC>(att + off, oa);
+        load_nc<NC>(Q + off, qa);
+        load_nc<NC>(dr + off, aa);
+        load_nc<NC>(att + off, oa);
         if (d3.thresh) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) aa[c] *= drop_keep_scale(d3, (uint32_t)(off + c));
@@ -361,10 +322,10 @@ __global__ __launch_bounds__(256) void k_attn_wide_dq(const float* __restrict__ 
     for (int j = 0; j < NT; ++j) dq[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kt = klo + 16 * w; kt < khi; kt += 64) {
         float ka[NC], va[NC];                      // A operands: K[kt + qi][g NC + c], V[kt + qi][g NC + c]
-        aw_zero<NC>(ka); aw_zero<NC>(va);
+        zero_nc<NC>(ka); zero_nc<NC>(va);
         if (kt + qi < L) {
-            aw_load<NC>(K + (rowbase + kt + qi) * D + h * HDV + g * NC, ka);
-            aw_load<NC>(V + (rowbase + kt + qi) * D + h * HDV + g * NC, va);
+            load_nc<NC>(K + (rowbase + kt + qi) * D + h * HDV + g * NC, ka);
+            load_nc<NC>(V + (rowbase + kt + qi) * D + h * HDV + g * NC, va);
         }
         f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -374,14 +335,14 @@ __global__ __launch_bounds__(256) void k_attn_wide_dq(const float* __restrict__ 
         }
         const int k4 = kt + 4 * g;                 // register r: key k4 + r, query qi
         float m2[4];
-        aw_drop4<PAIR>(d2, qrow, L, k4, m2);
+        attn_drop_q4<PAIR>(d2, qrow, L, k4, m2);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float p = __expf(sc[r] * scale + aw_bias(mask, rowbase, k4 + r, L) - lq);
+            const float p = __expf(sc[r] * scale + attn_key_bias(mask, rowbase, 0, k4 + r, L) - lq);
             const float ds = p * (dp[r] * m2[r] - dl) * scale;
             float kd[NT];                          // A operand: K[k4 + r][NT qi + j]
-            aw_zero<NT>(kd);
-            if (k4 + r < L) aw_load<NT>(K + (rowbase + k4 + r) * D + h * HDV + NT * qi, kd);
+            zero_nc<NT>(kd);
+            if (k4 + r < L) load_nc<NT>(K + (rowbase + k4 + r) * D + h * HDV + NT * qi, kd);
 #pragma unroll
             for (int j = 0; j < NT; ++j) dq[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(kd[j], ds, dq[j], 0, 0, 0);
         }
@@ -407,51 +368,24 @@ __global__ __launch_bounds__(256) void k_attn_wide_dq(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------
-template <int HDV, bool PAIR> static void attn_wide_fwd_go(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse,
-                                                           int B, int L, int H, int b_off, Drop d2, hipStream_t s) {
-    VSL_LAUNCH((k_attn_wide_fwd<HDV, PAIR>), dim3((L + 15) / 16, H, B), dim3(256), 0, s, Q, K, V, mask, att, lse, L, H, b_off, d2);
+void launch_attn_wide_fwd(const AttnArgs& a, hipStream_t s) {
+    attn_for_head_size<128, 64>(a.H, [&](auto hd) { attn_for_bool(attn_pair_hash(a.L), [&](auto pair) {
+        VSL_LAUNCH((k_attn_wide_fwd<decltype(hd)::value, decltype(pair)::value>), dim3((a.L + 15) / 16, a.H, a.B), dim3(256), 0, s, a.Q, a.K, a.V, a.mask,
+                   a.att, a.lse, a.L, a.H, a.b_off, a.d2);
+    }); });
 }
-void launch_attn_wide_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
-                          int L, int H, int b_off, Drop d2, hipStream_t s) {
-    const bool pair = L > 256;
-    if (H == 1) {
-        if (pair) attn_wide_fwd_go<128, true>(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
-        else attn_wide_fwd_go<128, false>(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
-    } else if (H == 2) {
-        if (pair) attn_wide_fwd_go<64, true>(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
-        else attn_wide_fwd_go<64, false>(Q, K, V, mask, att, lse, B, L, H, b_off, d2, s);
-    } else {
-        fprintf(stderr, "launch_attn_wide_fwd: num_heads=%d has no attention kernel\n", H);
-        abort();
-    }
-}
-
-template <int HDV, bool PAIR> static void attn_wide_bwd_go(const float* Q, const float* K, const float* V, const float* att, const float* dr,
-                                                           const float* lse, const float* mask, float* dQ, float* dK, float* dV, int B, int L,
-                                                           int H, int b_off, Drop d2, Drop d3, hipStream_t s, bool query_major) {
-    static size_t ok = 0;
-    ensure_dynamic_lds((const void*)k_attn_wide_dkv<HDV, PAIR>, attn_wide_dkv_lds<HDV>(), ok, "k_attn_wide_dkv");
-    VSL_LAUNCH((k_attn_wide_dkv<HDV, PAIR>), dim3((L + 15) / 16, H, B), dim3(256), attn_wide_dkv_lds<HDV>(), s, Q, K, V, att, dr, lse, mask, dK, dV,
-               L, H, b_off, d2, d3);
-    const int Lp = (L + 15) & ~15;
-    const int spans = query_major ? 1 : attn_bwd_dq_slabs(L), span = query_major ? Lp : 256;
-    VSL_LAUNCH((k_attn_wide_dq<HDV, PAIR>), dim3((L + 15) / 16 * spans, H, B), dim3(256), 0, s, Q, K, V, att, dr, lse, mask, dQ, L, H, b_off, span,
-               (size_t)B * L * D, d2, d3);
-}
-void launch_attn_wide_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
-                          const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                          Drop d3, hipStream_t s, bool query_major) {
-    const bool pair = L > 256;
-    if (H == 1) {
-        if (pair) attn_wide_bwd_go<128, true>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, query_major);
-        else attn_wide_bwd_go<128, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, query_major);
-    } else if (H == 2) {
-        if (pair) attn_wide_bwd_go<64, true>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, query_major);
-        else attn_wide_bwd_go<64, false>(Q, K, V, att, dr, lse, mask, dQ, dK, dV, B, L, H, b_off, d2, d3, s, query_major);
-    } else {
-        fprintf(stderr, "launch_attn_wide_bwd: num_heads=%d has no attention kernel\n", H);
-        abort();
-    }
+void launch_attn_wide_bwd(const AttnArgs& a, bool query_major, hipStream_t s) {
+    attn_for_head_size<128, 64>(a.H, [&](auto hd) { attn_for_bool(attn_pair_hash(a.L), [&](auto pair) {
+        constexpr int HDV = decltype(hd)::value;
+        constexpr bool PAIR = decltype(pair)::value;
+        dynamic_lds_optin<k_attn_wide_dkv<HDV, PAIR>>(attn_wide_dkv_lds<HDV>(), "k_attn_wide_dkv");
+        VSL_LAUNCH((k_attn_wide_dkv<HDV, PAIR>), dim3((a.L + 15) / 16, a.H, a.B), dim3(256), attn_wide_dkv_lds<HDV>(), s, a.Q, a.K, a.V, a.att, a.dr, a.lse,
+                   a.mask, a.dK, a.dV, a.L, a.H, a.b_off, a.d2, a.d3);
+        const int Lp = (a.L + 15) & ~15;
+        const int spans = query_major ? 1 : attn_bwd_dq_slabs(a.L), span = query_major ? Lp : 256;
+        VSL_LAUNCH((k_attn_wide_dq<HDV, PAIR>), dim3((a.L + 15) / 16 * spans, a.H, a.B), dim3(256), 0, s, a.Q, a.K, a.V, a.att, a.dr, a.lse, a.mask, a.dQ,
+                   a.L, a.H, a.b_off, span, (size_t)a.B * a.L * D, a.d2, a.d3);
+    }); });
 }
 
 }  // namespace vsl

@@ -16,45 +16,10 @@
 #include "common.hpp"
 #include "launch.hpp"
 #include "tile_bodies.hpp"
+#include "stamps.hpp"
 #include <type_traits>
 
 namespace vsl {
-
-__device__ long long g_stamps_e[32];
-__device__ int g_dbg_on_e = 0;
-#ifdef VSL_STAMPS       // see kernels_bwd.hip: stamps are a separate build
-#define ESTAMP(k) do { if (g_dbg_on_e && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_stamps_e[k] = clock64(); } while (0)
-#else
-#define ESTAMP(k) do { } while (0)
-#endif
-static int edbg_on() {
-#ifndef VSL_STAMPS
-    return 0;
-#endif
-    static int inited = 0, on = 0;
-    if (!inited) { inited = 1; on = getenv("VSL_DEBUG_TIMING") != nullptr; if (on) { int one = 1; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_on_e), &one, sizeof one); } }
-    return on;
-}
-static void edbg_report(const char* name, int nst, hipStream_t s, int& left) {
-    if (left <= 0) return;
-    long long h[32];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamps_e), sizeof h);
-    fprintf(stderr, "[%s cycles]", name);
-    for (int i = 1; i < nst; ++i) fprintf(stderr, " %lld", h[i] - h[i - 1]);
-    fprintf(stderr, " | total %lld\n", h[nst - 1] - h[0]);
-    --left;
-}
-
-static void edbg_report2(const char* name, int i0, int i1, hipStream_t s, int& left) {
-    if (left <= 0) return;
-    long long h[32];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamps_e), sizeof h);
-    fprintf(stderr, "[%s cycles] (from stamp 1: %lld)", name, h[i0] - h[1]);
-    for (int i = i0 + 1; i < i1; ++i) fprintf(stderr, " %lld", h[i] - h[i - 1]);
-    fprintf(stderr, "\n");
-}
 
 constexpr int CB_T = 512;                       // threads per workgroup (8 waves, 2 per SIMD)
 constexpr int CB_HALO = 4 * HALO;               // 12 rows each side
@@ -281,7 +246,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int R = a.R, L = a.L;
     const int r0 = SH ? blockIdx.x * TILE_M : blockIdx.x * L, rw0 = r0 - HL;      // global row of window row 0
-    ESTAMP(0);
+    STAMP(0);
     // ---- window rows rw0 .. rw0 + 55 (+ positional rows, :202): every load first
     float4 xv[4], pv[4];
 #pragma unroll
@@ -340,7 +305,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
     const bool plain = interior || one_owner;
     auto row_ok = [&](int wr) { return SH ? (full || rw0 + wr < R) : wr < L; };     // may window row wr (an owner row) be stored?
     __syncthreads();
-    ESTAMP(1);
+    STAMP(1);
     const Drop nodrop{0u, 0u, 1.f};
     const int col = 16 * w + (lane & 15), g4 = 4 * (lane >> 4);
 
@@ -354,7 +319,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
         if (one_owner) ln_rows512(Xs + in0 * LDP, VU + in0 * LDP, nin, P, P + 128, nodrop, 0, klo - in0, khi - in0);
         else ln_rows512(Xs + in0 * LDP, VU + in0 * LDP, nin, P, P + 128, nodrop, 0);
         __syncthreads();
-        if (l == 0) ESTAMP(8);
+        if (l == 0) STAMP(8);
         // ---- depthwise conv k = 7 along the sequence: thread = (channel, quarter of the row range), window in registers
         {
             const int c = tid & 127, seg = tid >> 7;
@@ -399,7 +364,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
             }
         }
         __syncthreads();
-        if (l == 0) ESTAMP(9);
+        if (l == 0) STAMP(9);
         // ---- pointwise GEMM + bias + ReLU (+ dropout) + residual, in place on the residual stream
         f32x4 acc[1][NRB];
 #pragma unroll
@@ -412,7 +377,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
             for (int k = 0; k < DWK; ++k) wkc[k] = a.dw_w[l < 3 ? l + 1 : 3][(tid & 127) * DWK + k];
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (l == 0) ESTAMP(10);
+        if (l == 0) STAMP(10);
         const float bv = P[256 + col];
         uint16_t* mk = reinterpret_cast<uint16_t*>(a.relu_mask[l]);
         const int mybit = 1 << (lane & 15);
@@ -452,9 +417,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
                 if (j < 4 && o >= HL && o < HL + TILE_M && row_ok(o)) mk[(size_t)(rw0 + o) * 8 + w] = (uint16_t)wv;
             }
         }
-        if (l == 0) ESTAMP(11);
+        if (l == 0) STAMP(11);
         __syncthreads();
-        if (l == 0) ESTAMP(12);
+        if (l == 0) STAMP(12);
         // owner rows of the layer output -> memory (16-byte stores); without the saves only the block output y3 leaves (the attention block's residual input)
         if constexpr (SAVE || l == 3)
 #pragma unroll
@@ -466,13 +431,13 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
         }
     };
     layer(std::integral_constant<int, 0>(), b3A, [&] { b3_load(b3B, a.W3[1], D, D, 16 * w); });
-    ESTAMP(2);
+    STAMP(2);
     layer(std::integral_constant<int, 1>(), b3B, [&] { b3_load(b3A, a.W3[2], D, D, 16 * w); });
-    ESTAMP(3);
+    STAMP(3);
     layer(std::integral_constant<int, 2>(), b3A, [&] { b3_load(b3B, a.W3[3], D, D, 16 * w); });
-    ESTAMP(4);
+    STAMP(4);
     layer(std::integral_constant<int, 3>(), b3B, [&] { b3_load(b3A, a.Wqkv3, D, 3 * D, 16 * w); });
-    ESTAMP(5);
+    STAMP(5);
     // ---- a8, first half (:168-173) on the owner rows: h1 = drop(LN1(y3)) ; [q | k | v] = h1 W^T + b  (wave w = head w)
     {
         const float* Pq = Ps + 4 * CB_PS;
@@ -501,7 +466,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd(CbFwdArgs a) {
         proj(b3B, a.qf.k, 1);
         proj(b3A, a.qf.v, 2);
     }
-    ESTAMP(6);
+    STAMP(6);
 }
 constexpr size_t cb_fwd_lds_split(int sh) {
     return (size_t)(((TILE_M + 8 * sh) + (sh ? TILE_M + 8 * sh + 12 : TILE_M + 2 * HALO)) * LDP + 3 * (TILE_M + 8 * sh) * CB_LDB / 2 + 4 * CB_PS + 640) * sizeof(float);
@@ -562,7 +527,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
     const int L = a.L;
     const int r0 = blockIdx.x * TILE_M, rw0 = r0 - HL;
     const uint32_t rbytes = (uint32_t)a.R * (D * 4);           // bytes of an (R, 128) fp32 tensor
-    ESTAMP(0);
+    STAMP(0);
     constexpr int NQ = (NW * 32 + NT - 1) / NT;                // float4 items per thread of the window
     float4 xv[NQ], pv[NQ];
     const int s_own = r0 / L;
@@ -619,7 +584,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
     }
     f32x2 wk2[DWK];                                          // depthwise taps of the thread's channel pair (2 lane, 2 lane + 1)
     __syncthreads();
-    ESTAMP(1);
+    STAMP(1);
     const int col = 16 * cb + (lane & 15), g4 = 4 * (lane >> 4);
     auto grp_sum = [](float v) { return grp8_sum(v); };       // sum over the LPR lanes of a row
     constexpr int TA[6] = {1, 0, 2, 0, 1, 0}, TB[6] = {1, 2, 0, 1, 0, 0};       // (a term, b term): mm, hl, lh, hm, mh, hh -- small terms first
@@ -694,7 +659,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
             preB(std::integral_constant<int, 1>());
         }
         __syncthreads();
-        if (l == 0) ESTAMP(8);
+        if (l == 0) STAMP(8);
         // ---- depthwise conv k = 7: thread = (channel pair, row segment = wave); window of QS + 6 rows in registers.  A wave whose segment
         // lies beyond the layer's rows recomputes segment 0 and discards it (the same instruction stream in every wave)
         {
@@ -726,7 +691,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
             }
         }
         __syncthreads();
-        if (l == 0) ESTAMP(9);
+        if (l == 0) STAMP(9);
         // ---- pointwise GEMM: this wave = 16 output columns x every row block, one block at a time, the epilogue of the previous block between
         // the MFMAs.  What the stamps and knock-out builds said on the way here (profiles/r05_notes.md): one accumulator chain per 16 x 16 tile
         // already runs the matrix pipe at its full rate (tools/ubench/mfma_rate.hip), the two waves of a SIMD take turns on it (the older one
@@ -806,9 +771,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
         preB(std::integral_constant<int, 10>());
         preB(std::integral_constant<int, 11>());
         static_for<0, 4>([&](auto RRc) { epi(std::integral_constant<int, NRB - 1>(), RRc); });
-        if (l == 0) ESTAMP(10);
+        if (l == 0) STAMP(10);
         __syncthreads();
-        if (l == 0) ESTAMP(11);
+        if (l == 0) STAMP(11);
         // ReLU decisions of the owner rows: one 16-byte store per row (the (R, 4) uint32 words)
         if constexpr (SAVE) {
             const u32x4_t mv = *reinterpret_cast<const u32x4_t*>(MB + (HL + (tid & 31)) * C2_MBW);
@@ -816,13 +781,13 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
         }
     };
     layer(std::integral_constant<int, 0>(), b3A, b3B, a.W3[1], std::integral_constant<int, D>());
-    ESTAMP(2);
+    STAMP(2);
     layer(std::integral_constant<int, 1>(), b3B, b3A, a.W3[2], std::integral_constant<int, D>());
-    ESTAMP(3);
+    STAMP(3);
     layer(std::integral_constant<int, 2>(), b3A, b3B, a.W3[3], std::integral_constant<int, D>());
-    ESTAMP(4);
+    STAMP(4);
     layer(std::integral_constant<int, 3>(), b3B, b3A, a.Wqkv3, std::integral_constant<int, 3 * D>());
-    ESTAMP(5);
+    STAMP(5);
     // ---- a8, first half (:168-173) on the owner rows: y3 -> memory ; h1 = drop(LN1(y3)) ; [q | k | v] = h1 W^T + b  (column block cb = head cb)
     {
         const float* Pq = Ps + 4 * CB_PS;
@@ -917,7 +882,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_fwd2(CbFwdArgs a) {
         proj(b3B, a.qf.k, 1);
         proj(b3A, a.qf.v, 2);
     }
-    ESTAMP(6);
+    STAMP(6);
 }
 constexpr size_t cb_fwd2_lds() {
     return (size_t)((C2_XR + C2_VUR) * LDP + 3 * (TILE_M + 24) * CB_LDB / 2 + 4 * CB_PS + 640 + C2_XR * C2_MBW / 2 + 4 * D * DWK) * sizeof(float);
@@ -952,7 +917,7 @@ void launch_convblock_fwd(const CbFwdArgs& a, hipStream_t s) {
     if (a.R % TILE_M == 0 && a.L % TILE_M == 0) launch_cbf2(a, a.R / TILE_M, s);     // whole tiles inside one sample each
     else launch_cbf<3>(a, (a.R + TILE_M - 1) / TILE_M, s);
     static int left = 6;
-    if (edbg_on() && a.R > 4096) { int l2 = left, l3 = left; edbg_report("convblock_fwd: load | L0 | L1 | L2 | L3 | qkv", 7, s, left); edbg_report2("  L0: LN | dw | gemm | epilogue | barrier", 8, 13, s, l2); edbg_report2("  L0 gemm: (stamp 14 = group 0 done) group 1", 14, 16, s, l3); }
+    if (stamps::enabled() && a.R > 4096) { int l2 = left, l3 = left; stamps::report("convblock_fwd: load | L0 | L1 | L2 | L3 | qkv", 7, s, left); stamps::report_range("  L0: LN | dw | gemm | epilogue | barrier", 8, 13, s, l2); stamps::report_range("  L0 gemm: (stamp 14 = group 0 done) group 1", 14, 16, s, l3); }
 }
 
 // =========================================================================================================
@@ -1006,7 +971,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
     const int r8 = tid >> 3, sub = tid & 7;
     // column layout of phase C
     const int cc = tid >> 2, seg = tid & 3;
-    ESTAMP(0);
+    STAMP(0);
     float4 xv[4];
     uint32_t mw[4];
     // Global traffic as in k_convblock_fwd2: raw buffer instructions that EVERY wave executes, rows that do not exist / are not to be stored get
@@ -1064,9 +1029,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) g0[q] = buf_load4(rv, rowoff + 128 * q);
-        ESTAMP(18);
+        STAMP(18);
         __syncthreads();
-        ESTAMP(19);
+        STAMP(19);
         f32x4 acc[1][NRQ];
 #pragma unroll
         for (int rb = 0; rb < NRQ; ++rb) acc[0][rb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1075,9 +1040,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
         b3_load(b3B, qk.WT3 + 2 * wchunk, 3 * D, D, 16 * w);
         __builtin_amdgcn_sched_barrier(0);
         put(P2, g1);
-        ESTAMP(20);
+        STAMP(20);
         __syncthreads();
-        ESTAMP(21);
+        STAMP(21);
         gemm16s<NRQ>(P2, ZPS, b3A, acc);
         __builtin_amdgcn_sched_barrier(0);
         b3_load(b3A, a.WT3[3], D, D, 16 * w);                     // layer 3's weight slice
@@ -1088,9 +1053,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) { xq[q] = buf_load4(rx, rowoff + 128 * q); rs[q] = buf_load4(rdr, rowoff + 128 * q); }
         }
-        ESTAMP(22);
+        STAMP(22);
         __syncthreads();
-        ESTAMP(23);
+        STAMP(23);
         gemm16s<NRQ>(Pz, ZPS, b3B, acc);
         __builtin_amdgcn_sched_barrier(0);
         fetch_layer(3);
@@ -1104,9 +1069,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
                     DU[row * LDP + col] = acc[0][rb][rr] * drop_mul(d1, (uint32_t)((rw0 + row) * D + col));
                 }
         }
-        ESTAMP(24);
+        STAMP(24);
         __syncthreads();
-        ESTAMP(25);
+        STAMP(25);
         {   // LayerNorm-1 backward per window row (8 lanes per row): dy = dr + rstd (g - mean(g) - xhat mean(g xhat)), g = Ts * gamma
             const int rc = r8 < NW ? r8 : 0;
             const float* tr = DU + rc * LDP + sub * 4;
@@ -1146,9 +1111,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
                     make_float4(ts[j].x * xq[j].x, ts[j].y * xq[j].y, ts[j].z * xq[j].z, ts[j].w * xq[j].w);
             }
         }
-        ESTAMP(26);
+        STAMP(26);
         __syncthreads();
-        ESTAMP(27);
+        STAMP(27);
         {   // column sums over the 32 owner rows -> this tile's partial slabs of LN1's gamma / beta
             const int c = tid & 127;
             const float* src = tid < 128 ? Xh + c : DU + HL * LDP + c;
@@ -1179,7 +1144,7 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
     if (tid < 64) {
         VF[tid] = (one_owner ? (tid >= klo && tid < khi) : row_in(tid)) ? 1.f : 0.f;
     }
-    ESTAMP(1);
+    STAMP(1);
 
     auto layer = [&](auto LC, auto& cur, auto& nxt) {
         constexpr int l = decltype(LC)::value;
@@ -1247,9 +1212,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
         }
         float* GBl = GB + (l & 1) * D;
         if (tid < D) GBl[tid] = gnext;
-        if (l == 3) ESTAMP(8);
+        if (l == 3) STAMP(8);
         __syncthreads();
-        if (l == 3) ESTAMP(9);
+        if (l == 3) STAMP(9);
         preB(std::integral_constant<int, 4>());
         // ---- x_l -> xhat in place, rstd per row (8 lanes per row)
         {
@@ -1274,14 +1239,14 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
             }
         }
         preF(std::integral_constant<int, 0>());
-        if (l == 3) ESTAMP(10);
+        if (l == 3) STAMP(10);
         preB(std::integral_constant<int, 5>());
         // ---- B: du = dz Wp
         f32x4 acc[1][NRB];
 #pragma unroll
         for (int rb = 0; rb < NRB; ++rb) acc[0][rb] = f32x4{0.f, 0.f, 0.f, 0.f};
         gemm16s<NRB>(Pz + ra * CB_LDB, ZPS, cur, acc);
-        if (l == 3) ESTAMP(11);
+        if (l == 3) STAMP(11);
         preF(std::integral_constant<int, 1>());
 #pragma unroll
         for (int rb = 0; rb < NRB; ++rb)
@@ -1291,9 +1256,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
                 DU[row * LDP + col] = acc[0][rb][rr] * VF[min(row, 63)];    // rows of another sample: zero padding of this one's conv
             }
         preB(std::integral_constant<int, 6>());
-        if (l == 3) ESTAMP(12);
+        if (l == 3) STAMP(12);
         __syncthreads();
-        if (l == 3) ESTAMP(13);
+        if (l == 3) STAMP(13);
         // ---- C: dv = depthwise^T(du) ; partial sums over the owner rows
         float dvo[8], dvh[HQ > 0 ? HQ : 1];
         float gw[DWK], slb = 0.f, slg = 0.f;
@@ -1403,9 +1368,9 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
             gnext = a.ln_g[lm][tid & (D - 1)];
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (l == 3) ESTAMP(14);
+        if (l == 3) STAMP(14);
         __syncthreads();
-        if (l == 3) ESTAMP(15);
+        if (l == 3) STAMP(15);
         // ---- D: dy <- dy + LN^T(dv)   (8 lanes per row)
         {
             const bool inD = r8 >= ra + SH && r8 < ra + SH + nD;
@@ -1442,19 +1407,19 @@ __global__ __launch_bounds__(CB_T, 2) void k_convblock_bwd(CbBwdArgs a) {
         }
         // no barrier: phase A of the next layer touches only what this thread itself read and wrote above -- except the dz planes of the
         // split path, which lie over the dv rows other threads are still reading
-        if (l == 3) ESTAMP(16);
+        if (l == 3) STAMP(16);
         if (l > 0) __syncthreads();
-        if (l == 3) ESTAMP(17);
+        if (l == 3) STAMP(17);
     };
     __syncthreads();
     layer(std::integral_constant<int, 3>(), b3A, b3B);
-    ESTAMP(2);
+    STAMP(2);
     layer(std::integral_constant<int, 2>(), b3B, b3A);
-    ESTAMP(3);
+    STAMP(3);
     layer(std::integral_constant<int, 1>(), b3A, b3B);
-    ESTAMP(4);
+    STAMP(4);
     layer(std::integral_constant<int, 0>(), b3B, b3A);
-    ESTAMP(5);
+    STAMP(5);
     if constexpr (TAIL != 0) {
         static_assert(TAIL == 3 ? SH == 0 : (FULL && SH == 3), "tails 1, 2 ride on whole tiles, tail 3 on sample tiles");
         __syncthreads();                                   // dx0's owner rows are in DY; every other LDS region is free
@@ -1495,7 +1460,7 @@ void launch_convblock_bwd(const CbBwdArgs& a, hipStream_t s) {
         else launch_cbb<3, true>(a, a.R / TILE_M, s);
     } else launch_cbb<3, false>(a, (a.R + TILE_M - 1) / TILE_M, s);
     static int left = 6;
-    if (edbg_on() && a.R > 4096) { int l2 = left; edbg_report("convblock_bwd: load | L3 | L2 | L1 | L0", 6, s, left); edbg_report2("  L3: (A) sync | xhat | gemm | DU | sync | C | sync | D | sync", 8, 18, s, l2); if (a.qkv) { int l3 = l2 + 1; edbg_report2("  qkv: (from 0: load+split c0) | sync | gemm c0 + split c1 | sync | gemm c1 + split c2 | sync | gemm c2 + Ts | sync | LN bwd | sync | (to stamp 1: sums + rest)", 18, 28, s, l3); } }
+    if (stamps::enabled() && a.R > 4096) { int l2 = left; stamps::report("convblock_bwd: load | L3 | L2 | L1 | L0", 6, s, left); stamps::report_range("  L3: (A) sync | xhat | gemm | DU | sync | C | sync | D | sync", 8, 18, s, l2); if (a.qkv) { int l3 = l2 + 1; stamps::report_range("  qkv: (from 0: load+split c0) | sync | gemm c0 + split c1 | sync | gemm c1 + split c2 | sync | gemm c2 + Ts | sync | LN bwd | sync | (to stamp 1: sums + rest)", 18, 28, s, l3); } }
 }
 // partial slabs the backward writes per parameter: one per workgroup
 int convblock_slabs(int R, int L) { return L <= TILE_M ? R / L : (R + TILE_M - 1) / TILE_M; }
@@ -1526,7 +1491,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
     const int q0 = bxs * TILE_M;
     const size_t rowbase = (size_t)b * L;
     const int qi = lane & 15, g = lane >> 4;
-    ESTAMP(0);
+    STAMP(0);
     const int Lp = (L + 15) & ~15;
     for (int k = tid; k < Lp; k += NT) Mb[k] = k < L ? (1.0f - a.mask[rowbase + k]) * MASK_VALUE : MASK_VALUE;
     // per-wave (= per-head) uniform bases + 32-bit lane offsets, so a fragment load is one saddr + voffset instruction
@@ -1572,7 +1537,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
     if (tid < 384) Pn[tid] = tid < 128 ? a.ln_g[tid] : tid < 256 ? a.ln_b[tid - 128] : a.bo[tid - 256];
     __syncthreads();
     cur.mb = *reinterpret_cast<const float4*>(&Mb[4 * g]);
-    ESTAMP(1);
+    STAMP(1);
     for (int kt = 0; kt < Lp; kt += 16) {
         if (kt + 16 < Lp) { load_kt(kt + 16, nxt); nxt.mb = *reinterpret_cast<const float4*>(&Mb[kt + 16 + 4 * g]); }
         __builtin_amdgcn_sched_barrier(0);
@@ -1616,7 +1581,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
             for (int qb = 0; qb < QB; ++qb) o[qb] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.vv[r], p[qb][r], o[qb], 0, 0, 0);
         cur = nxt;
     }
-    ESTAMP(2);
+    STAMP(2);
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
         const float lt = kgroup_sum(l[qb]);
@@ -1630,7 +1595,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
         }
     }
     __syncthreads();
-    ESTAMP(3);
+    STAMP(3);
     // ---- r = drop(att) + x (:183-184)
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -1646,10 +1611,10 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
         *reinterpret_cast<float4*>(&Rs[rr * LDP + c]) = v;
     }
     __syncthreads();
-    ESTAMP(4);
+    STAMP(4);
     ln_rows512(Rs, Hs, TILE_M, Pn, Pn + 128, a.d4, (int)rowbase + q0);
     __syncthreads();
-    ESTAMP(5);
+    STAMP(5);
     if (SAVE && a.h2_out) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -1676,7 +1641,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
                 a.y_out[(size_t)r * D + col] = yv[rb][rr];
             }
         }
-    ESTAMP(6);
+    STAMP(6);
     if constexpr (HT) {
         static_assert(QB == 1, "the span heads ride on the 16-wave instantiation");
         __syncthreads();                                   // every wave is through with Hs (the GEMM's A operand)
@@ -1690,7 +1655,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
     }
 }
 void launch_attn_block_fwd(const AttnBlockArgs& a, int B, hipStream_t s) {
-    // L <= 128 only: 16 waves (wave = head x 16-query block).  Longer sequences take k_attn_fwd + k_attn_out_fwd (kernels_fwd.hip); the 8-wave
+    // L <= 128 only: 16 waves (wave = head x 16-query block).  Longer sequences take k_attn_fwd (kernels_attn_h16.hip) + k_attn_out_fwd (kernels_fwd.hip); the 8-wave
     // instantiation that served 128 < L <= 256 until round 6 is gone (-0.6 % on configs[2] / [3] without it: profiles/r06_notes.md section 9).
     const dim3 grid((a.L + TILE_M - 1) / TILE_M, B);
     const size_t shm = (size_t)((a.L + 15) & ~15) * sizeof(float);
@@ -1708,7 +1673,7 @@ void launch_attn_block_fwd(const AttnBlockArgs& a, int B, hipStream_t s) {
     } else if (a.nosave) VSL_LAUNCH((k_attn_block_fwd<1, false, false>), grid, dim3(1024), shm, s, a);
     else VSL_LAUNCH(k_attn_block_fwd<1>, grid, dim3(1024), shm, s, a);
     static int left = 3;
-    if (edbg_on() && B > 16) edbg_report("attn_block_fwd", 7, s, left);
+    if (stamps::enabled() && B > 16) stamps::report("attn_block_fwd", 7, s, left);
 }
 
 }  // namespace vsl

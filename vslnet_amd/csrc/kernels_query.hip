@@ -28,32 +28,9 @@
 // register file of its CU (215 / 255 VGPRs x 2 waves per SIMD), so NOTHING co-resides with it, whatever its LDS footprint.
 #include "common.hpp"
 #include "launch.hpp"
+#include "stamps.hpp"
 
 namespace vsl {
-
-__device__ long long g_stamps_q[40];
-__device__ int g_dbg_on_q = 0;
-#ifdef VSL_STAMPS       // phase stamps of workgroup 0: a separate build (vslnet_amd/build.py --stamps), see kernels_bwd.hip
-#define QSTAMP(k) do { if (g_dbg_on_q && blockIdx.x == 0 && threadIdx.x == 0) g_stamps_q[k] = clock64(); } while (0)
-#else
-#define QSTAMP(k) do { } while (0)
-#endif
-static int qdbg_on() {
-#ifndef VSL_STAMPS
-    return 0;
-#endif
-    static int inited = 0, on = 0;
-    if (!inited) { inited = 1; on = getenv("VSL_DEBUG_TIMING") != nullptr; if (on) { int one = 1; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_on_q), &one, sizeof one); } }
-    return on;
-}
-static void qdbg_report(const char* name, int i0, int i1, hipStream_t s) {
-    long long h[40];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamps_q), sizeof h);
-    fprintf(stderr, "[%s cycles]", name);
-    for (int i = i0 + 1; i < i1; ++i) fprintf(stderr, " %lld", h[i] - h[i - 1]);
-    fprintf(stderr, " | total %lld\n", h[i1 - 1] - h[i0]);
-}
 
 constexpr int QT = 256;                         // threads per workgroup: 4 waves, one per SIMD
 constexpr int QROWS = 32;                       // rows of a sample window (L <= 32)
@@ -245,7 +222,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
     const int L = a.L, b = blockIdx.x, row0 = b * L;
     const size_t g0 = (size_t)row0 * D;
     const bool rok = rr < L;
-    QSTAMP(0);
+    STAMP(0);
     if (tid < QROWS) Mb[tid] = tid < L ? (1.0f - a.mask[row0 + tid]) * MASK_VALUE : MASK_VALUE;
     const size_t plane_pw = pack3_plane(D, D), plane_qkv = pack3_plane(D, 3 * D);
     const Drop nodrop{0u, 0u, 1.f, 0u};
@@ -291,7 +268,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) X[r] = acc[r] + pv[r];
     }
-    QSTAMP(1);
+    STAMP(1);
 
     // ---- four conv layers (:133-139): x <- x + drop(relu(pointwise(depthwise7(LN(x)))))
     // (a real loop: the kernel executes every instruction ONCE per workgroup and one workgroup runs per CU, so unrolled it was 128 KB of
@@ -310,7 +287,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
         vec2d(bv, a.pw_b[l], w, h);
         d2tile(X, T, w, m, h);
         __syncthreads();
-        if (l == 0) QSTAMP(10);
+        if (l == 0) STAMP(10);
         {
             Row4 x;
             tile_to_row(x, T, rr, sub);
@@ -319,7 +296,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
             row_to_tile(x, T, rr, sub);
         }
         __syncthreads();
-        if (l == 0) QSTAMP(11);
+        if (l == 0) STAMP(11);
         uint16_t* P = (l & 1) ? P1 : P0;
         {   // depthwise conv k = 7 along the sequence: thread = (channel, half of the rows); rows outside [0, L) are zeros in the tile
             float win[16 + 2 * HALO], uo[16];
@@ -335,7 +312,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
                 for (int k = 0; k < DWK; ++k) u += wk[k] * win[i + k];
                 uo[i] = u;
             }
-            if (l == 0) QSTAMP(12);
+            if (l == 0) STAMP(12);
 #pragma unroll
             for (int i = 0; i < 16; i += 2) pair_split_store(P, os + i, c, uo[i], uo[i + 1]);     // GEMM operand: three bf16 planes
             if constexpr (SAVE) {
@@ -346,12 +323,12 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
             }
         }
         __syncthreads();
-        if (l == 0) QSTAMP(13);
+        if (l == 0) STAMP(13);
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         tgemm<8>(P, ring, acc, l < 3 ? wnext(a.W3[min(l + 1, 3)], plane_pw, D, 32 * w, 0, 8) : wnext(a.Wqkv3, plane_qkv, 3 * D, 32 * w, 0, 8));
-        if (l == 0) QSTAMP(14);
+        if (l == 0) STAMP(14);
         const Drop dp = a.dp[l];
         uint32_t bits[2] = {0u, 0u};            // ReLU decisions of this lane's channels inside the two 16-channel groups of the wave
 #pragma unroll
@@ -370,8 +347,8 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
             uint16_t* mk = reinterpret_cast<uint16_t*>(a.relu_mask[l]);
             if (m < L) mk[(size_t)(row0 + m) * 8 + 2 * w + h] = (uint16_t)(h ? g1b : g0b);
         }
-        if (l == 0) QSTAMP(15);
-        QSTAMP(2 + l);
+        if (l == 0) STAMP(15);
+        STAMP(2 + l);
     }
 
     // ---- a8 first half (:168-173): h1 = drop(LN1(y3)) ; q, k, v = h1 W^T + b
@@ -405,7 +382,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
             d2global(V, a.v + g0, w, m, h, L);
         }
     }
-    QSTAMP(6);
+    STAMP(6);
     d2tile(V, T, w, m, h);                      // V[key][channel]: each wave reads back its own 32 columns only (the tile's row-phase readers are behind the barrier above)
     __syncthreads();
 
@@ -443,7 +420,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
         for (int r = 8 * hh; r < 8 * hh + 8; ++r) att[r] = O[r] * inv;
     }
     if constexpr (SAVE) d2global(att, a.att + g0, w, m, h, L);
-    QSTAMP(7);
+    STAMP(7);
     // ---- output block (:183-190): r = drop(att) + x ; h2 = drop(LN2(r)) ; y = drop(h2 Wo^T + b) + r
     {
         Row4 gl, bl, x;
@@ -471,7 +448,7 @@ __global__ __launch_bounds__(QT) void k_query_fwd(QueryFwdArgs a) {
             X[r] += (acc[r] + bo[r]) * drop_mul(a.d5, (uint32_t)((row0 + m) * D + 32 * w + nl(r, h)));
     }
     d2global(X, a.out + g0, w, m, h, L);
-    QSTAMP(8);
+    STAMP(8);
 }
 
 // =========================================================================================================
@@ -547,7 +524,7 @@ __global__ __launch_bounds__(QT) void k_query_bwd(QueryBwdArgs a) {
     const int L = a.L, b = blockIdx.x, row0 = b * L;
     const size_t g0 = (size_t)row0 * D;
     const bool rok = rr < L, mok = m < L;
-    QSTAMP(20);
+    STAMP(20);
     if (tid < QROWS) Mb[tid] = tid < L ? (1.0f - a.mask[row0 + tid]) * MASK_VALUE : MASK_VALUE;
     Ls[tid] = (tid & 31) < L ? a.lse[((size_t)b * 8 + (tid >> 5)) * L + (tid & 31)] : 0.f;
     const size_t plane_pw = pack3_plane(D, D), plane_t = pack3_plane(3 * D, D), plane_e = pack3_plane(D, a.EWc);
@@ -601,7 +578,7 @@ __global__ __launch_bounds__(QT) void k_query_bwd(QueryBwdArgs a) {
         for (int r = 0; r < 16; ++r) acc[r] = mok ? acc[r] * drop_mul(a.d4, (uint32_t)((row0 + m) * D + 32 * w + nl(r, h))) : 0.f;
         ln_bwd_t(xr, acc, a.ln2_g, DY, a.p_ln2g, a.p_ln2b, DR);
     }
-    QSTAMP(21);
+    STAMP(21);
 
     // ---- attention backward (:174-182), heads 2 w and 2 w + 1
     f32x16 dQd, dKd, dVd;
@@ -716,7 +693,7 @@ __global__ __launch_bounds__(QT) void k_query_bwd(QueryBwdArgs a) {
         d2global(dKd, a.dk + g0, w, m, h, L);
         d2global(dVd, a.dv + g0, w, m, h, L);
     }
-    QSTAMP(22);
+    STAMP(22);
 
     // ---- a8 first half backward (:168-173): dh1 = [dQ | dK | dV] [Wq; Wk; Wv] ; dy3 = dr + LN1^T(dh1 * m1)
     {
@@ -736,7 +713,7 @@ __global__ __launch_bounds__(QT) void k_query_bwd(QueryBwdArgs a) {
         for (int r = 0; r < 16; ++r) acc[r] = mok ? acc[r] * drop_mul(a.d1, (uint32_t)((row0 + m) * D + 32 * w + nl(r, h))) : 0.f;
         ln_bwd_t(x3, acc, a.ln1_g, DR, a.p_ln1g, a.p_ln1b, DY);
     }
-    QSTAMP(23);
+    STAMP(23);
 
     // ---- conv layers 3 .. 0 (autograd of :133-139)
 #pragma unroll 1
@@ -835,7 +812,7 @@ __global__ __launch_bounds__(QT) void k_query_bwd(QueryBwdArgs a) {
             row_ln_bwd(out, dvr, xh, rstd, a.ln_g[l], DY, sub, rok);
             DY = out;
         }
-        QSTAMP(24 + (3 - l));
+        STAMP(24 + (3 - l));
     }
     row_store(DY, a.dx0 + g0, rr, sub, rok);            // grad wrt Embedding.linear's output (the positional table's partial slabs are these rows)
 
@@ -858,7 +835,7 @@ __global__ __launch_bounds__(QT) void k_query_bwd(QueryBwdArgs a) {
             }
         }
     }
-    QSTAMP(28);
+    STAMP(28);
 }
 
 bool query_fused_ok(int L, int H, int EW) { (void)EW; return L <= QROWS && H == 8; }
@@ -869,10 +846,7 @@ void launch_query_bwd(const QueryBwdArgs& a, int B, hipStream_t s) {
     ensure_dynamic_lds((const void*)k_query_bwd, query_bwd_lds(), ok, "k_query_bwd");
     VSL_LAUNCH(k_query_bwd, dim3(B), dim3(QT), query_bwd_lds(), s, a);
     static int left = 2;
-    if (qdbg_on() && B > 16 && left > 0) {
-        --left;
-        qdbg_report("query_bwd: out block | attention | qkv + LN1 | L3 | L2 | L1 | L0 | linear", 20, 29, s);
-    }
+    if (stamps::enabled() && B > 16) stamps::report_range("query_bwd: out block | attention | qkv + LN1 | L3 | L2 | L1 | L0 | linear", 20, 29, s, left);
 }
 void launch_query_fwd(const QueryFwdArgs& a, int B, hipStream_t s) {
     static size_t ok = 0, okn = 0;
@@ -884,10 +858,10 @@ void launch_query_fwd(const QueryFwdArgs& a, int B, hipStream_t s) {
         VSL_LAUNCH(k_query_fwd<true>, dim3(B), dim3(QT), query_fwd_lds(), s, a);
     }
     static int left = 2;
-    if (qdbg_on() && B > 16 && left > 0) {
-        --left;
-        qdbg_report("query_fwd: linear | L0 | L1 | L2 | L3 | LN1+qkv | attention | out", 0, 9, s);
-        qdbg_report("  query_fwd L0 from d2tile: LN | dw | dw write | gemm | epilogue", 10, 16, s);
+    if (stamps::enabled() && B > 16) {
+        int l2 = left;
+        stamps::report("query_fwd: linear | L0 | L1 | L2 | L3 | LN1+qkv | attention | out", 9, s, left);
+        stamps::report_range("  query_fwd L0 from d2tile: LN | dw | dw write | gemm | epilogue", 10, 16, s, l2);
     }
 }
 

@@ -134,6 +134,10 @@ inline void ensure_dynamic_lds(const void* func, size_t bytes, size_t& granted, 
         granted = bytes;
     }
 }
+template <auto KERNEL> void dynamic_lds_optin(size_t bytes, const char* name) {      // (one grant per kernel instantiation)
+    static size_t granted = 0;
+    ensure_dynamic_lds((const void*)KERNEL, bytes, granted, name);
+}
 
 // ---------------------------------------------------------------- forward
 void launch_pack(const float* params, float* pack, const PackJob* jobs_dev, int njobs, hipStream_t s);
@@ -170,7 +174,7 @@ struct CbFwdArgs {
     int nosave;                    // inference: the instantiation that stores y[3], q, k, v only (x0_out, y[0..2], u, relu_mask, qf.h1 may be null; no dropout)
 };
 void launch_convblock_fwd(const CbFwdArgs& a, hipStream_t s);
-// the attention-output backward of one encoder application (a8 :183-190 backward; kernels_bwd.hip attn_out_bwd_tile)
+// the attention-output backward of one encoder application (a8 :183-190 backward; tile_bodies.hpp attn_out_bwd_tile)
 struct AttnOutBwdArgs {
     const float *dy, *dy2, *r_in, *ln_g, *WTpack;
     float *g_o, *dr, *p_lng, *p_lnb;
@@ -224,13 +228,25 @@ bool convblock_bwd_hosts_tail(int R, int L);      // does launch_convblock_bwd h
 bool convblock_bwd_hosts_linear(int R, int L);    // ... and tail 3 (the Embedding linear's data gradient)?
 bool convblock_bwd_hosts_qkv(int R, int L);       // ... and CbBwdArgs::qkv?  (its LN1 partial slabs are then convblock_slabs(R, L) many)
 int convblock_slabs(int R, int L);        // partial slabs per parameter of launch_convblock_bwd (= its grid)
-// The attention core of one encoder application, every head count and every L (kernels_attn_long.hip): what the host units call.  The per-head-size
-// launchers further down (launch_attn_fwd / _bwd: 8 heads, launch_attn_hd_*: 4 / 16, launch_attn_wide_*: 1 / 2) are their implementation.
-// (lse, and r_out / h2_out below, may be null in all the attention launchers: an inference forward does not store them)
-void launch_attn_fwd_any(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B, int L, int H, int b_off,
-                         Drop d2, hipStream_t s);
-void launch_attn_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
-                     int L, int H, int b_off, Drop d2, hipStream_t s);
+// The attention core of one encoder application (a8 :174-182), every head count and every L: kernels_attn.hip picks the unit of the head size
+// (attn.hpp: the contract between those units).  Q / K / V / att / dr / dQ / dK / dV are (R, 128) rows with head h at columns h hd .. h hd + hd - 1,
+// mask is the key mask (B, L), lse (B, H, L) is in natural-log units.
+struct AttnArgs {
+    const float *Q, *K, *V, *mask;
+    float *att, *lse;             // forward: outputs (lse may be null: an inference forward does not store it) ; backward: inputs
+    const float* dr;              // backward only from here: gradient of r = drop3(att) + x
+    float *dQ, *dK, *dV;          // dQ: attn_dq_slabs(L) slabs of (R, 128) that k_qkv_bwd adds
+    int B, L, H, b_off;
+    Drop d2, d3;                  // probabilities ; attention output (backward only)
+};
+void launch_attn_fwd(const AttnArgs& a, hipStream_t s);       // L > 128 or H != 8 (8 heads at L <= 128: launch_attn_block_fwd)
+// key-major dK / dV for every L.  dQ up to L = ATTN_SLAB_MAX_L (or with VSL_ATTN_DQ_SLABS=1): attn_bwd_dq_slabs(L) partial slabs, one per 256-key
+// block; longer: computed query-major, complete in slab 0.  attn_dq_slabs(L) = the slabs written either way (the plan allocates them)
+void launch_attn_bwd(const AttnArgs& a, hipStream_t s);
+int attn_bwd_dq_slabs(int L);
+int attn_dq_slabs(int L);
+inline bool attn_heads_supported(int H) { return H == 1 || H == 2 || H == 4 || H == 8 || H == 16; }
+// (r_out / h2_out may be null: an inference forward does not store them)
 void launch_attn_out_fwd(const float* att, const float* x, const float* ln_g, const float* ln_b, const float* Wpack,
                          const float* bo, float* r_out, float* h2_out, float* y_out, int R, Drop d3, Drop d4, Drop d5,
                          hipStream_t s);
@@ -355,34 +371,6 @@ void launch_rnn_bwd(const RnnBwdArgs& a, hipStream_t s);      // one image = W_h
 void launch_wgrad(const WgradBatch& wb, hipStream_t s);     // kernels_wgrad.hip
 void launch_attn_out_bwd(const float* dy, const float* dy2, const float* r, const float* ln_g, const float* WTpack, float* g_o,
                          float* dr, float* p_lng, float* p_lnb, int R, Drop d4, Drop d5, hipStream_t s);
-// dq = false (L > 256 only): dK / dV alone, the key blocks write no dQ partials (k_attn_dq computes dQ: launch_attn_bwd_any)
-void launch_attn_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
-                     const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                     Drop d3, hipStream_t s, bool dq = true);
-int attn_bwd_dq_slabs(int L);             // L > 256: dQ is written as this many (R, 128) partial slabs (one per 256-key block); k_qkv_bwd adds them
-// the attention core of num_heads 4 / 16 (head sizes 32 / 8; kernels_attn_hd.hip), every L: the contracts of launch_attn_fwd / launch_attn_bwd,
-// dQ as attn_bwd_dq_slabs(L) partial slabs
-void launch_attn_hd_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
-                        int L, int H, int b_off, Drop d2, hipStream_t s);
-void launch_attn_hd_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
-                        const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                        Drop d3, hipStream_t s, bool dq = true);
-// the attention core of num_heads 1 / 2 (head sizes 128 / 64; kernels_attn_wide.hip), every L: the same contracts.  The backward is a key-major
-// dK / dV kernel plus a query-major dQ kernel; query_major = false: dQ as attn_bwd_dq_slabs(L) partial slabs (one per 256-key block),
-// true (L > ATTN_SLAB_MAX_L): the complete dQ in slab 0 -- attn_dq_slabs(L) either way
-void launch_attn_wide_fwd(const float* Q, const float* K, const float* V, const float* mask, float* att, float* lse, int B,
-                          int L, int H, int b_off, Drop d2, hipStream_t s);
-void launch_attn_wide_bwd(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
-                          const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2,
-                          Drop d3, hipStream_t s, bool query_major);
-// the attention backward of every head count (kernels_attn_long.hip): L <= ATTN_SLAB_MAX_L (or VSL_ATTN_DQ_SLABS=1) = the launchers above;
-// longer = their dK / dV-only instantiations + k_attn_dq, which writes the complete dQ into slab 0.  attn_dq_slabs(L): the slabs k_qkv_bwd
-// adds (and the plan allocates) on that route
-void launch_attn_bwd_any(const float* Q, const float* K, const float* V, const float* att, const float* dr, const float* lse,
-                         const float* mask, float* dQ, float* dK, float* dV, int B, int L, int H, int b_off, Drop d2, Drop d3, hipStream_t s);
-bool attn_dq_query_major(int L);
-int attn_dq_slabs(int L);
-inline bool attn_heads_supported(int H) { return H == 1 || H == 2 || H == 4 || H == 8 || H == 16; }
 void launch_qkv_bwd(const float* dQ, const float* dK, const float* dV, const float* x, const float* dr,
                     const float* ln_g, const uint16_t* WT3 /* split pack of the (384, 128) operand */, float* dx, float* p_lng, float* p_lnb, int R,
                     Drop d1, hipStream_t s, int dq_slabs = 1);
