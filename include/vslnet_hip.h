@@ -197,6 +197,38 @@ typedef struct {                       /* zero-initialise; new fields are append
 int vsl_localize_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, int64_t* out);
 int vsl_localize(vsl_handle h, const vsl_localize_io* io, void* hip_stream);
 
+/* TRAINING THROUGH A SHARED VIDEO ENCODING: one step over N videos and B queries, query b paired with video video_index[b] (no reference counterpart:
+ * it runs the video half once per sample).  VisualProjection and encoder application 0 run forward AND backward on N T rows; the query branch,
+ * CQAttention, CQConcatenate, the highlight layer, the predictor, the span heads and the losses run on B samples as in vsl_forward / vsl_backward.
+ * In these calls the vsl_io fields carry: video_features (or the bf16 copy) as (N, T, video_feature_dim); v_mask as the (B, T) PER-QUERY mask, i.e.
+ * video_v_mask[video_index] (vsl_loss then works unchanged); outputs and seeds as (B, T); training = 1, or 0 for the saved evaluation path.
+ * Semantics:
+ *   - dropout: the sites of the video half -- VisualProjection's input and sites 0..8 of encoder application 0 -- are keyed by the element index in
+ *     their (N, T, .) tensors: ONE mask per video, shared by its queries.  Every other site keeps its (B, .) keying, CQAttention's context dropout
+ *     included (it applies to sample b).  At drop_rate 0 the step is mathematically vsl_forward / vsl_backward on the replicated batch
+ *     video_features[video_index]; at drop_rate > 0 it is a different but equally valid stochastic estimate -- not reference parity;
+ *   - the gradient of the encoding is dCv[n] = sum over {b : video_index[b] = n} of dC[b], added in ASCENDING b.  There is no floating-point atomic
+ *     anywhere in the path: two runs of the same step give bit-identical gradients.  A video without a query gets a zero dCv and contributes nothing;
+ *   - the encoding is computed inside the step at the batch's T, so the rule of vsl_encode_video about an encoding and its padded T does not arise.
+ * vsl_io.inference != 0 is refused (use vsl_encode_video + vsl_localize), and so are a non-zero sample_offset and early_grads_event (data parallel is not
+ * supported through a shared encoding).  fused_loss and fused_step work as in vsl_backward.  The handle remembers what its last forward was:
+ * vsl_backward after vsl_forward_shared and vsl_backward_shared after any other forward are errors, and vsl_loss finds its scratch in the last
+ * forward's plan.  The addressing limits (2^31 workspace floats, 2 GiB per (rows, 128) activation) apply to N T 128 and to B T 128 separately.
+ * Detect the feature by the presence of the symbols: VSL_ABI_VERSION does not change for an added entry point. */
+typedef struct {                       /* zero-initialise; new fields are appended */
+    int32_t N;                         /* videos (>= 1)                                                                                    */
+    const int32_t* video_index;        /* (B), device: video of query b.  0 <= value < N is the CALLER'S precondition: the library does not */
+                                       /* read it on the host, and an index outside the range reads outside the encoding                   */
+    const float* video_v_mask;         /* (N, T): per VIDEO                                                                                */
+} vsl_shared_io;
+/* floats of vsl_io.workspace for a shared step: the training plan with the video half sized by N, plus dCv (N, T, 128) and N + 1 + B ints of grouping */
+int vsl_shared_workspace_floats(vsl_handle h, int B, int N, int T, int Lq, int Lc, int64_t* out);
+int vsl_forward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream);
+int vsl_backward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream);
+/* vsl_workspace_offset for the plan of a shared step: tensors of the video half ("video_affine", "venc", "venc_*", "relu_venc_*", "d_video_affine")
+ * have N T rows; added names: "d_venc_video" (dCv, (N, T, 128)), "group_start" (N + 1 int32), "group_members" (B int32) */
+int64_t vsl_shared_workspace_offset(vsl_handle h, int B, int N, int T, int Lq, int Lc, const char* name);
+
 /* compute_loss + compute_highlight_loss (VSLNet_t7.py:67-72) and their gradient seeds */
 int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_stream);
 /* autograd backward of everything in vsl_forward (main_t7.py:110); needs the same io (workspace, seed) */

@@ -76,7 +76,10 @@ def build_parser():
     p.add_argument('--data', type=str, default='resident', help='[resident | loader] resident: the whole split lives in HBM and a '
                    'batch is a device gather; loader: host-side collate + H2D copy per step, like the reference')
     p.add_argument('--share_videos', action='store_true', help='--mode test with --data resident: encode every video once and localise each '
-                   'query against the resident encoding (runner.eval_test_shared); every batch is then padded to the split\'s longest video')
+                   'query against the resident encoding (runner.eval_test_shared); every batch is then padded to the split\'s longest video.  '
+                   '--mode train with --data resident, one process: batches grouped by video (--queries_per_video) and the training step through a '
+                   'shared encoding (Engine.forward_shared): the video half runs once per video, forward and backward')
+    p.add_argument('--queries_per_video', type=int, default=4, help='--mode train --share_videos: queries of one video per group of the grouped order')
     p.add_argument('--synthetic_train', type=int, default=512)
     p.add_argument('--synthetic_test', type=int, default=128)
     return p
@@ -103,10 +106,18 @@ def train(configs, dataset, features, device, world, rank, log=print):
     from vslnet_amd.model.VSLNet import VSLNet, build_optimizer_and_scheduler
     model_dir = model_home(configs)
     gen = torch.Generator().manual_seed(configs.seed)                       # same shuffle on every rank
+    share = bool(getattr(configs, 'share_videos', False))
+    if share:
+        if world > 1:
+            raise ValueError('--mode train --share_videos is single-process: data parallel through a shared encoding is not supported (run without torchrun)')
+        if configs.data != 'resident':
+            raise ValueError('--mode train --share_videos needs --data resident (the grouped order gathers one feature row per video out of the split held in device memory)')
+        if configs.optimizer != 'fused':
+            raise ValueError('--mode train --share_videos runs the production sequence (lazy loss, fused optimizer): use --optimizer fused')
     if configs.data == 'resident':
         train_loader = data.ResidentSplit(dataset['train_set'], features, configs, device, train=True, generator=gen)
         test_loader = data.ResidentSplit(dataset['test_set'], features, configs, device, train=False)
-        shards = lambda: train_loader.shards(rank, world)
+        shards = (lambda: train_loader.shards(queries_per_video=configs.queries_per_video)) if share else (lambda: train_loader.shards(rank, world))
         log('dataset resident in HBM: %.1f MiB train, %.1f MiB test' % (train_loader.nbytes() / 2 ** 20, test_loader.nbytes() / 2 ** 20))
     elif configs.data == 'loader':
         train_loader = data.get_train_loader(dataset['train_set'], features, configs, pin=True, generator=gen)
@@ -174,8 +185,12 @@ def train(configs, dataset, features, device, world, rank, log=print):
                         losses, seeds = torch.zeros(4, device=device), None
                     else:
                         q_mask = (batch['word_ids'] != 0).float()
-                        eng.forward(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['v_mask'], q_mask,
-                                    training=True, seed=(configs.seed << 20) + global_step, sample_offset=batch['row0'])
+                        if share:       # N videos, B queries: the video half once per video (the engine's backward dispatches on the last forward)
+                            eng.forward_shared(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['video_v_mask'], q_mask,
+                                               batch['video_index'], training=True, seed=(configs.seed << 20) + global_step)
+                        else:
+                            eng.forward(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['v_mask'], q_mask,
+                                        training=True, seed=(configs.seed << 20) + global_step, sample_offset=batch['row0'])
                         losses, *seeds = eng.loss(batch['s_labels'], batch['e_labels'], batch['h_labels'], 1.0,
                                                   configs.highlight_lambda, inv_batch=inv_batch, mask_sum=mask_sum, lazy=True)
                     dp.backward_exchange_step(eng, xchg, grads, seeds, opt)          # (tests/test_dp_gloo.py drives its multi-rank half on 2 and 3 ranks)

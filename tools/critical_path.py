@@ -10,6 +10,7 @@ prints:
     and gaps where the HOST enqueued the launch after its dependencies had already finished (host-late).
 
     python tools/critical_path.py [--steps-before 30] [--out profiles/r06_critical_path.txt] [bench shape flags]
+    python tools/critical_path.py --qpv 4 --out profiles/shared_train_critical_path.txt      # the step through a shared encoding: N = batch / 4 videos
 """
 import argparse
 import os
@@ -95,6 +96,7 @@ def main():
     ap.add_argument('--steps-before', type=int, default=30)
     ap.add_argument('--steps-after', type=int, default=10)
     ap.add_argument('--out', default='')
+    ap.add_argument('--qpv', type=int, default=0, help='> 0: the training step through a shared video encoding (Engine.forward_shared), this many queries per video')
     args = ap.parse_args()
     import torch
     from vslnet_amd.model.VSLNet import VSLNet
@@ -110,11 +112,19 @@ def main():
     pad_vec, glove_vec = model.embedding_net.word_emb.pad_vec.data, model.embedding_net.word_emb.glove_vec.data
     batches = [synthetic_batch(configs, B, T, Lq, Lc, seed=100 + 1000 * k) for k in range(10)]
     mask_sum = float(batches[0]['v_mask'].sum().item())
+    N = (B + args.qpv - 1) // args.qpv if args.qpv > 0 else B
+    vidx = (torch.arange(B, device='cuda') // max(args.qpv, 1)).to(torch.int32)
+    if args.qpv > 0:
+        for b in batches:
+            b['vfeats'], b['video_v_mask'] = b['vfeats'][:N].contiguous(), b['v_mask'][:N].contiguous()
     opt = FlatAdamW(flat, eng.layout, lr=configs.init_lr, num_train_steps=100000, clip_norm=configs.clip_norm, engine=eng)
 
     def step(i):
         b = batches[i % len(batches)]
-        eng.forward(flat, pad_vec, glove_vec, b['word_ids'], b['char_ids'], b['vfeats'], b['v_mask'], b['q_mask'], training=True, seed=i)
+        if args.qpv > 0:
+            eng.forward_shared(flat, pad_vec, glove_vec, b['word_ids'], b['char_ids'], b['vfeats'], b['video_v_mask'], b['q_mask'], vidx, training=True, seed=i)
+        else:
+            eng.forward(flat, pad_vec, glove_vec, b['word_ids'], b['char_ids'], b['vfeats'], b['v_mask'], b['q_mask'], training=True, seed=i)
         _, d_h, d_sl, d_el = eng.loss(b['s_labels'], b['e_labels'], b['h_labels'], 1.0, configs.highlight_lambda, inv_batch=1.0 / B, mask_sum=mask_sum, lazy=True)
         backward_exchange_step(eng, None, grads, (d_h, d_sl, d_el), opt)
 
@@ -140,7 +150,8 @@ def main():
     per = len(recs) // (1 + args.steps_after)
     one = recs[:per]
     nxt = recs[per]['start_us'] - recs[0]['start_us'] if len(recs) > per else float('nan')
-    title = 'critical-path ledger, HIP events on the dispatch packets (tools/critical_path.py): B=%d T=%d Dv=%d Lq=%d %s, drop 0.2, optimizer inside' % (B, T, Dv, Lq, args.predictor)
+    title = 'critical-path ledger, HIP events on the dispatch packets (tools/critical_path.py): B=%d T=%d Dv=%d Lq=%d %s, drop 0.2, optimizer inside%s' % (
+        B, T, Dv, Lq, args.predictor, ', shared encoding: %d videos, %d queries per video' % (N, args.qpv) if args.qpv > 0 else '')
     out = open(args.out, 'w') if args.out else sys.stdout
     res = ledger(one, out, ms_per_step=plain, title=title)
     out.write('\n# step period with the events attached (first launch of this step -> first launch of the next): %.1f us ; un-instrumented loop: %.1f us per step\n' % (nxt, 1e3 * plain))

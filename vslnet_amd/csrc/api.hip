@@ -23,6 +23,8 @@ static int workspace_floats(vsl_handle_s* h, PlanKind kind, int B, int T, int Lq
     return 0;
 }
 
+static int64_t plan_offset(vsl_handle_s* h, const Plan* p, const char* name);
+
 extern "C" {
 
 const char* vsl_last_error(void) { return g_err.c_str(); }
@@ -117,6 +119,23 @@ int64_t vsl_workspace_offset(vsl_handle h, int B, int T, int Lq, int Lc, const c
     Plan* p = nullptr;
     if (h && h->last_infer) { fail("vsl_workspace_offset: the last forward saved nothing (inference mode): there is no saved activation to point at"); return -2; }
     if (!h || !name || get_plan(h, B, T, Lq, Lc, &p)) return -1;
+    return plan_offset(h, p, name);
+}
+
+int64_t vsl_shared_workspace_offset(vsl_handle h, int B, int N, int T, int Lq, int Lc, const char* name) {
+    Plan* p = nullptr;
+    if (h && h->last_infer) { fail("vsl_shared_workspace_offset: the last forward saved nothing (inference mode): there is no saved activation to point at"); return -2; }
+    if (!h || !name || get_plan(h, B, T, Lq, Lc, &p, PlanKind::TrainShared, N)) return -1;
+    const std::string n = name;
+    if (n == "d_venc_video") return p->dCv;
+    if (n == "group_start") return p->csr;
+    if (n == "group_members") return p->csr + p->csr_members();
+    return plan_offset(h, p, name);
+}
+
+}  // extern "C"
+
+static int64_t plan_offset(vsl_handle_s* h, const Plan* p, const char* name) {
     const std::string n = name;
     const std::pair<const char*, int64_t> tab[] = {
         {"video_affine", p->vf}, {"embedding_net", p->qf}, {"emb_concat", p->E}, {"venc", p->ve.out}, {"qenc", p->qe.out},
@@ -150,6 +169,36 @@ int64_t vsl_workspace_offset(vsl_handle h, int B, int T, int Lq, int Lc, const c
     return -1;
 }
 
+// the checks vsl_backward and vsl_backward_shared share: the seeds or the fused loss, the gradient bucket, the fused optimizer step
+static int check_backward_io(vsl_handle_s* h, const vsl_io* io, const char* who) {
+    if (const vsl_loss_io* l = io->fused_loss) {
+        if (!l->start_labels || !l->end_labels || !l->h_labels || !l->losses) return fail("%s: fused_loss has a null pointer", who);
+        if (!l->d_start_logits || !l->d_end_logits || !l->d_h_score) return fail("%s: fused_loss needs the three gradient seed outputs", who);
+        if (!io->grads) return fail("%s needs grads", who);
+    } else
+    if (!io->d_start_logits || !io->d_end_logits || !io->grads) return fail("%s needs d_start_logits, d_end_logits and grads", who);
+    if (const vsl_fused_step* fs = io->fused_step) {
+        if (!fs->params || !fs->exp_avg || !fs->exp_avg_sq) return fail("%s: fused_step needs params, exp_avg and exp_avg_sq", who);
+        if (fs->hp.step < 1) return fail("%s: fused_step.hp.step must be >= 1 (got %d)", who, fs->hp.step);
+        if (io->early_grads_event) return fail("%s: fused_step (single process) and early_grads_event (data parallel) exclude each other", who);
+        if (int rc = ensure_opt_state(h)) return rc;
+    }
+    return 0;
+}
+
+static int check_shared_io(const vsl_io* io, const vsl_shared_io* sh, const char* who) {
+    if (!sh) return fail("%s: the vsl_shared_io is NULL", who);
+    if (sh->N < 1) return fail("%s: N=%d videos (at least one)", who, sh->N);
+    if (!sh->video_index) return fail("%s: video_index is NULL (the video of each query)", who);
+    if (!sh->video_v_mask) return fail("%s: video_v_mask is NULL (the (N, T) clip mask of the videos)", who);
+    if (io->inference) return fail("%s: inference != 0 is refused -- a forward that is never differentiated over a shared encoding is vsl_encode_video + vsl_localize", who);
+    if (io->sample_offset) return fail("%s: sample_offset=%d is refused: data parallel is not supported through a shared encoding", who, io->sample_offset);
+    if (io->early_grads_event) return fail("%s: early_grads_event is refused: data parallel is not supported through a shared encoding", who);
+    return 0;
+}
+
+extern "C" {
+
 int vsl_forward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
     if (io->inference && io->training) return fail("vsl_forward: inference and training exclude each other (the inference kernels have no dropout)");
@@ -161,8 +210,55 @@ int vsl_forward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     forward_full(c);
     HIP_OK(hipGetLastError());
     h->last_infer = io->inference != 0;
+    h->last_fwd = io->inference ? vsl_handle_s::FwdInfer : vsl_handle_s::FwdFull;
     if (io->inference) h->infer_ws = io->workspace;
     else if (h->infer_ws == io->workspace) h->infer_ws = nullptr;
+    return 0;
+}
+
+// ---- training through a shared video encoding: N videos, B queries per step
+int vsl_shared_workspace_floats(vsl_handle h, int B, int N, int T, int Lq, int Lc, int64_t* out) {
+    if (!h || !out) return fail("null argument");
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, B, T, Lq, Lc, &p, PlanKind::TrainShared, N)) return rc;
+    *out = p->total;
+    return 0;
+}
+
+int vsl_forward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream) {
+    if (int rc = check_io(h, io)) return rc;
+    if (int rc = check_shared_io(io, sh, "vsl_forward_shared")) return rc;
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, PlanKind::TrainShared, sh->N)) return rc;
+    Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
+    c.main = c.s;
+    c.sh = sh;
+    CallScope scope(h);
+    forward_shared_train(c);
+    HIP_OK(hipGetLastError());
+    h->last_infer = false;
+    h->last_fwd = vsl_handle_s::FwdShared;
+    h->shared_N = sh->N;
+    if (h->infer_ws == io->workspace) h->infer_ws = nullptr;
+    return 0;
+}
+
+int vsl_backward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream) {
+    if (int rc = check_io(h, io)) return rc;
+    if (int rc = check_shared_io(io, sh, "vsl_backward_shared")) return rc;
+    if (h->last_fwd != vsl_handle_s::FwdShared || io->workspace == h->infer_ws)
+        return fail("vsl_backward_shared: the handle's last forward was not vsl_forward_shared (an ordinary forward is differentiated by vsl_backward; an inference forward saved nothing)");
+    if (sh->N != h->shared_N) return fail("vsl_backward_shared: N=%d, but the last vsl_forward_shared ran over N=%d videos", sh->N, h->shared_N);
+    if (int rc = check_backward_io(h, io, "vsl_backward_shared")) return rc;
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, PlanKind::TrainShared, sh->N)) return rc;
+    Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
+    c.main = c.s;
+    c.sh = sh;
+    CallScope scope(h);
+    run_backward(c);
+    HIP_OK(hipGetLastError());
+    h->sq_src = p->sq_cover ? p->sq_dev : nullptr; h->sq_n = p->nblocks; h->sq_grads = io->grads;
     return 0;
 }
 
@@ -190,6 +286,7 @@ int vsl_encode_video(vsl_handle h, const vsl_encode_io* e, void* hip_stream) {
     CallScope scope(h);
     forward_encode(c, e->video_encoding);
     HIP_OK(hipGetLastError());
+    h->last_fwd = vsl_handle_s::FwdInfer;
     h->last_infer = true;            // (nothing saved: vsl_backward in this workspace and vsl_workspace_offset are refused as after an inference forward)
     h->infer_ws = e->workspace;
     return 0;
@@ -221,6 +318,7 @@ int vsl_localize(vsl_handle h, const vsl_localize_io* l, void* hip_stream) {
     forward_localize(c, CqContext{l->video_encoding, l->video_index}, l->v_mask);
     HIP_OK(hipGetLastError());
     h->last_infer = true;
+    h->last_fwd = vsl_handle_s::FwdInfer;
     h->infer_ws = l->workspace;
     return 0;
 }
@@ -231,7 +329,8 @@ int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_str
     if ((l->d_h_score == nullptr) != (l->d_start_logits == nullptr) || (l->d_h_score == nullptr) != (l->d_end_logits == nullptr))
         return fail("gradient seed outputs must be all set or all null");
     Plan* p = nullptr;
-    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, io->inference ? PlanKind::Infer : PlanKind::Train)) return rc;      // (its scratch lies where that forward's plan put it)
+    const bool shared = !io->inference && h->last_fwd == vsl_handle_s::FwdShared;      // (the outputs of vsl_forward_shared: vsl_io.v_mask is the (B, T) per-query mask)
+    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, io->inference ? PlanKind::Infer : shared ? PlanKind::TrainShared : PlanKind::Train, h->shared_N)) return rc;      // (its scratch lies where that forward's plan put it)
     ProfScope ps(h, "loss");
     launch_loss(io->start_logits, io->end_logits, io->h_score, l->start_labels, l->end_labels, l->h_labels, io->v_mask, io->B,
                 io->T, l->inv_batch, l->mask_sum, l->w_loc, l->w_highlight, io->workspace + p->loss_scratch, l->losses,
@@ -244,20 +343,11 @@ int vsl_backward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
     if (io->inference || io->workspace == h->infer_ws)
         return fail("vsl_backward: the last forward saved nothing (inference mode): run vsl_forward with inference = 0 for a batch that is to be differentiated");
-    if (const vsl_loss_io* l = io->fused_loss) {
-        if (!l->start_labels || !l->end_labels || !l->h_labels || !l->losses) return fail("vsl_backward: fused_loss has a null pointer");
-        if (!l->d_start_logits || !l->d_end_logits || !l->d_h_score) return fail("vsl_backward: fused_loss needs the three gradient seed outputs");
-        if (!io->grads) return fail("vsl_backward needs grads");
-    } else
-    if (!io->d_start_logits || !io->d_end_logits || !io->grads) return fail("vsl_backward needs d_start_logits, d_end_logits and grads");
+    if (h->last_fwd == vsl_handle_s::FwdShared)
+        return fail("vsl_backward: the handle's last forward was vsl_forward_shared: its saves are differentiated by vsl_backward_shared");
+    if (int rc = check_backward_io(h, io, "vsl_backward")) return rc;
     Plan* p = nullptr;
     if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p)) return rc;
-    if (const vsl_fused_step* fs = io->fused_step) {
-        if (!fs->params || !fs->exp_avg || !fs->exp_avg_sq) return fail("vsl_backward: fused_step needs params, exp_avg and exp_avg_sq");
-        if (fs->hp.step < 1) return fail("vsl_backward: fused_step.hp.step must be >= 1 (got %d)", fs->hp.step);
-        if (io->early_grads_event) return fail("vsl_backward: fused_step (single process) and early_grads_event (data parallel) exclude each other");
-        if (int rc = ensure_opt_state(h)) return rc;
-    }
     Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
     c.main = c.s;
     CallScope scope(h);

@@ -227,6 +227,9 @@ void run_backward(Ctx& c) {
     const Plan& p = *c.p;
     const int B = p.B, T = p.T, Lq = p.Lq, R = B * T, Rq = B * Lq;
     const int ntiles = (R + TILE_M - 1) / TILE_M, nchunk = (R + WG_ROWS - 1) / WG_ROWS, nchunk_q = (Rq + WG_ROWS - 1) / WG_ROWS;
+    // a step through a shared encoding (plan TrainShared): the video half -- encoder application 0 and VisualProjection -- runs on Nv T rows
+    const bool shared = p.kind == PlanKind::TrainShared;
+    const int Nv = p.NV(), Rv = Nv * T;
     const vsl_io* io = c.io;
     // streams: `main` carries the dependent dX chain; sw = every weight-gradient GEMM (they only feed the final
     // reduction); sq = the query-side chain (query encoder pass + embedding stack) once CQAttention's backward is done
@@ -438,6 +441,7 @@ void run_backward(Ctx& c) {
             q.dC = c.W(p.dC); q.dQ = c.W(p.dQtot); q.dSr = c.W(p.dSr); q.dSs = c.W(p.dSs);
             q.P1 = c.W(p.cqP1); q.P2 = c.W(p.cqP2); q.P3 = c.W(p.cqP3); q.P4 = c.W(p.cqP4); q.P5 = c.W(p.cqP5);
         }
+        if (shared && !c.dry) q.vidx = c.sh->video_index;        // C is the (Nv, T, 128) encoding; dC stays (B, T, 128)
         q.T = T; q.Lq = Lq; q.b_off = 0; q.dc = c.drop(SITE_CQ_C); q.dq = c.drop(SITE_CQ_Q);
         q.p_w4C = c.slab(P.w4C, D, B * ntile); q.p_w4mlu = c.slab(P.w4mlu, D, B * ntile);
         q.p_w4Q = c.slab(P.w4Q, D, B); q.p_pool = c.slab(P.pool_w, D, B); q.p_bcat = c.slab(P.cat_b, D, B);
@@ -462,21 +466,27 @@ void run_backward(Ctx& c) {
     // The step's LAST weight-gradient batch (VisualProjection + the video pass' four pointwise gradients, sample-local query path) starts into an
     // empty chip: chunk rows that make it whole rounds of one-workgroup-per-CU chunks (Dv = 1024: 12 blocks x 32 chunks = 1.5 rounds -> 400 rows,
     // 252 workgroups; profiles/r06_notes.md section 8: -0.6 % against 256-row chunks).
-    const int tail_rows = query_fused(c) ? wgrad_rows_whole_rounds(R, (cf.video_feature_dim + 127) / 128 + 4, c.h->cus) : WG_ROWS;
+    const int tail_rows = query_fused(c) ? wgrad_rows_whole_rounds(Rv, (cf.video_feature_dim + 127) / 128 + 4, c.h->cus) : WG_ROWS;
     c.pw_rows = tail_rows == WG_ROWS ? 0 : tail_rows;
-    enc_bwd(c, P.fe, K.fe, p.ve, c.dry ? nullptr : c.W(p.dC), nullptr, p.dvf, c.dry ? nullptr : io->v_mask, B, 0, sw, &pw_video);
+    // shared encoding: dCv[n] = the sum of dC[b] over the queries of video n in ascending b (kernels_shared.hip; the CSR is the forward's), a
+    // stand-alone launch at the head of the video chain
+    if (shared) {
+        const int* csr = c.dry ? nullptr : reinterpret_cast<const int*>(c.W(p.csr));
+        LAUNCH("group_sum", launch_group_sum(c.W(p.dC), csr, csr + p.csr_members(), c.W(p.dCv), Nv, T, c.s));
+    }
+    enc_bwd(c, P.fe, K.fe, p.ve, c.dry ? nullptr : c.W(shared ? p.dCv : p.dC), nullptr, p.dvf, c.dry ? nullptr : c.video_mask(), Nv, 0, sw, &pw_video);
     c.pw_rows = 0;
     {   // tail of the video stream: VisualProjection + the video pass' pointwise weight gradients, back to back, no waits
         WgradBatch wb;
         memset(&wb, 0, sizeof wb);
         WgradJob j = wjob();
         j.rows = tail_rows == WG_ROWS ? 0 : tail_rows;
-        const int nchunk = wgrad_chunks(R, tail_rows);      // (shadows the 256-row count: this job's slabs)
+        const int nchunk = wgrad_chunks(Rv, tail_rows);     // (shadows the 256-row count: this job's slabs)
         if (!c.dry) {
             j.G[0] = c.W(p.dvf); j.Afull = io->video_features;
             if (io->video_features_bf16) { j.Afull = reinterpret_cast<const float*>(io->video_features_bf16); j.a_bf16 = 1; }
         }
-        j.nG = 1; j.nA = 0; j.K = cf.video_feature_dim; j.R = R; j.drop_on_A = 1; j.dp = c.drop(SITE_VIS);
+        j.nG = 1; j.nA = 0; j.K = cf.video_feature_dim; j.R = Rv; j.drop_on_A = 1; j.dp = c.drop(SITE_VIS);
         j.out = c.slab(P.va_w, D * cf.video_feature_dim, nchunk);
         j.out_bias[0] = c.slab(P.va_b, D, nchunk);
         wb.j[wb.n++] = j;

@@ -101,18 +101,18 @@ bool query_fused(const Ctx& c) {
 
 // ---- the stages: each enqueues on c.s and reads nothing but its arguments, the plan and the call's vsl_io
 
-// VisualProjection + encoder application 0 over the plan's B x T clips; `out`: the caller's encoding (vsl_encode_video), nullptr = the plan's own buffer
+// VisualProjection + encoder application 0 over the clips of the plan's video half (B x T; N x T in a shared training step); `out`: the caller's encoding (vsl_encode_video), nullptr = the plan's own buffer
 static void video_branch(Ctx& c, float* out) {
     const vsl_config& cf = c.h->cfg; const ModelP& P = c.h->P; const ModelPk& K = c.h->K;
     const Plan& p = *c.p; const vsl_io& io = *c.io;
-    const int R = p.B * p.T;
+    const int Nv = p.NV(), R = Nv * p.T;
     if (io.video_features_bf16)      // bf16 throughput mode
         LAUNCH("vproj_fwd", launch_vproj_fwd_bf16(io.video_features_bf16, reinterpret_cast<const uint16_t*>(c.PK(K.va_f16)), c.P(P.va_b), c.W(p.vf), R,
                                                   cf.video_feature_dim, c.drop(SITE_VIS), c.s));
     else
         LAUNCH("vproj_fwd", launch_vproj_fwd3(io.video_features, reinterpret_cast<const uint16_t*>(c.PK(K.va_f3)), c.P(P.va_b), c.W(p.vf), R, cf.video_feature_dim,
                                               c.drop(SITE_VIS), c.s));
-    enc_fwd(c, P.fe, K.fe, p.ve, c.W(p.vf), io.v_mask, p.B, 0, nullptr, out);
+    enc_fwd(c, P.fe, K.fe, p.ve, c.W(p.vf), c.video_mask(), Nv, 0, nullptr, out);
 }
 
 // a pack launch another stream's kernel has to wait for: its stop event and its record in the profiler's ledger (nullptr / -1: nothing to wait for)
@@ -278,8 +278,10 @@ static PackWait side_packs(Ctx& c, hipStream_t sp) {
     return w;
 }
 
-// vsl_forward: the video branch and the query branch side by side, joined in front of the CQ kernels
-void forward_full(Ctx& c) {
+// the video branch and the query branch side by side, joined in front of the CQ kernels.  `vidx` (a shared training step): the video branch ran over
+// the plan's N videos and CQAttention reads its output through the index; the grouping of the queries by video (the backward's reduction of dC reads
+// it) is built beside the branches on the pack stream, off the dependent chain
+static void forward_joined(Ctx& c, const int* vidx) {
     const vsl_handle_s* h = c.h;
     const Plan& p = *c.p;
     const int nj = (int)h->jobs.size(), nfirst = h->jobs_char + h->jobs_first;
@@ -305,9 +307,21 @@ void forward_full(Ctx& c) {
     query_branch(c, emb_pack);
     c.s = c.main;
     c.order(sq, c.main);                   // join
+    if (vidx) {
+        int* const csr = reinterpret_cast<int*>(c.W(p.csr));
+        c.s = split3 ? sp : c.main;
+        LAUNCH("group_csr", launch_group_csr(vidx, p.B, p.NV(), csr, csr + p.csr_members(), c.s));
+        c.s = c.main;
+    }
     if (split3) c.order(sp, c.main);       // the remaining packs (long done)
-    fuse_and_predict(c, CqContext{c.W(p.ve.out), nullptr});
+    fuse_and_predict(c, CqContext{c.W(p.ve.out), vidx});
 }
+
+// vsl_forward
+void forward_full(Ctx& c) { forward_joined(c, nullptr); }
+
+// vsl_forward_shared: N videos, B queries, query b against video video_index[b]
+void forward_shared_train(Ctx& c) { forward_joined(c, c.sh->video_index); }
 
 // vsl_encode_video: the video half alone -- the shared encoder's and VisualProjection's operands, the projection, encoder application 0
 // into the caller's buffer.  One stream: there is no query branch to run beside it.

@@ -65,11 +65,14 @@ enum class PlanKind {
     Train,      // every save + the whole backward (build_train_plan)
     Infer,      // what a forward keeps live, reused by liveness (build_infer_plan)
     Encode,     // vsl_encode_video: B = videos, Lq = Lc = 0 (build_encode_plan)
-    Localize    // vsl_localize: the inference plan without the video pass
+    Localize,   // vsl_localize: the inference plan without the video pass
+    TrainShared // vsl_forward_shared / vsl_backward_shared: the training plan with the video half sized by N videos, everything else by B queries
 };
 
 struct Plan {
     int B, T, Lq, Lc;
+    int N = 0;                          // TrainShared: videos (VisualProjection + encoder application 0 run on N T rows); 0 = one video per sample
+    int NV() const { return N > 0 ? N : B; }       // samples of the video half
     PlanKind kind = PlanKind::Train;
     int64_t vmask = -1;                 // Localize: the (N, T) clip mask gathered to (B, T)
     int64_t pack = -1, vf = -1, E = -1, argpos = -1, qf = -1;
@@ -87,6 +90,8 @@ struct Plan {
     EncTmp tmp[4];                      // one set per encoder application: the applications' backward chains and their
                                         // weight-gradient launches overlap on different streams
     int64_t df2 = -1, df1 = -1, dC = -1, dSr = -1, dSs = -1, dQtot = -1, dvf = -1, dqf = -1, dE = -1, cqP1 = -1, cqP2 = -1, cqP3 = -1, cqP4 = -1, cqP5 = -1;
+    int64_t dCv = -1, csr = -1;         // TrainShared: grad of the (N, T, 128) encoding ; the grouping as ints: start[N + 1], then members[B] from csr + csr_members()
+    int64_t csr_members() const { return ((int64_t)NV() + 1 + 3) & ~int64_t(3); }
     int64_t partial = -1, partial_floats = 0, total = 0;      // the partial arena (offset, extent) ; the workspace's extent
     std::vector<int64_t> part_offs;     // sequence of partial-arena allocations made by the backward
     ReduceSeg* segs_dev = nullptr;
@@ -117,8 +122,11 @@ struct vsl_handle_s {
     const float* sq_src = nullptr;       // the last vsl_backward's per-block sums of squares (Plan::sq_dev), their count, the bucket they describe
     int sq_n = 0;
     const float* sq_grads = nullptr;
-    std::map<std::tuple<int, int, int, int, vsl::PlanKind>, vsl::Plan*> plans;      // key: B, T, Lq, Lc, kind
+    std::map<std::tuple<int, int, int, int, int, vsl::PlanKind>, vsl::Plan*> plans;      // key: B, T, Lq, Lc, N (TrainShared; 0 otherwise), kind
     const void* infer_ws = nullptr;      // workspace the last INFERENCE forward ran in (it holds no saves: vsl_backward on it is refused) ; a training forward in it clears this
+    enum LastFwd { FwdNone, FwdFull, FwdInfer, FwdShared };
+    LastFwd last_fwd = FwdNone;          // what the handle's last forward was: vsl_backward / vsl_backward_shared refuse the other kind's saves, vsl_loss finds its scratch in that plan
+    int shared_N = 0;                    // N of the last vsl_forward_shared
     bool last_infer = false;             // the handle's last forward was an inference forward (vsl_workspace_offset then has nothing to point at)
     uint64_t plan_clock = 0;
     // side streams for the independent chains (query branch, weight gradients) + fork/join events
@@ -187,7 +195,10 @@ struct Ctx {
     const vsl_loss_io* pend_loss = nullptr;   // vsl_io.fused_loss off the dependent chain: launched on the weight-gradient stream behind its first ordering point (loss_on_side)
     int pw_rows = 0;                    // rows per chunk of the NEXT enc_bwd's pointwise weight-gradient jobs (0 = WG_ROWS): the step's last batch, run_backward
     bool defer_w = false;
-    bool inf() const { return p->kind != PlanKind::Train; }
+    const vsl_shared_io* sh = nullptr;  // vsl_forward_shared / vsl_backward_shared: the videos' index and clip mask (the plan is TrainShared then)
+    bool inf() const { return p->kind != PlanKind::Train && p->kind != PlanKind::TrainShared; }
+    // the clip mask of the video half: (N, T) per video in a shared step, vsl_io.v_mask otherwise
+    const float* video_mask() const { return sh ? sh->video_v_mask : io->v_mask; }
     // a tensor only the backward reads: its address in a training forward, nullptr in an inference forward (the kernels then do not store it)
     float* SV(int64_t off) const { return inf() ? nullptr : ws + off; }
     const float* P(int off) const { return io->params + off; }
@@ -265,7 +276,7 @@ void build_packs(vsl_handle_s* h);
 void finish_pack_jobs(vsl_handle_s* h);
 int ensure_opt_state(vsl_handle_s* h);
 // plan.hip
-int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind kind = PlanKind::Train);
+int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind kind = PlanKind::Train, int N = 0);     // N: TrainShared only
 void free_plan(Plan* p);
 // streams.hip
 bool prof_selected(const vsl_handle_s* h, const char* name);
@@ -273,6 +284,7 @@ bool query_chain_is_longer(const Plan& p);      // after the backward's video / 
 // forward.hip
 struct CqContext { const float* C; const int* vidx; };     // the context of CQAttention: C (B, T, 128), or a resident (N, T, 128) encoding read through vidx (B)
 void forward_full(Ctx& c);
+void forward_shared_train(Ctx& c);              // c.sh set, plan TrainShared
 void forward_encode(Ctx& c, float* video_encoding);
 void forward_localize(Ctx& c, CqContext ctx, const float* vmask_nt);
 bool query_fused(const Ctx& c);
@@ -281,6 +293,6 @@ extern std::atomic<unsigned long long> g_rnn_launches;
 unsigned rnn_epoch(long long* gen = nullptr);
 void rnn_granules_fresh(Ctx& c, Plan& p, long long gen);
 // backward.hip
-void run_backward(Ctx& c);
+void run_backward(Ctx& c);                      // the ordinary step, or (plan TrainShared, c.sh set unless dry) the step through a shared encoding
 
 }  // namespace vsl

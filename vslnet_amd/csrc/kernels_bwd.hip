@@ -371,6 +371,7 @@ void launch_cqcat_bwd(const float* dg0, const float* dg1, const float* dg2, cons
 //      and the w4C / w4mlu parameter slabs
 //   D: dQ total (+ WeightedPool / pooled-bias path), w4Q / pool / W2 / bias slabs
 // =========================================================================================================
+template <bool VIDX>
 __global__ __launch_bounds__(256) void k_cq_bwd_a(CqBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int T = a.T, Lq = a.Lq, LQ1 = Lq + 1;
@@ -405,7 +406,7 @@ __global__ __launch_bounds__(256) void k_cq_bwd_a(CqBwdArgs a) {
         for (int r = 0; r < 16; ++r) Dc[acc_row(r, lane) * CATP + t * D + col] = acc[t][r];
     STAMP(2);
     __syncthreads();
-    load_tile128(Gs, a.C + crow * D, t0, TILE_M, T);      // Gs now holds the C tile
+    load_tile128(Gs, a.C + (VIDX ? (size_t)a.vidx[b] * T : crow) * D, t0, TILE_M, T);      // Gs now holds the C tile
     // recompute c2q = S_row Q and q2c = S_row M (:229-230) on the matrix cores: K = Lq, wave = 32 output channels
     f32x16 c2q[1], q2c[1];
     zero_acc(c2q);
@@ -573,6 +574,7 @@ __device__ __forceinline__ void cq_sum_dM(float* dMs, const float* __restrict__ 
     }
 }
 
+template <bool VIDX>
 __global__ __launch_bounds__(256) void k_cq_bwd_b(CqBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int T = a.T, Lq = a.Lq, LQ1 = Lq + 1;
@@ -585,7 +587,7 @@ __global__ __launch_bounds__(256) void k_cq_bwd_b(CqBwdArgs a) {
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, hh = lane >> 5;
     const int b = blockIdx.y, tl = blockIdx.x, t0 = tl * TILE_M, ntile = gridDim.x;
     const size_t crow = (size_t)b * T;
-    load_tile128(Cs, a.C + crow * D, t0, TILE_M, T);
+    load_tile128(Cs, a.C + (VIDX ? (size_t)a.vidx[b] * T : crow) * D, t0, TILE_M, T);
     for (int e = tid; e < TILE_M * Lq; e += 256) {
         const int i = e / Lq, j = e - i * Lq;
         St[i * LQ1 + j] = t0 + i < T ? a.Scol[(crow + t0) * Lq + e] : 0.f;
@@ -655,6 +657,7 @@ __global__ __launch_bounds__(256) void k_cq_bwd_b(CqBwdArgs a) {
         a.P2[(size_t)(b * ntile + tl) * Lq + tid] = sacc;
     }
 }
+template <bool VIDX>
 __global__ __launch_bounds__(256) void k_cq_bwd_c(CqBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int T = a.T, Lq = a.Lq, LQ1 = Lq + 1;
@@ -672,7 +675,7 @@ __global__ __launch_bounds__(256) void k_cq_bwd_c(CqBwdArgs a) {
     const int b = blockIdx.y, tl = blockIdx.x, t0 = tl * TILE_M, ntile = gridDim.x;
     const size_t crow = (size_t)b * T, qrow = (size_t)b * Lq;
     // ---- prologue: tile loads + the cross-tile sums
-    load_tile128(Cs, a.C + crow * D, t0, TILE_M, T);
+    load_tile128(Cs, a.C + (VIDX ? (size_t)a.vidx[b] * T : crow) * D, t0, TILE_M, T);
     cq_sum_dM(dMs, a.P1, b, ntile, Lq);
     if (!big)
     for (int e = tid; e < Lq * D; e += 256) {
@@ -916,14 +919,19 @@ void launch_cq_bwd(const CqBwdArgs& a0, int B, hipStream_t s) {
     const size_t shmA = (size_t)(TILE_M * CATP + TILE_M * LDP + 2 * TILE_M * (Lq + 1) + 72 + npart * TILE_M * (32 * ((Lq + 31) / 32) + 1)) * sizeof(float);
     const size_t shmB = (size_t)(32 * ((Lq + 31) / 32) * LDP + TILE_M * LDP + TILE_M * (Lq + 1) + npart * TILE_M * (32 * ((Lq + 31) / 32) + 1)) * sizeof(float);
     const size_t shmC = (size_t)((Lq > CQ_BIG_LQ ? 1 : 2) * Lq * LDP + 2 * TILE_M * LDP + 2 * TILE_M * (Lq + 1) + 16 + Lq + TILE_M + 4 * D) * sizeof(float);
-    static size_t okA = 0, okB = 0, okC = 0;
-    ensure_dynamic_lds((const void*)k_cq_bwd_a, shmA, okA, "k_cq_bwd_a");
-    ensure_dynamic_lds((const void*)k_cq_bwd_b, shmB, okB, "k_cq_bwd_b");
-    ensure_dynamic_lds((const void*)k_cq_bwd_c, shmC, okC, "k_cq_bwd_c");
-    VSL_LAUNCH(k_cq_bwd_a, dim3(ntile, B), dim3(256), shmA, s, a);
-    { static int left = 2; if (stamps::enabled()) stamps::report("cq_bwd_a: load | gemm512 | Dc store | C load + c2q/q2c | product rule | dS_row + partials | sync | softmax bwd", 8, s, left); }
-    VSL_LAUNCH(k_cq_bwd_b, dim3(ntile, B), dim3(256), shmB, s, a);
-    VSL_LAUNCH(k_cq_bwd_c, dim3(ntile, B), dim3(256), shmC, s, a);
+    // VIDX (a.vidx != nullptr, vsl_backward_shared): the reads of C go through the index, one scalar load per workgroup, as in the forward kernels
+    auto go = [&](auto ka, auto kb, auto kc, size_t (&ok)[3], const char* na, const char* nb, const char* nc) {
+        ensure_dynamic_lds((const void*)ka, shmA, ok[0], na);
+        ensure_dynamic_lds((const void*)kb, shmB, ok[1], nb);
+        ensure_dynamic_lds((const void*)kc, shmC, ok[2], nc);
+        VSL_LAUNCH(ka, dim3(ntile, B), dim3(256), shmA, s, a);
+        { static int left = 2; if (stamps::enabled()) stamps::report("cq_bwd_a: load | gemm512 | Dc store | C load + c2q/q2c | product rule | dS_row + partials | sync | softmax bwd", 8, s, left); }
+        VSL_LAUNCH(kb, dim3(ntile, B), dim3(256), shmB, s, a);
+        VSL_LAUNCH(kc, dim3(ntile, B), dim3(256), shmC, s, a);
+    };
+    static size_t ok[3] = {0, 0, 0}, okv[3] = {0, 0, 0};
+    if (a.vidx) go(k_cq_bwd_a<true>, k_cq_bwd_b<true>, k_cq_bwd_c<true>, okv, "k_cq_bwd_a<true>", "k_cq_bwd_b<true>", "k_cq_bwd_c<true>");
+    else go(k_cq_bwd_a<false>, k_cq_bwd_b<false>, k_cq_bwd_c<false>, ok, "k_cq_bwd_a", "k_cq_bwd_b", "k_cq_bwd_c");
 }
 // the per-sample tail (dQ, pooled-query path): nothing on the video side reads its outputs, so it runs on the query stream
 void launch_cq_bwd_query(const CqBwdArgs& a0, int B, hipStream_t s) {

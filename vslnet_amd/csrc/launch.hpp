@@ -394,9 +394,14 @@ struct CqBwdArgs {
     float *p_W2;                                         // [B][128][128] for Wcat[:, 128:]
     int T, Lq, b_off, ntile;
     Drop dc, dq;
+    const int* vidx;      // nullable (B), device: C is the (N, T, 128) encoding of a shared-video training step and sample b reads video vidx[b]; everything written stays at sample b
 };
 void launch_cq_bwd(const CqBwdArgs& a, int B, hipStream_t s);          // kernels a, b, c: dC final, dQ partials
 void launch_cq_bwd_query(const CqBwdArgs& a, int B, hipStream_t s);    // kernel d: dQ + pooled-query parameters
+// training through a shared video encoding (kernels_shared.hip): the CSR of the queries of each video (start[N + 1], members[B] ascending within a
+// video) from the device index, and dCv (N, T, 128) = the sum of dC (B, T, 128) over each video's queries in member order
+void launch_group_csr(const int* vidx, int B, int N, int* start, int* members, hipStream_t s);
+void launch_group_sum(const float* dC, const int* start, const int* members, float* dCv, int N, int T, hipStream_t s);
 // the backward of that launch (autograd of the same lines) + the Embedding linear's data gradient; per-SAMPLE partial slabs
 struct QueryBwdArgs {
     const float* dout;             // (Rq,128) grad wrt the encoder output

@@ -141,17 +141,23 @@ int build_reduce_tables(vsl_handle_s* h, Plan* p, const std::vector<SlabRec>& re
 
 // The training plan: every tensor the backward reads is saved, every backward temporary has its own buffer, and the partial arena behind them is
 // laid out by a dry run of the backward.
-int build_train_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) {
+// N > 0 (PlanKind::TrainShared): the video half -- VisualProjection's output, encoder application 0's saves and backward temporaries, dvf, and
+// through the dry run its partial slabs -- is sized by N T rows, everything else by B; added: dCv (N, T, 128) and the grouping's CSR (N + 1 + B ints).
+// The 2 GiB / 32-bit-offset limits apply to N T 128 and to B T 128 separately.
+int build_train_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, int N = 0) {
     if (int rc = check_shape(h, B, T, Lq, Lc)) return rc;
+    if (N > 0)
+        if (int rc = check_video_shape(h, N, T, " (N = videos of the shared step)")) return rc;
     const vsl_config& cf = h->cfg;
     Plan* p = new Plan();
     p->B = B; p->T = T; p->Lq = Lq; p->Lc = Lc;
-    const int64_t R = (int64_t)B * T, Rq = (int64_t)B * Lq;
+    if (N > 0) { p->N = N; p->kind = PlanKind::TrainShared; }
+    const int64_t R = (int64_t)B * T, Rq = (int64_t)B * Lq, Rv = (int64_t)p->NV() * T;
     const int H = cf.num_heads, EW = cf.word_dim + 100;
     Bump al;
     p->pack = al(h->pack_floats);
-    p->vf = al(R * D); p->E = al(Rq * EW); p->argpos = al((Rq * 100 + 3) / 4); p->qf = al(Rq * D);
-    plan_encoder(al, p->ve, B, T, H); plan_encoder(al, p->qe, B, Lq, H);
+    p->vf = al(Rv * D); p->E = al(Rq * EW); p->argpos = al((Rq * 100 + 3) / 4); p->qf = al(Rq * D);
+    plan_encoder(al, p->ve, p->NV(), T, H); plan_encoder(al, p->qe, B, Lq, H);
     const bool rnn = cf.predictor == 0;
     if (rnn) {
         p->p1.R = p->p2.R = (int)R; p->p1.L = p->p2.L = T;
@@ -176,7 +182,7 @@ int build_train_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) 
     p->gz_s = al(R * D); p->gz_e = al(R * D); p->dfeat_s = al(R * D); p->dfeat_e = al(R * D);
     p->dxh_s = al(R * D); p->dxh_e = al(R * D); p->g_s1 = al(R * D); p->g_gated = al(R * D);
     for (int ap = 0; ap < (rnn ? 2 : 4); ++ap) {
-        const int64_t Ra = ap == 1 ? Rq : R;
+        const int64_t Ra = ap == 1 ? Rq : ap == 0 ? Rv : R;
         EncTmp& t = p->tmp[ap];
         t.dr = al(Ra * D); t.dq = al(Ra * D * attn_dq_slabs(ap == 1 ? Lq : T)); t.dk = al(Ra * D); t.dv = al(Ra * D);
         t.go = al(Ra * D);
@@ -189,7 +195,8 @@ int build_train_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out) 
         p->cqP1 = al((int64_t)B * nt * 2 * Lq * D); p->cqP2 = al((int64_t)B * nt * Lq); p->cqP3 = al((int64_t)B * nt * Lq);
         p->cqP4 = al((int64_t)B * nt * Lq * D); p->cqP5 = al((int64_t)B * nt * D);
     }
-    p->dSr = al(R * Lq); p->dSs = al(R * Lq); p->dQtot = al(Rq * D); p->dvf = al(R * D); p->dqf = al(Rq * D); p->dE = al(Rq * EW);
+    p->dSr = al(R * Lq); p->dSs = al(R * Lq); p->dQtot = al(Rq * D); p->dvf = al(Rv * D); p->dqf = al(Rq * D); p->dE = al(Rq * EW);
+    if (N > 0) { p->dCv = al(Rv * D); p->csr = al(p->csr_members() + B); }
     p->partial = al(0);
     // dry-run the backward to lay out the partial arena and collect the reduction table
     std::vector<SlabRec> recs;
@@ -293,14 +300,17 @@ void free_plan(Plan* p) {
 // shape a realistic run sees (64 entries thrashed under shuffled real-data batches) and evicts the least recently used one
 // beyond that.  (A forward and its backward use the same shape back to back, so a live plan is never evicted.)
 constexpr size_t MAX_PLANS = 2048;
-int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind kind) {
-    auto key = std::make_tuple(B, T, Lq, Lc, kind);
+int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind kind, int N) {
+    if (kind != PlanKind::TrainShared) N = 0;
+    else if (N < 1) return fail("shared training step: N=%d videos (at least one)", N);
+    auto key = std::make_tuple(B, T, Lq, Lc, N, kind);
     auto it = h->plans.find(key);
     if (it != h->plans.end()) { it->second->last_use = ++h->plan_clock; *out = it->second; return 0; }
     Plan* p = nullptr;
     int rc = 0;
     switch (kind) {
         case PlanKind::Train: rc = build_train_plan(h, B, T, Lq, Lc, &p); break;
+        case PlanKind::TrainShared: rc = build_train_plan(h, B, T, Lq, Lc, &p, N); break;
         case PlanKind::Infer:
         case PlanKind::Localize: rc = build_infer_plan(h, B, T, Lq, Lc, &p, kind); break;
         case PlanKind::Encode: rc = build_encode_plan(h, B, T, &p); break;

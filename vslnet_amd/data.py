@@ -227,8 +227,9 @@ class ResidentSplit:
             return np.arange(n, dtype=np.int64)
         return torch.randperm(n, generator=self.generator).numpy()         # shuffle=True of data_loader_t7.py:86
 
-    def _gather(self, idx_dev, T, Lq, Lc):
-        vf = torch.index_select(self.feats[:, :T], 0, self.d_vid[idx_dev])
+    def _gather(self, idx_dev, T, Lq, Lc, videos=None):
+        """`videos` (grouped order): the records whose videos make the rows of the feature block, instead of one row per record"""
+        vf = torch.index_select(self.feats[:, :T], 0, self.d_vid[idx_dev if videos is None else videos])
         out = [vf, torch.index_select(self.d_words[:, :Lq], 0, idx_dev), torch.index_select(self.d_chars[:, :Lq, :Lc], 0, idx_dev)]
         if self.train:
             out += [self.d_s[idx_dev], self.d_e[idx_dev], torch.index_select(self.d_h[:, :T], 0, idx_dev)]
@@ -250,8 +251,35 @@ class ResidentSplit:
             full[a:a + step] = part.encoding
         return VideoEncoding(full, v_mask, owner=part.owner, epoch=part.epoch)
 
-    def shards(self, rank=0, world=1, order=None):
-        """One dict per GLOBAL batch: this rank's rows on the device + what the losses need about the whole batch."""
+    def _grouped_order(self, K):
+        """The grouped order of shards(queries_per_video=K): each video's records are shuffled and cut into groups of at most K, the groups are
+        shuffled and concatenated.  -> (order, group id of every position).  Every record appears once; K = 1 is one record per group."""
+        by_vid = {}
+        for i, v in enumerate(self.vid_of):
+            by_vid.setdefault(int(v), []).append(i)
+        groups = []
+        for v in sorted(by_vid):
+            recs = np.asarray(by_vid[v], dtype=np.int64)
+            if self.train:
+                recs = recs[torch.randperm(len(recs), generator=self.generator).numpy()]
+            groups += [recs[a:a + K] for a in range(0, len(recs), K)]
+        pick = torch.randperm(len(groups), generator=self.generator).numpy() if self.train else np.arange(len(groups))
+        order = np.concatenate([groups[g] for g in pick])
+        gid = np.concatenate([np.full(len(groups[g]), k, dtype=np.int64) for k, g in enumerate(pick)])
+        return order, gid
+
+    def shards(self, rank=0, world=1, order=None, queries_per_video=None):
+        """One dict per GLOBAL batch: this rank's rows on the device + what the losses need about the whole batch.
+        queries_per_video=K (single process): the GROUPED order for the training step through a shared encoding (Engine.forward_shared) -- each
+        video's records shuffled and cut into groups of at most K, the groups shuffled and concatenated up to batch_size (a group that crosses a
+        batch boundary continues as a smaller group of the next batch).  The dict then holds one row of `vfeats` (N, T, Dv) and `video_v_mask` (N, T)
+        per group and `video_index` (B, int32, device) = the row of each query; `v_mask` stays the (B, T) per-query mask.  Every record appears
+        once per epoch; K = 1 gives N = B, today's content."""
+        if queries_per_video is not None:
+            if world != 1 or order is not None:
+                raise ValueError('shards(queries_per_video=...) is the single-process grouped order: data parallel through a shared encoding is not supported')
+            yield from self._grouped_shards(max(1, min(int(queries_per_video), self.batch_size)))
+            return
         order = self._order(order)
         d_order = torch.from_numpy(order).to(self.device)                  # the only per-epoch upload
         bs = self.batch_size
@@ -270,6 +298,28 @@ class ResidentSplit:
                  'word_ids': g[1], 'char_ids': g[2]}
             if self.train:
                 b.update(s_labels=g[3], e_labels=g[4], h_labels=g[5])
+            yield b
+
+    def _grouped_shards(self, K):
+        order, gid = self._grouped_order(K)
+        d_order = torch.from_numpy(order).to(self.device)
+        bs = self.batch_size
+        for a in range(0, len(order), bs):
+            idx, g = order[a:a + bs], gid[a:a + bs]
+            lens = self.lens[idx]
+            T, Lq, Lc = int(lens.max()), int(self.nwords[idx].max()), int(self.nchars[idx].max())
+            first = np.concatenate([[True], g[1:] != g[:-1]])                 # first query of each group: the rows of the video tensors
+            vrow = np.cumsum(first) - 1
+            idx_dev = d_order[a:a + bs]
+            first_dev = idx_dev[torch.from_numpy(np.flatnonzero(first)).to(self.device)]
+            out = self._gather(idx_dev, T, Lq, Lc, videos=first_dev)
+            l_dev = self.d_lens[idx_dev]
+            ar = torch.arange(T, device=self.device)[None, :]
+            b = {'records': [self.records[i] for i in idx], 'lens_global': lens, 'row0': 0, 'vfeats': out[0], 'v_mask': (ar < l_dev[:, None]).float(),
+                 'video_v_mask': (ar < self.d_lens[first_dev][:, None]).float(), 'video_index': torch.from_numpy(vrow.astype(np.int32)).to(self.device),
+                 'word_ids': out[1], 'char_ids': out[2]}
+            if self.train:
+                b.update(s_labels=out[3], e_labels=out[4], h_labels=out[5])
             yield b
 
     def __iter__(self):

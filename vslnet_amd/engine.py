@@ -50,6 +50,10 @@ class vsl_localize_io(C.Structure):
                 ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('workspace', C.c_void_p)]
 
 
+class vsl_shared_io(C.Structure):
+    _fields_ = [('N', C.c_int32), ('video_index', C.c_void_p), ('video_v_mask', C.c_void_p)]
+
+
 class VideoEncoding:
     """What Engine.encode_video returns and Engine.localize reads: the shared feature encoder's output for N videos padded to T clips, and their
     clip masks.  It belongs to its T and to the parameter values it was computed with (include/vslnet_hip.h).  `owner` / `epoch` are set by
@@ -86,7 +90,8 @@ ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count',
                'vsl_workspace_floats', 'vsl_forward', 'vsl_loss', 'vsl_backward', 'vsl_extract_index',
                'vsl_adamw_step', 'vsl_workspace_offset', 'vsl_profile_select', 'vsl_profile_read', 'vsl_profile_launch', 'vsl_abi_version',
                'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats',
-               'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize']
+               'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize',
+               'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -136,6 +141,12 @@ def load_library():
         lib.vsl_localize_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
         lib.vsl_encode_video.argtypes = [C.c_void_p, C.POINTER(vsl_encode_io), C.c_void_p]
         lib.vsl_localize.argtypes = [C.c_void_p, C.POINTER(vsl_localize_io), C.c_void_p]
+    if hasattr(lib, 'vsl_forward_shared'):                   # (likewise: training through a shared video encoding)
+        lib.vsl_shared_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        lib.vsl_forward_shared.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
+        lib.vsl_backward_shared.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
+        lib.vsl_shared_workspace_offset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
+        lib.vsl_shared_workspace_offset.restype = C.c_int64
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
     lib.vsl_loss.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_loss_io), C.c_void_p]
     lib.vsl_backward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -214,6 +225,8 @@ class Engine:
         self.use_inference = True
         # vsl_encode_video / vsl_localize: one encoding per video, many queries against it.  An older build has neither; both methods then raise
         self.has_shared_video = hasattr(self.lib, 'vsl_encode_video') and hasattr(self.lib, 'vsl_localize')
+        # vsl_forward_shared / vsl_backward_shared: a training step over N videos and B queries.  An older build has neither; forward_shared then raises
+        self.has_shared_train = hasattr(self.lib, 'vsl_forward_shared') and hasattr(self.lib, 'vsl_backward_shared')
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -243,6 +256,7 @@ class Engine:
             self.layout.append((name.value.decode(), off.value, num.value, tuple(dims[j] for j in range(nd.value))))
         self._ws, self._grown = None, False
         self._last = None
+        self._last_shared = None                            # the vsl_shared_io of the last forward when that was forward_shared (loss / backward / ws_view dispatch on it)
         self._pending_loss = None
 
     def __del__(self):
@@ -302,13 +316,25 @@ class Engine:
             self._call(self.lib.vsl_localize_workspace_floats(self.h, B, T, Lq, Lc, C.byref(n)))
         return int(n.value)
 
+    def shared_workspace_floats(self, B, N, T, Lq, Lc):
+        """Floats a shared training step of B queries over N videos needs (the training plan with the video half sized by N, + dCv and the grouping)."""
+        self._need_shared_train()
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._call(self.lib.vsl_shared_workspace_floats(self.h, B, N, T, Lq, Lc, C.byref(n)))
+        return int(n.value)
+
+    def _need_shared_train(self):
+        if not self.has_shared_train:
+            raise VslError('the loaded library has no shared-encoding training step (vsl_forward_shared / vsl_backward_shared are missing)')
+
     def _grow_ws(self, n):
         """The one shared workspace (see workspace()), grown to at least `n` floats."""
         if self._ws is None or self._ws.numel() < n:
             # drop EVERY reference to the old one first (the last forward's io / keep-alive tuple hold it too): old and new must not
             # coexist at the growth peak beside an HBM-resident dataset (ADVICE r2)
             self._ws = None
-            self._last = self._last_ws = self._keep = None
+            self._last = self._last_ws = self._keep = self._last_shared = None
             self._ws = torch.empty(int(n * 1.25) if self._grown else n, dtype=torch.float32, device=self.device)
             self._grown = True
         return self._ws
@@ -329,7 +355,10 @@ class Engine:
         io = self._last
         if io is not None and io.inference:
             raise VslError('ws_view(%r): the last forward was an inference forward (or encode_video / localize), which saves nothing' % (name,))
-        off = self.lib.vsl_workspace_offset(self.h, io.B, io.T, io.Lq, io.Lc, name.encode())
+        if self._last_shared is not None:                   # the plan of a shared step: the video half's tensors have N T rows
+            off = self.lib.vsl_shared_workspace_offset(self.h, io.B, self._last_shared.N, io.T, io.Lq, io.Lc, name.encode())
+        else:
+            off = self.lib.vsl_workspace_offset(self.h, io.B, io.T, io.Lq, io.Lc, name.encode())
         if off < 0:
             raise KeyError(name)
         n = 1
@@ -381,10 +410,65 @@ class Engine:
         io.inference = int(bool(inference))
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._call(self.lib.vsl_forward(self.h, C.byref(io), stream))
-        self._last, self._last_ws = io, ws              # (io.inference marks it: backward() and ws_view() raise on an inference forward)
+        self._last, self._last_ws, self._last_shared = io, ws, None      # (io.inference marks it: backward() and ws_view() raise on an inference forward)
         self.inference_forwards += int(bool(inference))
         # keep every tensor the io struct points to alive until the backward
         self._keep = (flat, pad_vec, glove_vec, word_ids, char_ids, vfeats, v_mask, q_mask, out, ws)
+        return out[0], out[1], out[2]
+
+    # ---- training through a shared video encoding: N videos, B queries per step -----------------------------
+    def forward_shared(self, flat, pad_vec, glove_vec, word_ids, char_ids, video_features, video_v_mask, q_mask, video_index, training=True, seed=0):
+        """forward() over N videos and B queries, query b paired with video video_index[b]: VisualProjection and the video pass of the feature
+        encoder run on the (N, T, video_feature_dim) features once, everything else on B samples.  -> (h_score, start_logits, end_logits), each (B, T).
+        loss() and backward() then work as after forward() (backward() runs the video half's backward on N T rows and sums the encoding's gradient
+        over each video's queries in ascending b: deterministic).  The dropout of the video half draws ONE mask per video (include/vslnet_hip.h): at
+        drop_rate 0 the step is the ordinary one on the replicated batch, otherwise a different but equally valid stochastic estimate.
+        `video_v_mask` is the (N, T) per-video mask; the (B, T) per-query mask is built here.  `video_index` as a list / numpy array / CPU tensor
+        is range-checked and uploaded as int32; a DEVICE tensor (int32 or int64) is trusted.  `training=False`: the saved evaluation path."""
+        self._need_shared_train()
+        if video_features.dim() != 3 or video_features.shape[0] < 1:
+            raise ValueError('forward_shared: video_features must be (N, T, video_feature_dim) with N >= 1 videos, got %s' % (tuple(video_features.shape),))
+        N, T, Dv = video_features.shape
+        bf16 = video_features.dtype == torch.bfloat16
+        B, Lq, Lc = char_ids.shape
+        if isinstance(video_index, torch.Tensor) and video_index.is_cuda:
+            vidx = video_index.to(torch.int32).contiguous()
+        else:
+            host = torch.as_tensor(video_index).to(torch.int64).reshape(-1)
+            if host.numel() and (int(host.min()) < 0 or int(host.max()) >= N):
+                raise ValueError('forward_shared: video_index out of range: values in [%d, %d], the batch holds %d videos' % (int(host.min()), int(host.max()), N))
+            vidx = host.to(torch.int32).to(self.device)
+        _chk(vidx, torch.int32, (B,), 'video_index')
+        _chk(flat, torch.float32, (self.param_floats,), 'params')
+        _chk(word_ids, torch.int64, (B, Lq), 'word_ids')
+        _chk(char_ids, torch.int64, (B, Lq, Lc), 'char_ids')
+        _chk(video_features, torch.bfloat16 if bf16 else torch.float32, (N, T, self.cfg.video_feature_dim), 'video_features')
+        _chk(video_v_mask, torch.float32, (N, T), 'video_v_mask')
+        _chk(q_mask, torch.float32, (B, Lq), 'q_mask')
+        if self.cfg.word_table:
+            pad_vec = glove_vec = None
+        else:
+            _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
+            _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
+        self._flush_loss()
+        ws = self._grow_ws(self.shared_workspace_floats(B, N, T, Lq, Lc))
+        v_mask = video_v_mask.index_select(0, vidx.long()).contiguous()       # the (B, T) per-query mask
+        out = torch.empty(3, B, T, dtype=torch.float32, device=self.device)
+        io = vsl_io()
+        io.B, io.T, io.Lq, io.Lc = B, T, Lq, Lc
+        io.params, io.pad_vec, io.glove_vec = _ptr(flat), _ptr(pad_vec), _ptr(glove_vec)
+        io.word_ids, io.char_ids = _ptr(word_ids), _ptr(char_ids)
+        io.video_features, io.video_features_bf16 = (None, _ptr(video_features)) if bf16 else (_ptr(video_features), None)
+        io.v_mask, io.q_mask = _ptr(v_mask), _ptr(q_mask)
+        io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
+        io.workspace = _ptr(ws)
+        io.training, io.seed = int(bool(training)), int(seed) & 0xFFFFFFFFFFFFFFFF
+        sh = vsl_shared_io()
+        sh.N, sh.video_index, sh.video_v_mask = N, _ptr(vidx), _ptr(video_v_mask)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_forward_shared(self.h, C.byref(io), C.byref(sh), stream))
+        self._last, self._last_ws, self._last_shared = io, ws, sh
+        self._keep = (flat, pad_vec, glove_vec, word_ids, char_ids, video_features, video_v_mask, v_mask, vidx, q_mask, out, ws)
         return out[0], out[1], out[2]
 
     # ---- one encoding per video, many queries against it (evaluation only) ---------------------------------
@@ -393,7 +477,7 @@ class Engine:
         ws_view() raise until the next saved-path forward (a marker in place of that forward's io, as after forward(inference=True))."""
         mark = vsl_io()
         mark.inference = 1
-        self._last, self._last_ws, self._keep = mark, None, keep
+        self._last, self._last_ws, self._keep, self._last_shared = mark, None, keep, None
 
     def encode_video(self, flat, vfeats, v_mask):
         """VisualProjection + the video pass of the shared feature encoder for N videos, once: -> VideoEncoding (encoding (N, T, 128), v_mask (N, T)).
@@ -522,7 +606,7 @@ class Engine:
         return int(self.lib.vsl_early_grad_offset(self.h))
 
     def backward(self, d_h, d_sl, d_el, grads, early_event=None, fused_step=None):
-        """Backward of the LAST forward; writes the flat gradient bucket `grads` (same layout as the params).
+        """Backward of the LAST forward (forward() or forward_shared()); writes the flat gradient bucket `grads` (same layout as the params).
         `early_event` (torch.cuda.Event, data parallel): recorded by the library as soon as grads[early_grad_offset():] is final.
         `fused_step` (single process; `FlatAdamW.fused_step()`): dict(flat, exp_avg, exp_avg_sq, lr, step, betas, eps, weight_decay, clip_norm,
         hf_order[, grad_norm_out]) -- this optimizer step is applied inside the backward's last launch (final reduction + clip + AdamW in one
@@ -546,6 +630,8 @@ class Engine:
         _chk(grads, torch.float32, (self.param_floats,), 'grads')
         io.d_h_score, io.d_start_logits, io.d_end_logits, io.grads = _ptr(d_h), _ptr(d_sl), _ptr(d_el), _ptr(grads)
         io.early_grads_event = None
+        if early_event is not None and self._last_shared is not None:
+            raise ValueError('early_event belongs to the data-parallel exchange, which a shared-encoding step does not support')
         if early_event is not None:
             early_event.record(torch.cuda.current_stream(self.device))     # creates the handle lazily; harmless: recorded again by the library
             io.early_grads_event = C.c_void_p(early_event.cuda_event)
@@ -569,7 +655,10 @@ class Engine:
             io.fused_step = C.cast(C.pointer(fs), C.c_void_p)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         try:
-            self._call(self.lib.vsl_backward(self.h, C.byref(io), stream))
+            if self._last_shared is not None:
+                self._call(self.lib.vsl_backward_shared(self.h, C.byref(io), C.byref(self._last_shared), stream))
+            else:
+                self._call(self.lib.vsl_backward(self.h, C.byref(io), stream))
         finally:
             io.fused_step = io.fused_loss = None          # (`fs` / the loss struct live until here; the library reads them during the call only)
         return grads

@@ -62,6 +62,33 @@ class _ForwardFn(torch.autograd.Function):
         return (None,) * 6 + tuple(views[n] for n in model._flat_names)
 
 
+class _SharedForwardFn(torch.autograd.Function):
+    """VSLNet.forward_shared: N videos, B queries, one encoding per video (Engine.forward_shared); the backward is the engine's own dispatch."""
+
+    @staticmethod
+    def forward(ctx, model, word_ids, char_ids, vfeats, v_mask, q_mask, video_index, *params):
+        eng = model._engine_for(vfeats.device)
+        model._step += 1
+        we = model.embedding_net.word_emb
+        vf = vfeats.contiguous()
+        h, sl, el = eng.forward_shared(model._flat, we.pad_vec.data if we.is_pretrained else None, we.glove_vec.data if we.is_pretrained else None,
+                                       word_ids.contiguous(), char_ids.contiguous(), vf if vf.dtype == torch.bfloat16 else vf.float(),
+                                       v_mask.contiguous().float(), q_mask.contiguous().float(), video_index, training=model.training,
+                                       seed=(model._seed << 20) + model._step)
+        ctx.model, ctx.token = model, model._step
+        return h, sl, el
+
+    @staticmethod
+    def backward(ctx, d_h, d_sl, d_el):
+        model = ctx.model
+        if ctx.token != model._step:
+            raise RuntimeError('VSLNet.backward: another forward ran since this graph was built; the HIP engine keeps the '
+                               'saved activations of the latest forward only')
+        g = model._engine.backward(d_h.contiguous(), d_sl.contiguous(), d_el.contiguous(), torch.empty_like(model._flat_grad))
+        views = model._engine.views(g)
+        return (None,) * 7 + tuple(views[n] for n in model._flat_names)
+
+
 class _LossFn(torch.autograd.Function):
     """compute_loss / compute_highlight_loss through the fused loss kernel; `which` selects the returned term."""
 
@@ -190,6 +217,19 @@ class VSLNet(nn.Module):
                                word_ids.contiguous(), char_ids.contiguous(), video_features.contiguous().float(), v_mask.contiguous().float(),
                                q_mask.contiguous().float(), inference=True)
         return _ForwardFn.apply(self, word_ids, char_ids, video_features, v_mask, q_mask, *self._flat_params)
+
+    # ---- training through a shared video encoding (no reference counterpart: the reference runs the video half once per sample) ----
+    def forward_shared(self, word_ids, char_ids, video_features, v_mask, q_mask, video_index):
+        """forward() over N videos and B queries: `video_features` (N, T, video_feature_dim) and `v_mask` (N, T) per VIDEO, the query tensors per
+        query, query b paired with video video_index[b] (list / numpy / CPU tensor: range-checked; device tensor: trusted).  VisualProjection and
+        the video pass of the feature encoder run once per video, forward and backward; -> (h_score, start_logits, end_logits), each (B, T), for
+        compute_loss / compute_highlight_loss (with the per-query mask v_mask[video_index]) and .backward().  The video half's dropout draws one
+        mask per video: at drop_rate 0 this is forward() on the replicated batch, otherwise a different, equally valid stochastic estimate
+        (DESIGN section 7).  A training / grad-enabled call: evaluation that is never differentiated goes through encode_video + localize."""
+        if not self.training and not torch.is_grad_enabled():
+            raise RuntimeError('VSLNet.forward_shared is the training step through a shared encoding; under eval() + no_grad() use encode_video + localize')
+        self._engine_for(video_features.device)
+        return _SharedForwardFn.apply(self, word_ids, char_ids, video_features, v_mask, q_mask, video_index, *self._flat_params)
 
     # ---- one encoding per video, many queries against it (no reference counterpart: the reference encodes the video once per query) ----
     def _shared_video_mode(self, what):
