@@ -22,7 +22,7 @@ def predicted_routes(B, T, Lq, num_heads=8, predictor='transformer', lazy=True):
     """-> (labels the step launches among ROUTE_LABELS, whether the loss seeds are computed inside the heads' backward), from the predicates:
     query_fused_ok (kernels_query.hip), enc_fwd's attention choice and attn_block_fwd_hosts_heads (forward.hip, launch.hpp), cq_col_folds
     (kernels_fwd.hip), convblock_bwd_hosts_qkv + attn_bwd_dq_slabs (kernels_enc.hip, kernels_attn_h16.hip), rnn_fused_ok (kernels_lstm.hip) and
-    run_backward's seeds_inline (backward.hip)."""
+    loss_seeds' seeds_inline (backward.hip)."""
     h8 = num_heads == 8
     query_local = h8 and Lq <= 32
     enc_L = [T] + ([] if query_local else [Lq]) + ([T, T] if predictor == 'transformer' else [])      # the encoder applications' lengths

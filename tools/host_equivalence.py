@@ -11,8 +11,9 @@
     after the fused optimizer step of that backward.
 Cases: every row of tests/test_dispatch_boundaries.py::ROWS as one training step (dropout on, fixed seed, fused optimizer step) and as an
 inference forward; the smallest shapes that reach the attention kernels those rows do not (1 and 2 heads with the element hash, the pair hash
-over two dQ slabs and query-major dQ; 4 and 16 heads with query-major dQ); encode_video + localize with a repeated and permuted video index, both predictors, fp32 and bf16 features; the headline
-bench shape; one B > 80 rnn shape (chunked LSTM launches over three streams).  The whole set runs three times, each in a fresh child process
+over two dQ slabs and query-major dQ; 4 and 16 heads with query-major dQ); encode_video + localize with a repeated and permuted video index, both predictors, fp32 and bf16 features;
+one training step through a shared encoding (Engine.forward_shared) with the same index, both predictors, at the two shapes that reach the
+sample-local and the row-tile query path and the folded and the unfolded CQ column; the headline bench shape; one B > 80 rnn shape (chunked LSTM launches over three streams).  The whole set runs three times, each in a fresh child process
 (the switches are read once per process): default, VSL_MULTI_STREAM=0, and every fusion switch off.  The children run one after the other,
 each under its own time limit; the tool stops at the first one that does not exit with 0."""
 import hashlib
@@ -35,6 +36,7 @@ OFFSET_NAMES = ['video_affine', 'embedding_net', 'emb_concat', 'venc', 'qenc', '
                 'd_gated_enc', 'd_gated_hs', 'd_gated_he', 'd_venc', 'd_qenc', 'd_video_affine', 'd_embedding_net', 'd_pred_s', 'd_pred_s_head',
                 'd_cq_concat', 'd_cq_attention', 'd_emb_concat', 'hid_s', 'hid_e', 'no_such_name'] + \
                ['relu_%s_%d' % (e, i) for e in ENC for i in range(4)] + ['%s_y%d' % (e, i) for e in ENC for i in range(4)] + ['%s_x0' % e for e in ENC]
+SHARED_OFFSET_NAMES = ['d_venc_video', 'group_start', 'group_members']      # vsl_shared_workspace_offset only
 STEP_SEED = (5 << 33) + 2024
 # (B, T, Lq) beyond test_dispatch_boundaries.ROWS: T = 129 element hash, 257 pair hash + two dQ slabs, 1025 query-major dQ (the DQ = false instantiations)
 ATTN_SHAPES_LONG = ((1, 1025, 9),)
@@ -128,6 +130,29 @@ def shared_video(cfgkw, N, B, T, Lq, bf16, Lc=6):
     return rec
 
 
+def shared_train(cfgkw, N, B, T, Lq, Lc=6):
+    """One training step through a shared encoding: dropout on, fixed seed, lazy loss, the fused optimizer step."""
+    import torch
+    eng, flat, pad, glove, b, d = setup(cfgkw, B, T, Lq, Lc)
+    idx = [(7 * i + 3) % N for i in range(B)]          # repeated and permuted
+    vmask = d['v_mask'][:N].contiguous()
+    rec = {}
+    eng.profile_select('*')
+    h, sl, el = eng.forward_shared(flat, pad, glove, d['word_ids'], d['char_ids'], d['vfeats'][:N].contiguous(), vmask, d['q_mask'], idx, training=True, seed=STEP_SEED)
+    rec['shared_workspace_floats'] = eng.shared_workspace_floats(B, N, T, Lq, Lc)
+    rec['offsets'] = {n: int(eng.lib.vsl_shared_workspace_offset(eng.h, B, N, T, Lq, Lc, n.encode())) for n in OFFSET_NAMES + SHARED_OFFSET_NAMES}
+    losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0, inv_batch=1.0 / B, mask_sum=float(b['v_mask'][:N][idx].sum()), lazy=True)
+    m, v = torch.zeros_like(flat), torch.zeros_like(flat)
+    g = eng.backward(d_h, d_sl, d_el, eng.new_flat(), fused_step=dict(flat=flat, exp_avg=m, exp_avg_sq=v, lr=1e-3, step=1, clip_norm=1.0))
+    si, ei = eng.extract_index(sl, el)
+    torch.cuda.synchronize()
+    rec['train_ledger'] = ledger(eng)
+    eng.profile_select(None)
+    rec['train'] = {'h_score': sha(h), 'start_logits': sha(sl), 'end_logits': sha(el), 'start_index': sha(si), 'end_index': sha(ei), 'losses': sha(losses),
+                    'seeds': sha(torch.stack([d_h, d_sl, d_el])), 'grads': sha(g), 'params_after_step': sha(flat), 'exp_avg': sha(m), 'exp_avg_sq': sha(v)}
+    return rec
+
+
 def child(out_path):
     from tests.test_dispatch_boundaries import ROWS
     cases = {}
@@ -145,6 +170,9 @@ def child(out_path):
             for (N, B, T, Lq) in ((3, 8, 64, 9), (2, 5, 160, 33)):
                 cases['shared:%s-%s-N%d-B%d-T%d-Lq%d' % (pred, 'bf16' if bf16 else 'fp32', N, B, T, Lq)] = \
                     shared_video(dict(video_feature_dim=64, predictor=pred), N, B, T, Lq, bf16)
+    for pred in ('transformer', 'rnn'):
+        for (N, B, T, Lq) in ((3, 8, 64, 9), (2, 5, 160, 33)):
+            cases['shared_train:%s-N%d-B%d-T%d-Lq%d' % (pred, N, B, T, Lq)] = shared_train(dict(video_feature_dim=64, predictor=pred), N, B, T, Lq)
     with open(out_path, 'w') as f:
         json.dump(cases, f)
 

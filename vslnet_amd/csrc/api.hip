@@ -1,6 +1,8 @@
-// C ABI of libvslnet_hip.so (declared in include/vslnet_hip.h): every entry point checks its arguments, looks up the plan of the shape, builds the
-// call's context and hands over to the unit that does the work (layout.hip, plan.hip, forward.hip, backward.hip; the vsl_profile_* entry points
-// live with the profiler in streams.hip).  Host code only -- no device code lives here.
+// C ABI of libvslnet_hip.so (declared in include/vslnet_hip.h).  Every entry point checks its arguments and states its own refusals; the five
+// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, vsl_backward / vsl_backward_shared) then go
+// through ONE path, enqueue(): plan of the shape, the call's context, the CallScope, the sequence of forward.hip / backward.hip, the launch-error
+// check and, for a forward, record_forward(): what it left for the calls behind it.  (layout.hip, plan.hip do the rest; the vsl_profile_* entry
+// points live with the profiler in streams.hip.)  Host code only -- no device code lives here.
 #include "host.hpp"
 
 using namespace vsl;
@@ -15,12 +17,44 @@ static int check_io(vsl_handle_s* h, const vsl_io* io) {
     return 0;
 }
 
-static int workspace_floats(vsl_handle_s* h, PlanKind kind, int B, int T, int Lq, int Lc, int64_t* out) {
+static int workspace_floats(vsl_handle_s* h, PlanKind kind, int B, int T, int Lq, int Lc, int64_t* out, int N = 0) {
     if (!h || !out) return fail("null argument");
     Plan* p = nullptr;
-    if (int rc = get_plan(h, B, T, Lq, Lc, &p, kind)) return rc;
+    if (int rc = get_plan(h, B, T, Lq, Lc, &p, kind, N)) return rc;
     *out = p->total;
     return 0;
+}
+
+// A forward has been enqueued: what the calls behind it find.  infer_ws = the workspace of the last forward that saved nothing, cleared only by a
+// saved-path forward in that same workspace.
+static void record_forward(vsl_handle_s* h, vsl_handle_s::LastFwd kind, const float* workspace, int shared_N) {
+    h->last_fwd = kind;
+    if (kind == vsl_handle_s::FwdShared) h->shared_N = shared_N;
+    if (kind == vsl_handle_s::FwdInfer) h->infer_ws = workspace;
+    else if (h->infer_ws == workspace) h->infer_ws = nullptr;
+}
+
+// One enqueuing call: the plan of the io's shape, the call's context, the call's bookkeeping, `seq` (which enqueues), the launch-error check, and
+// -- `fwd` other than FwdNone: the call is a forward of that kind -- the record of it.
+template <class Seq>
+static int enqueue(vsl_handle_s* h, const vsl_io* io, PlanKind kind, const vsl_shared_io* sh, void* hip_stream, vsl_handle_s::LastFwd fwd, Seq&& seq) {
+    Plan* p = nullptr;
+    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, kind, sh ? sh->N : 0)) return rc;
+    Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
+    c.main = c.s;
+    c.sh = sh;
+    CallScope scope(h);
+    seq(c);
+    HIP_OK(hipGetLastError());
+    if (fwd != vsl_handle_s::FwdNone) record_forward(h, fwd, io->workspace, sh ? sh->N : 0);
+    return 0;
+}
+
+// vsl_workspace_offset / vsl_shared_workspace_offset behind a forward that saved nothing: refused (-2)
+static bool saved_nothing(vsl_handle_s* h, const char* who) {
+    if (!h || h->last_fwd != vsl_handle_s::FwdInfer) return false;
+    fail("%s: the last forward saved nothing (inference mode): there is no saved activation to point at", who);
+    return true;
 }
 
 static int64_t plan_offset(vsl_handle_s* h, const Plan* p, const char* name);
@@ -66,8 +100,7 @@ int vsl_create(const vsl_config* cfg, vsl_handle* out) {
         return fail("hipMalloc/hipMemcpy of the pack table failed");
     }
     {
-        const char* e = getenv("VSL_MULTI_STREAM");
-        h->multi_stream = !(e && e[0] == '0');
+        h->multi_stream = switch_on("VSL_MULTI_STREAM", true);     // (per handle: read at every vsl_create)
         if (h->multi_stream)
             for (int k = 0; k < 2; ++k) {
                 // side(1) carries the weight gradients: nothing waits for them until the final reduction, so it runs at the
@@ -117,14 +150,14 @@ int vsl_inference_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, i
 
 int64_t vsl_workspace_offset(vsl_handle h, int B, int T, int Lq, int Lc, const char* name) {
     Plan* p = nullptr;
-    if (h && h->last_infer) { fail("vsl_workspace_offset: the last forward saved nothing (inference mode): there is no saved activation to point at"); return -2; }
+    if (saved_nothing(h, "vsl_workspace_offset")) return -2;
     if (!h || !name || get_plan(h, B, T, Lq, Lc, &p)) return -1;
     return plan_offset(h, p, name);
 }
 
 int64_t vsl_shared_workspace_offset(vsl_handle h, int B, int N, int T, int Lq, int Lc, const char* name) {
     Plan* p = nullptr;
-    if (h && h->last_infer) { fail("vsl_shared_workspace_offset: the last forward saved nothing (inference mode): there is no saved activation to point at"); return -2; }
+    if (saved_nothing(h, "vsl_shared_workspace_offset")) return -2;
     if (!h || !name || get_plan(h, B, T, Lq, Lc, &p, PlanKind::TrainShared, N)) return -1;
     const std::string n = name;
     if (n == "d_venc_video") return p->dCv;
@@ -197,50 +230,31 @@ static int check_shared_io(const vsl_io* io, const vsl_shared_io* sh, const char
     return 0;
 }
 
+// the body vsl_backward and vsl_backward_shared (sh != nullptr) share behind their own refusals
+static int backward(vsl_handle_s* h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream, const char* who) {
+    if (int rc = check_backward_io(h, io, who)) return rc;
+    Plan* p = nullptr;
+    if (int rc = enqueue(h, io, sh ? PlanKind::TrainShared : PlanKind::Train, sh, hip_stream, vsl_handle_s::FwdNone, [&](Ctx& c) { run_backward(c); p = c.p; })) return rc;
+    h->sq_src = p->sq_cover ? p->sq_dev : nullptr; h->sq_n = p->nblocks; h->sq_grads = io->grads;
+    return 0;
+}
+
 extern "C" {
 
 int vsl_forward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
     if (io->inference && io->training) return fail("vsl_forward: inference and training exclude each other (the inference kernels have no dropout)");
-    Plan* p = nullptr;
-    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, io->inference ? PlanKind::Infer : PlanKind::Train)) return rc;
-    Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
-    c.main = c.s;
-    CallScope scope(h);
-    forward_full(c);
-    HIP_OK(hipGetLastError());
-    h->last_infer = io->inference != 0;
-    h->last_fwd = io->inference ? vsl_handle_s::FwdInfer : vsl_handle_s::FwdFull;
-    if (io->inference) h->infer_ws = io->workspace;
-    else if (h->infer_ws == io->workspace) h->infer_ws = nullptr;
-    return 0;
+    if (io->inference) return enqueue(h, io, PlanKind::Infer, nullptr, hip_stream, vsl_handle_s::FwdInfer, forward_full);
+    return enqueue(h, io, PlanKind::Train, nullptr, hip_stream, vsl_handle_s::FwdFull, forward_full);
 }
 
 // ---- training through a shared video encoding: N videos, B queries per step
-int vsl_shared_workspace_floats(vsl_handle h, int B, int N, int T, int Lq, int Lc, int64_t* out) {
-    if (!h || !out) return fail("null argument");
-    Plan* p = nullptr;
-    if (int rc = get_plan(h, B, T, Lq, Lc, &p, PlanKind::TrainShared, N)) return rc;
-    *out = p->total;
-    return 0;
-}
+int vsl_shared_workspace_floats(vsl_handle h, int B, int N, int T, int Lq, int Lc, int64_t* out) { return workspace_floats(h, PlanKind::TrainShared, B, T, Lq, Lc, out, N); }
 
 int vsl_forward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
     if (int rc = check_shared_io(io, sh, "vsl_forward_shared")) return rc;
-    Plan* p = nullptr;
-    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, PlanKind::TrainShared, sh->N)) return rc;
-    Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
-    c.main = c.s;
-    c.sh = sh;
-    CallScope scope(h);
-    forward_shared_train(c);
-    HIP_OK(hipGetLastError());
-    h->last_infer = false;
-    h->last_fwd = vsl_handle_s::FwdShared;
-    h->shared_N = sh->N;
-    if (h->infer_ws == io->workspace) h->infer_ws = nullptr;
-    return 0;
+    return enqueue(h, io, PlanKind::TrainShared, sh, hip_stream, vsl_handle_s::FwdShared, forward_full);
 }
 
 int vsl_backward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream) {
@@ -249,17 +263,7 @@ int vsl_backward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh,
     if (h->last_fwd != vsl_handle_s::FwdShared || io->workspace == h->infer_ws)
         return fail("vsl_backward_shared: the handle's last forward was not vsl_forward_shared (an ordinary forward is differentiated by vsl_backward; an inference forward saved nothing)");
     if (sh->N != h->shared_N) return fail("vsl_backward_shared: N=%d, but the last vsl_forward_shared ran over N=%d videos", sh->N, h->shared_N);
-    if (int rc = check_backward_io(h, io, "vsl_backward_shared")) return rc;
-    Plan* p = nullptr;
-    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, PlanKind::TrainShared, sh->N)) return rc;
-    Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
-    c.main = c.s;
-    c.sh = sh;
-    CallScope scope(h);
-    run_backward(c);
-    HIP_OK(hipGetLastError());
-    h->sq_src = p->sq_cover ? p->sq_dev : nullptr; h->sq_n = p->nblocks; h->sq_grads = io->grads;
-    return 0;
+    return backward(h, io, sh, hip_stream, "vsl_backward_shared");
 }
 
 // ---- one encoding per video, many queries against it (evaluation only: no dropout, nothing saved, no backward)
@@ -274,22 +278,13 @@ int vsl_encode_video(vsl_handle h, const vsl_encode_io* e, void* hip_stream) {
         return fail("vsl_encode_io has a null device pointer");
     if (e->video_features_bf16 && (h->cfg.video_feature_dim % 8 != 0))
         return fail("bf16 features need video_feature_dim %% 8 == 0 (got %d)", h->cfg.video_feature_dim);
-    Plan* p = nullptr;
-    if (int rc = get_plan(h, e->N, e->T, 0, 0, &p, PlanKind::Encode)) return rc;
     vsl_io io;
     memset(&io, 0, sizeof io);
     io.B = e->N; io.T = e->T;
     io.params = e->params; io.video_features = e->video_features; io.video_features_bf16 = e->video_features_bf16; io.v_mask = e->v_mask;
     io.workspace = e->workspace; io.inference = 1;
-    Ctx c{h, p, &io, (hipStream_t)hip_stream, false, io.workspace};
-    c.main = c.s;
-    CallScope scope(h);
-    forward_encode(c, e->video_encoding);
-    HIP_OK(hipGetLastError());
-    h->last_fwd = vsl_handle_s::FwdInfer;
-    h->last_infer = true;            // (nothing saved: vsl_backward in this workspace and vsl_workspace_offset are refused as after an inference forward)
-    h->infer_ws = e->workspace;
-    return 0;
+    // (FwdInfer: nothing saved -- vsl_backward in this workspace and vsl_workspace_offset are refused as after an inference forward)
+    return enqueue(h, &io, PlanKind::Encode, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) { forward_encode(c, e->video_encoding); });
 }
 
 int vsl_localize(vsl_handle h, const vsl_localize_io* l, void* hip_stream) {
@@ -302,25 +297,17 @@ int vsl_localize(vsl_handle h, const vsl_localize_io* l, void* hip_stream) {
     if (!l->params || (!h->cfg.word_table && (!l->pad_vec || !l->glove_vec)) || !l->word_ids || !l->char_ids || !l->q_mask || !l->h_score || !l->start_logits ||
         !l->end_logits || !l->workspace)
         return fail("vsl_localize_io has a null device pointer");
-    Plan* p = nullptr;
-    if (int rc = get_plan(h, l->B, l->T, l->Lq, l->Lc, &p, PlanKind::Localize)) return rc;
     vsl_io io;
     memset(&io, 0, sizeof io);
     io.B = l->B; io.T = l->T; io.Lq = l->Lq; io.Lc = l->Lc;
     io.params = l->params; io.pad_vec = l->pad_vec; io.glove_vec = l->glove_vec;
     io.word_ids = l->word_ids; io.char_ids = l->char_ids; io.q_mask = l->q_mask;
-    io.v_mask = l->workspace + p->vmask;          // every kernel behind the join reads the gathered (B, T) mask
     io.h_score = l->h_score; io.start_logits = l->start_logits; io.end_logits = l->end_logits;
     io.workspace = l->workspace; io.inference = 1;
-    Ctx c{h, p, &io, (hipStream_t)hip_stream, false, io.workspace};
-    c.main = c.s;
-    CallScope scope(h);
-    forward_localize(c, CqContext{l->video_encoding, l->video_index}, l->v_mask);
-    HIP_OK(hipGetLastError());
-    h->last_infer = true;
-    h->last_fwd = vsl_handle_s::FwdInfer;
-    h->infer_ws = l->workspace;
-    return 0;
+    return enqueue(h, &io, PlanKind::Localize, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) {
+        io.v_mask = c.W(c.p->vmask);          // every kernel behind the join reads the gathered (B, T) mask
+        forward_localize(c, CqContext{l->video_encoding, l->video_index}, l->v_mask);
+    });
 }
 
 int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_stream) {
@@ -345,16 +332,7 @@ int vsl_backward(vsl_handle h, const vsl_io* io, void* hip_stream) {
         return fail("vsl_backward: the last forward saved nothing (inference mode): run vsl_forward with inference = 0 for a batch that is to be differentiated");
     if (h->last_fwd == vsl_handle_s::FwdShared)
         return fail("vsl_backward: the handle's last forward was vsl_forward_shared: its saves are differentiated by vsl_backward_shared");
-    if (int rc = check_backward_io(h, io, "vsl_backward")) return rc;
-    Plan* p = nullptr;
-    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p)) return rc;
-    Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
-    c.main = c.s;
-    CallScope scope(h);
-    run_backward(c);
-    HIP_OK(hipGetLastError());
-    h->sq_src = p->sq_cover ? p->sq_dev : nullptr; h->sq_n = p->nblocks; h->sq_grads = io->grads;
-    return 0;
+    return backward(h, io, nullptr, hip_stream, "vsl_backward");
 }
 
 int vsl_abi_version(void) { return VSL_ABI_VERSION; }

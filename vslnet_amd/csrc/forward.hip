@@ -13,31 +13,25 @@ static void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const
         // the whole conv block + LN1 / QKV in ONE launch (kernels_enc.hip: 12-row recomputed halo)
         CbFwdArgs a;
         memset(&a, 0, sizeof a);
-        if (!c.dry) {
-            a.xin = xin; a.pos = c.P(P.pos); a.x0_out = c.SV(w.x0); a.nosave = c.inf();
-            for (int i = 0; i < 4; ++i) {
-                a.ln_g[i] = c.P(P.lng[i]); a.ln_b[i] = c.P(P.lnb[i]); a.dw_w[i] = c.P(P.dw[i]);
-                a.pw_b[i] = c.P(P.pwb[i]); a.y[i] = i == 3 ? c.W(w.y[i]) : c.SV(w.y[i]); a.u[i] = c.SV(w.u[i]);      // (y[3]: the attention block's residual input)
-                a.relu_mask[i] = reinterpret_cast<uint32_t*>(c.SV(w.mask[i])); a.dp[i] = c.drop(app * 16 + i);
-            }
-            a.qf = QkvFuse{c.P(P.ln1g), c.P(P.ln1b), c.P(P.qb), c.P(P.kb), c.P(P.vb), c.SV(w.h1), c.W(w.q), c.W(w.k), c.W(w.v),
-                           c.drop(app * 16 + 4)};
-            for (int i = 0; i < 4; ++i) a.W3[i] = reinterpret_cast<const uint16_t*>(c.PK(K.pw_f3[i]));
-            a.Wqkv3 = reinterpret_cast<const uint16_t*>(c.PK(K.qkv_f3));
-            a.R = R; a.L = L;
+        a.xin = xin; a.pos = c.P(P.pos); a.x0_out = c.SV(w.x0); a.nosave = c.inf();
+        for (int i = 0; i < 4; ++i) {
+            a.ln_g[i] = c.P(P.lng[i]); a.ln_b[i] = c.P(P.lnb[i]); a.dw_w[i] = c.P(P.dw[i]);
+            a.pw_b[i] = c.P(P.pwb[i]); a.y[i] = i == 3 ? c.W(w.y[i]) : c.SV(w.y[i]); a.u[i] = c.SV(w.u[i]);      // (y[3]: the attention block's residual input)
+            a.relu_mask[i] = reinterpret_cast<uint32_t*>(c.SV(w.mask[i])); a.dp[i] = c.drop(app * 16 + i);
         }
+        a.qf = QkvFuse{c.P(P.ln1g), c.P(P.ln1b), c.P(P.qb), c.P(P.kb), c.P(P.vb), c.SV(w.h1), c.W(w.q), c.W(w.k), c.W(w.v),
+                       c.drop(app * 16 + 4)};
+        for (int i = 0; i < 4; ++i) a.W3[i] = reinterpret_cast<const uint16_t*>(c.PK(K.pw_f3[i]));
+        a.Wqkv3 = reinterpret_cast<const uint16_t*>(c.PK(K.qkv_f3));
+        a.R = R; a.L = L;
         LAUNCH("convblock_fwd", launch_convblock_fwd(a, c.s));
     }
     if (H == 8 && L <= 128) {      // attention core + output block in one launch (kernels_enc.hip)
-        AttnBlockArgs ab;
-        memset(&ab, 0, sizeof ab);
-        if (!c.dry) {
-            ab = AttnBlockArgs{c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob),
-                               c.SV(w.att), c.SV(w.lse), c.SV(w.r), c.SV(w.h2), yout, L, 0,
-                               c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8)};
-            ab.nosave = c.inf();
-            if (ht) { ab.head_tail = 1; ab.hs = ht->hs; ab.he = ht->he; ab.head_x = ht->x; ab.head_vmask = ht->vmask; }
-        }
+        AttnBlockArgs ab{c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob),
+                         c.SV(w.att), c.SV(w.lse), c.SV(w.r), c.SV(w.h2), yout, L, 0,
+                         c.drop(app * 16 + 5), c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8)};
+        ab.nosave = c.inf();
+        if (ht) { ab.head_tail = 1; ab.hs = ht->hs; ab.he = ht->he; ab.head_x = ht->x; ab.head_vmask = ht->vmask; }
         LAUNCH("attn_block_fwd", launch_attn_block_fwd(ab, Bn, c.s));
         return;
     }
@@ -95,7 +89,7 @@ void rnn_granules_fresh(Ctx& c, Plan& p, long long gen) {
 
 // Lq <= 32: the query branch runs as sample-local launches (kernels_query.hip) in both directions (VSL_QUERY_FUSED=0: row-tile launches)
 bool query_fused(const Ctx& c) {
-    static const bool on = !(getenv("VSL_QUERY_FUSED") && getenv("VSL_QUERY_FUSED")[0] == '0');
+    static const bool on = switch_on("VSL_QUERY_FUSED", true);
     return on && query_fused_ok(c.p->Lq, c.h->cfg.num_heads, c.h->cfg.word_dim + 100);
 }
 
@@ -135,23 +129,21 @@ static void query_branch(Ctx& c, PackWait emb_pack) {
         // the rest of the query branch in ONE sample-local launch (kernels_query.hip)
         QueryFwdArgs qa;
         memset(&qa, 0, sizeof qa);
-        if (!c.dry) {
-            const EncP& E = P.fe; const EncPk& EK = K.fe; const EncWs& w = p.qe;
-            qa.E = c.W(p.E); qa.Wemb3 = reinterpret_cast<const uint16_t*>(c.PK(K.emb_f3)); qa.b_emb = c.P(P.emb_b); qa.qf = c.SV(p.qf); qa.nosave = c.inf();
-            qa.pos = c.P(E.pos); qa.x0 = c.SV(w.x0);
-            for (int i = 0; i < 4; ++i) {
-                qa.W3[i] = reinterpret_cast<const uint16_t*>(c.PK(EK.pw_f3[i]));
-                qa.ln_g[i] = c.P(E.lng[i]); qa.ln_b[i] = c.P(E.lnb[i]); qa.dw_w[i] = c.P(E.dw[i]); qa.pw_b[i] = c.P(E.pwb[i]);
-                qa.y[i] = c.SV(w.y[i]); qa.u[i] = c.SV(w.u[i]); qa.relu_mask[i] = reinterpret_cast<uint32_t*>(c.SV(w.mask[i])); qa.dp[i] = c.drop(16 + i);
-            }
-            qa.Wqkv3 = reinterpret_cast<const uint16_t*>(c.PK(EK.qkv_f3)); qa.Wo3 = reinterpret_cast<const uint16_t*>(c.PK(EK.o_f3));
-            qa.ln1_g = c.P(E.ln1g); qa.ln1_b = c.P(E.ln1b); qa.bq = c.P(E.qb); qa.bk = c.P(E.kb); qa.bv = c.P(E.vb);
-            qa.h1 = c.SV(w.h1); qa.q = c.SV(w.q); qa.k = c.SV(w.k); qa.v = c.SV(w.v); qa.d1 = c.drop(16 + 4);
-            qa.mask = io.q_mask; qa.ln2_g = c.P(E.ln2g); qa.ln2_b = c.P(E.ln2b); qa.bo = c.P(E.ob);
-            qa.att = c.SV(w.att); qa.lse = c.SV(w.lse); qa.r = c.SV(w.r); qa.h2 = c.SV(w.h2); qa.out = c.W(w.out);
-            qa.d2 = c.drop(16 + 5); qa.d3 = c.drop(16 + 6); qa.d4 = c.drop(16 + 7); qa.d5 = c.drop(16 + 8);
-            qa.EW = cf.word_dim + 100; qa.L = Lq; qa.b_off = 0;
+        const EncP& E = P.fe; const EncPk& EK = K.fe; const EncWs& w = p.qe;
+        qa.E = c.W(p.E); qa.Wemb3 = reinterpret_cast<const uint16_t*>(c.PK(K.emb_f3)); qa.b_emb = c.P(P.emb_b); qa.qf = c.SV(p.qf); qa.nosave = c.inf();
+        qa.pos = c.P(E.pos); qa.x0 = c.SV(w.x0);
+        for (int i = 0; i < 4; ++i) {
+            qa.W3[i] = reinterpret_cast<const uint16_t*>(c.PK(EK.pw_f3[i]));
+            qa.ln_g[i] = c.P(E.lng[i]); qa.ln_b[i] = c.P(E.lnb[i]); qa.dw_w[i] = c.P(E.dw[i]); qa.pw_b[i] = c.P(E.pwb[i]);
+            qa.y[i] = c.SV(w.y[i]); qa.u[i] = c.SV(w.u[i]); qa.relu_mask[i] = reinterpret_cast<uint32_t*>(c.SV(w.mask[i])); qa.dp[i] = c.drop(16 + i);
         }
+        qa.Wqkv3 = reinterpret_cast<const uint16_t*>(c.PK(EK.qkv_f3)); qa.Wo3 = reinterpret_cast<const uint16_t*>(c.PK(EK.o_f3));
+        qa.ln1_g = c.P(E.ln1g); qa.ln1_b = c.P(E.ln1b); qa.bq = c.P(E.qb); qa.bk = c.P(E.kb); qa.bv = c.P(E.vb);
+        qa.h1 = c.SV(w.h1); qa.q = c.SV(w.q); qa.k = c.SV(w.k); qa.v = c.SV(w.v); qa.d1 = c.drop(16 + 4);
+        qa.mask = io.q_mask; qa.ln2_g = c.P(E.ln2g); qa.ln2_b = c.P(E.ln2b); qa.bo = c.P(E.ob);
+        qa.att = c.SV(w.att); qa.lse = c.SV(w.lse); qa.r = c.SV(w.r); qa.h2 = c.SV(w.h2); qa.out = c.W(w.out);
+        qa.d2 = c.drop(16 + 5); qa.d3 = c.drop(16 + 6); qa.d4 = c.drop(16 + 7); qa.d5 = c.drop(16 + 8);
+        qa.EW = cf.word_dim + 100; qa.L = Lq; qa.b_off = 0;
         LAUNCH("query_fwd", launch_query_fwd(qa, B, c.s));
         return;
     }
@@ -171,7 +163,7 @@ static void fuse_and_predict(Ctx& c, CqContext ctx) {
     hipStream_t sq = c.side(0);
     // short videos, short queries: the column kernel (column softmax over the clips, M = S_col^T C, WeightedPool) is folded into its neighbours --
     // one launch and one boundary less on the dependent chain (VSL_CQ_FOLD=0: three launches)
-    static const bool fold_on = !(getenv("VSL_CQ_FOLD") && getenv("VSL_CQ_FOLD")[0] == '0');
+    static const bool fold_on = switch_on("VSL_CQ_FOLD", true);
     const bool cq_fold = fold_on && cq_col_folds(T, Lq);
     const CqPoolArgs pool{c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb)};
     LAUNCH("cq_score", launch_cq_score(ctx.C, c.W(p.qe.out), io.q_mask, c.P(P.w4C), c.P(P.w4Q), c.P(P.w4mlu), c.W(p.S), c.W(p.Srow), B, T,
@@ -253,7 +245,7 @@ static void fuse_and_predict(Ctx& c, CqContext ctx) {
     HeadArgs he{c.W(p.p2.out), c.P(P.eln_g), c.P(P.eln_b), c.PK(K.e0_f), c.P(P.e0b), c.P(P.e1w), c.P(P.e1b), c.SV(p.hid_e),
                 c.SV(p.lnf_e), io.end_logits};
     // T <= 128: the second pass' attention-block kernel goes on with both span heads on its tiles (one launch less on the dependent chain)
-    static const bool heads_on = !(getenv("VSL_HEADS_FUSED") && getenv("VSL_HEADS_FUSED")[0] == '0');
+    static const bool heads_on = switch_on("VSL_HEADS_FUSED", true);
     const bool heads_hosted = heads_on && cf.num_heads == 8 && attn_block_fwd_hosts_heads(T);
     HeadTail ht{hs, he, c.W(p.gated), io.v_mask};
     enc_fwd(c, P.pe, K.pe, p.p2, c.W(p.p1.out), io.v_mask, B, 3, heads_hosted ? &ht : nullptr);
@@ -278,10 +270,12 @@ static PackWait side_packs(Ctx& c, hipStream_t sp) {
     return w;
 }
 
-// the video branch and the query branch side by side, joined in front of the CQ kernels.  `vidx` (a shared training step): the video branch ran over
+// vsl_forward / vsl_forward_shared: the video branch and the query branch side by side, joined in front of the CQ kernels.  `vidx` (a shared training
+// step: c.sh set, plan TrainShared, N videos, B queries, query b against video video_index[b]): the video branch ran over
 // the plan's N videos and CQAttention reads its output through the index; the grouping of the queries by video (the backward's reduction of dC reads
 // it) is built beside the branches on the pack stream, off the dependent chain
-static void forward_joined(Ctx& c, const int* vidx) {
+void forward_full(Ctx& c) {
+    const int* const vidx = c.video_index();
     const vsl_handle_s* h = c.h;
     const Plan& p = *c.p;
     const int nj = (int)h->jobs.size(), nfirst = h->jobs_char + h->jobs_first;
@@ -316,12 +310,6 @@ static void forward_joined(Ctx& c, const int* vidx) {
     if (split3) c.order(sp, c.main);       // the remaining packs (long done)
     fuse_and_predict(c, CqContext{c.W(p.ve.out), vidx});
 }
-
-// vsl_forward
-void forward_full(Ctx& c) { forward_joined(c, nullptr); }
-
-// vsl_forward_shared: N videos, B queries, query b against video video_index[b]
-void forward_shared_train(Ctx& c) { forward_joined(c, c.sh->video_index); }
 
 // vsl_encode_video: the video half alone -- the shared encoder's and VisualProjection's operands, the projection, encoder application 0
 // into the caller's buffer.  One stream: there is no query branch to run beside it.

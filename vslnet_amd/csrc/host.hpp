@@ -123,11 +123,12 @@ struct vsl_handle_s {
     int sq_n = 0;
     const float* sq_grads = nullptr;
     std::map<std::tuple<int, int, int, int, int, vsl::PlanKind>, vsl::Plan*> plans;      // key: B, T, Lq, Lc, N (TrainShared; 0 otherwise), kind
+    // what the last forward left (api.hip record_forward):
     const void* infer_ws = nullptr;      // workspace the last INFERENCE forward ran in (it holds no saves: vsl_backward on it is refused) ; a training forward in it clears this
     enum LastFwd { FwdNone, FwdFull, FwdInfer, FwdShared };
-    LastFwd last_fwd = FwdNone;          // what the handle's last forward was: vsl_backward / vsl_backward_shared refuse the other kind's saves, vsl_loss finds its scratch in that plan
+    LastFwd last_fwd = FwdNone;          // its kind: vsl_backward / vsl_backward_shared refuse the other kind's saves, vsl_loss finds its scratch in that plan, and after
+                                         // FwdInfer (inference forward, vsl_encode_video, vsl_localize) vsl_workspace_offset has nothing to point at
     int shared_N = 0;                    // N of the last vsl_forward_shared
-    bool last_infer = false;             // the handle's last forward was an inference forward (vsl_workspace_offset then has nothing to point at)
     uint64_t plan_clock = 0;
     // side streams for the independent chains (query branch, weight gradients) + fork/join events
     hipStream_t side[2] = {nullptr, nullptr};
@@ -186,24 +187,40 @@ struct Ctx {
     Plan* p;
     const vsl_io* io;
     hipStream_t s;
-    bool dry;                           // plan-building pass: record partial-slab allocations, launch nothing
+    // Plan-building pass (build_train_plan runs run_backward once per plan, with io == nullptr and ws == nullptr; a forward is never run dry): record
+    // the partial-slab allocations, launch nothing.  Every pointer this struct hands out -- W, SV, P, PK, part_ptr, slab, the vsl_io accessors below --
+    // is nullptr then, so no call site tests `dry` to form one.  What does test it is behaviour, not addressing: LAUNCH and order_n (nothing is
+    // enqueued), part_alloc / reg / slab (record instead of replay), the backward's choice of streams and of deferring weight gradients (a dry run has
+    // no streams), and the blocks that touch what has no null value to stand in for it: vsl_io.early_grads_event, and the process-wide tag counter of
+    // the fused rnn launches.  (fused_loss / fused_step and their scalar fields sit behind fused_loss() / fused_step(), null in a dry run.)
+    bool dry;
     float* ws;
     size_t part_idx = 0;
     int64_t part_cur = 0;
     std::vector<SlabRec>* recs = nullptr;
-    std::vector<WgradBatch> pend;       // weight-gradient batches waiting for ONE ordering point (wgrad_async / wgrad_flush)
-    const vsl_loss_io* pend_loss = nullptr;   // vsl_io.fused_loss off the dependent chain: launched on the weight-gradient stream behind its first ordering point (loss_on_side)
-    int pw_rows = 0;                    // rows per chunk of the NEXT enc_bwd's pointwise weight-gradient jobs (0 = WG_ROWS): the step's last batch, run_backward
-    bool defer_w = false;
     const vsl_shared_io* sh = nullptr;  // vsl_forward_shared / vsl_backward_shared: the videos' index and clip mask (the plan is TrainShared then)
     bool inf() const { return p->kind != PlanKind::Train && p->kind != PlanKind::TrainShared; }
-    // the clip mask of the video half: (N, T) per video in a shared step, vsl_io.v_mask otherwise
-    const float* video_mask() const { return sh ? sh->video_v_mask : io->v_mask; }
     // a tensor only the backward reads: its address in a training forward, nullptr in an inference forward (the kernels then do not store it)
-    float* SV(int64_t off) const { return inf() ? nullptr : ws + off; }
-    const float* P(int off) const { return io->params + off; }
-    const float* PK(int off) const { return ws + p->pack + off; }
-    float* W(int64_t off) const { return ws + off; }
+    float* SV(int64_t off) const { return dry || inf() ? nullptr : ws + off; }
+    const float* P(int off) const { return dry ? nullptr : io->params + off; }
+    const float* PK(int off) const { return dry ? nullptr : ws + p->pack + off; }
+    float* W(int64_t off) const { return dry ? nullptr : ws + off; }
+    // what the backward reads from the call's vsl_io (nullptr in a dry run: there is no call)
+    const float* v_mask() const { return dry ? nullptr : io->v_mask; }      const float* q_mask() const { return dry ? nullptr : io->q_mask; }
+    // the clip mask of the video half: (N, T) per video in a shared step, vsl_io.v_mask otherwise ; the shared step's video of each query
+    const float* video_mask() const { return dry ? nullptr : sh ? sh->video_v_mask : io->v_mask; }
+    const int* video_index() const { return dry || !sh ? nullptr : sh->video_index; }
+    const int64_t* word_ids() const { return dry ? nullptr : io->word_ids; }  const int64_t* char_ids() const { return dry ? nullptr : io->char_ids; }
+    const float* video_features() const { return dry ? nullptr : io->video_features; }
+    const uint16_t* video_features_bf16() const { return dry ? nullptr : io->video_features_bf16; }
+    float* h_score() const { return dry ? nullptr : io->h_score; }            float* grads() const { return dry ? nullptr : io->grads; }
+    float* start_logits() const { return dry ? nullptr : io->start_logits; }  float* end_logits() const { return dry ? nullptr : io->end_logits; }
+    // the loss seeds: the outputs of vsl_io.fused_loss when the loss is part of the call, the caller's otherwise
+    const float* d_start_logits() const { return dry ? nullptr : io->fused_loss ? io->fused_loss->d_start_logits : io->d_start_logits; }
+    const float* d_end_logits() const { return dry ? nullptr : io->fused_loss ? io->fused_loss->d_end_logits : io->d_end_logits; }
+    const float* d_h_score() const { return dry ? nullptr : io->fused_loss ? io->fused_loss->d_h_score : io->d_h_score; }
+    // the loss / the optimizer step inside the call (nullptr: not asked for, or a dry run)
+    const vsl_loss_io* fused_loss() const { return dry ? nullptr : io->fused_loss; }   const vsl_fused_step* fused_step() const { return dry ? nullptr : io->fused_step; }
     // raw allocation in the partial arena
     int64_t part_alloc(int64_t n) {
         n = (n + 3) & ~int64_t(3);
@@ -218,9 +235,9 @@ struct Ctx {
     float* slab(int dst, int n, int nslabs) {
         const int64_t o = part_alloc((int64_t)n * nslabs);
         reg(dst, n, p->partial + o, nslabs, n);
-        return dry ? nullptr : ws + p->partial + o;
+        return W(p->partial + o);
     }
-    float* part_ptr(int64_t o) const { return dry ? nullptr : ws + p->partial + o; }
+    float* part_ptr(int64_t o) const { return W(p->partial + o); }
     // make stream `to` wait for everything enqueued so far on stream `from` ; order2: one event record on `from`, two waiters (streams.hip)
     void order(hipStream_t from, hipStream_t to) { order_n(from, &to, 1); }
     void order2(hipStream_t from, hipStream_t to1, hipStream_t to2) { const hipStream_t to[2] = {to1, to2}; order_n(from, to, 2); }
@@ -283,8 +300,7 @@ bool prof_selected(const vsl_handle_s* h, const char* name);
 bool query_chain_is_longer(const Plan& p);      // after the backward's video / query fork
 // forward.hip
 struct CqContext { const float* C; const int* vidx; };     // the context of CQAttention: C (B, T, 128), or a resident (N, T, 128) encoding read through vidx (B)
-void forward_full(Ctx& c);
-void forward_shared_train(Ctx& c);              // c.sh set, plan TrainShared
+void forward_full(Ctx& c);                      // vsl_forward, or (c.sh set, plan TrainShared) vsl_forward_shared
 void forward_encode(Ctx& c, float* video_encoding);
 void forward_localize(Ctx& c, CqContext ctx, const float* vmask_nt);
 bool query_fused(const Ctx& c);

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void k_attn_dq(const float* __restrict__ Q, co
 }
 
 bool attn_dq_query_major(int L) {
-    static const bool slabs = getenv("VSL_ATTN_DQ_SLABS") && getenv("VSL_ATTN_DQ_SLABS")[0] == '1';
+    static const bool slabs = switch_on("VSL_ATTN_DQ_SLABS", false);
     return L > ATTN_SLAB_MAX_L && !slabs;
 }
 int attn_dq_slabs(int L) { return attn_dq_query_major(L) ? 1 : attn_bwd_dq_slabs(L); }

@@ -749,12 +749,12 @@ __global__ __launch_bounds__(512, 2) void k_rnn_bwd(RnnBwdArgs a) {
 }
 
 static bool lstm_one_sample(int B) {
-    static const bool on = !(getenv("VSL_LSTM1") && getenv("VSL_LSTM1")[0] == '0');
+    static const bool on = switch_on("VSL_LSTM1", true);
     return on && B <= 256;
 }
 
 bool rnn_fused_ok(int B) {            // VSL_RNN_FUSED=0 keeps the chunked launches (the path of 80 < B <= 256) at every batch size
-    static const bool on = !(getenv("VSL_RNN_FUSED") && getenv("VSL_RNN_FUSED")[0] == '0');
+    static const bool on = switch_on("VSL_RNN_FUSED", true);
     return on && lstm_one_sample(B) && B <= RNN_FUSED_MAX_B;
 }
 void launch_rnn_fwd(const RnnFwdArgs& a, hipStream_t s) {

@@ -449,4 +449,8 @@ int embed_bwd_chunk(int Rq, int Lc, int char_dim);      // words per workgroup t
 constexpr int EB_IMG_Q = 76;      // k-steps of the embedding backward's B-operand image ([channel tile][76][64 lanes], PackJob type 8)
 constexpr int CHARW_TOTAL = 15000;
 
+// A switch of the environment: VSL_X=0 turns off what is on by default, VSL_X=1 turns on what is off, anything else leaves the default.  A call
+// site keeps the answer in a function-local static, so that a process reads each switch once.
+inline bool switch_on(const char* name, bool dflt) { const char* e = getenv(name); return e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : dflt; }
+
 }  // namespace vsl
