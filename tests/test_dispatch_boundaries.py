@@ -21,7 +21,7 @@ ROUTE_LABELS = ('attn_block_fwd', 'attn_fwd', 'attn_out_fwd', 'head_fwd', 'qkv_b
 def predicted_routes(B, T, Lq, num_heads=8, predictor='transformer', lazy=True):
     """-> (labels the step launches among ROUTE_LABELS, whether the loss seeds are computed inside the heads' backward), from the predicates:
     query_fused_ok (kernels_query.hip), enc_fwd's attention choice and attn_block_fwd_hosts_heads (forward.hip, launch.hpp), cq_col_folds
-    (kernels_fwd.hip), convblock_bwd_hosts_qkv + attn_bwd_dq_slabs (kernels_enc.hip, kernels_attn_h16.hip), rnn_fused_ok (kernels_lstm.hip) and
+    (kernels_cq.hip), convblock_bwd_hosts_qkv + attn_bwd_dq_slabs (kernels_enc.hip, kernels_attn_h16.hip), rnn_fused_ok (kernels_lstm.hip) and
     loss_seeds' seeds_inline (backward.hip)."""
     h8 = num_heads == 8
     query_local = h8 and Lq <= 32

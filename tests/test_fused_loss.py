@@ -3,7 +3,7 @@
 For T >= 32 (a row tile then touches at most two samples) with the caller's mask sum the loss kernel leaves the dependent chain -- it runs behind the
 main stream's last kernel -- and the
 span heads' backward and the highlight layer's backward compute their seeds from the logits themselves (the same expressions: tile_bodies.hpp
-loss_ce_seed / loss_hl_seed, kernels_bwd.hip loss_sample_lse).  Whatever the path: the same losses, the same seeds, the same gradients as
+loss_ce_seed / loss_hl_seed, kernels_head.hip loss_sample_lse).  Whatever the path: the same losses, the same seeds, the same gradients as
 loss() followed by backward()."""
 import pytest
 import torch

@@ -13,7 +13,12 @@ Cases: every row of tests/test_dispatch_boundaries.py::ROWS as one training step
 inference forward; the smallest shapes that reach the attention kernels those rows do not (1 and 2 heads with the element hash, the pair hash
 over two dQ slabs and query-major dQ; 4 and 16 heads with query-major dQ); encode_video + localize with a repeated and permuted video index, both predictors, fp32 and bf16 features;
 one training step through a shared encoding (Engine.forward_shared) with the same index, both predictors, at the two shapes that reach the
-sample-local and the row-tile query path and the folded and the unfolded CQ column; the headline bench shape; one B > 80 rnn shape (chunked LSTM launches over three streams).  The whole set runs three times, each in a fresh child process
+sample-local and the row-tile query path and the folded and the unfolded CQ column; the headline bench shape; one B > 80 rnn shape (chunked LSTM launches over three streams);
+the launchers those do not reach, at B = 3, T = 40, Lq = 9, Dv = 64 unless named: a step with the trainable word table (k_word_table_bwd, k_zero4, the table
+branch of embed_fwd), a step on bf16 features (k_vproj_fwd_bf16), the separate calls (an eager loss() that leaves the mask sum to the device, a
+loss(want_grads=False), a plain backward(), adamw_step with and without norm_from_backward and the norm it reports), a step at char_dim 100 and
+word_dim 52 with Lq = 40 (two channel blocks in the embedding kernels; k_linear_fwd), and a step at Lq = 100, T = 64 (k_cq_score<16>, the
+CQ_BIG_LQ layout of k_cq_out and of the CQ backward, the unfolded column).  The whole set runs three times, each in a fresh child process
 (the switches are read once per process): default, VSL_MULTI_STREAM=0, and every fusion switch off.  The children run one after the other,
 each under its own time limit; the tool stops at the first one that does not exit with 0."""
 import hashlib
@@ -66,7 +71,8 @@ def setup(cfgkw, B, T, Lq, Lc, ragged_extreme=False):
     d = {k: v.cuda().contiguous() for k, v in b.items()}
     eng = Engine(cfg)
     flat = flat_from_state_dict(eng, P)
-    pad, glove = P['embedding_net.word_emb.pad_vec'].cuda(), P['embedding_net.word_emb.glove_vec'].cuda()
+    pad, glove = P.get('embedding_net.word_emb.pad_vec'), P.get('embedding_net.word_emb.glove_vec')       # (absent: trainable word table)
+    pad, glove = (None if pad is None else pad.cuda()), (None if glove is None else glove.cuda())
     return eng, flat, pad, glove, b, d
 
 
@@ -80,9 +86,11 @@ def sizes_and_offsets(eng, B, T, Lq, Lc):
     return out
 
 
-def train_and_infer(cfgkw, B, T, Lq, Lc=6, lazy=True, ragged_extreme=False):
+def train_and_infer(cfgkw, B, T, Lq, Lc=6, lazy=True, ragged_extreme=False, bf16=False):
     import torch
     eng, flat, pad, glove, b, d = setup(cfgkw, B, T, Lq, Lc, ragged_extreme)
+    if bf16:
+        d['vfeats'] = d['vfeats'].to(torch.bfloat16)
     rec = {}
     eng.profile_select('*')
     h, sl, el = eng.forward(flat, pad, glove, d['word_ids'], d['char_ids'], d['vfeats'], d['v_mask'], d['q_mask'], training=True, seed=STEP_SEED)
@@ -153,6 +161,31 @@ def shared_train(cfgkw, N, B, T, Lq, Lc=6):
     return rec
 
 
+def separate_calls(cfgkw, B, T, Lq, Lc=6):
+    """The calls a fused step folds away, each on its own: the eager loss with the mask sum left to the device, the losses alone, a plain backward,
+    and the optimizer step with the norm from the backward's reduction and then from its own pass over the bucket."""
+    import torch
+    eng, flat, pad, glove, b, d = setup(cfgkw, B, T, Lq, Lc)
+    rec = {}
+    eng.profile_select('*')
+    h, sl, el = eng.forward(flat, pad, glove, d['word_ids'], d['char_ids'], d['vfeats'], d['v_mask'], d['q_mask'], training=True, seed=STEP_SEED)
+    losses, d_h, d_sl, d_el = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0, mask_sum=0.0)
+    losses_only = eng.loss(d['s_labels'], d['e_labels'], d['h_labels'], 1.0, 5.0, mask_sum=0.0, want_grads=False)[0]
+    g = eng.backward(d_h, d_sl, d_el, eng.new_flat())
+    m, v, gn = torch.zeros_like(flat), torch.zeros_like(flat), torch.zeros(2, device='cuda')
+    eng.adamw_step(flat, g, m, v, 1e-3, 1, clip_norm=1.0, grad_norm_out=gn[0:1], norm_from_backward=True)
+    torch.cuda.synchronize()
+    rec['step1'] = {'params': sha(flat), 'exp_avg': sha(m), 'exp_avg_sq': sha(v)}
+    eng.adamw_step(flat, g, m, v, 1e-3, 2, clip_norm=1.0, grad_norm_out=gn[1:2])
+    torch.cuda.synchronize()
+    rec['step2'] = {'params': sha(flat), 'exp_avg': sha(m), 'exp_avg_sq': sha(v)}
+    rec['calls_ledger'] = ledger(eng)
+    eng.profile_select(None)
+    rec['out'] = {'h_score': sha(h), 'start_logits': sha(sl), 'end_logits': sha(el), 'losses': sha(losses), 'losses_only': sha(losses_only),
+                  'seeds': sha(torch.stack([d_h, d_sl, d_el])), 'grads': sha(g), 'grad_norms': sha(gn)}
+    return rec
+
+
 def child(out_path):
     from tests.test_dispatch_boundaries import ROWS
     cases = {}
@@ -173,6 +206,12 @@ def child(out_path):
     for pred in ('transformer', 'rnn'):
         for (N, B, T, Lq) in ((3, 8, 64, 9), (2, 5, 160, 33)):
             cases['shared_train:%s-N%d-B%d-T%d-Lq%d' % (pred, N, B, T, Lq)] = shared_train(dict(video_feature_dim=64, predictor=pred), N, B, T, Lq)
+    small = dict(video_feature_dim=64)
+    cases['launchers:word-table-B3-T40-Lq9'] = train_and_infer(dict(small, word_table=True), 3, 40, 9)
+    cases['launchers:bf16-features-B3-T40-Lq9'] = train_and_infer(small, 3, 40, 9, bf16=True)
+    cases['launchers:separate-calls-B3-T40-Lq9'] = separate_calls(small, 3, 40, 9)
+    cases['launchers:char100-wd52-B3-T56-Lq40'] = train_and_infer(dict(small, char_dim=100, word_dim=52), 3, 56, 40)
+    cases['launchers:B3-T64-Lq100'] = train_and_infer(small, 3, 64, 100)
     with open(out_path, 'w') as f:
         json.dump(cases, f)
 

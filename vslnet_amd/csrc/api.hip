@@ -319,9 +319,9 @@ int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_str
     const bool shared = !io->inference && h->last_fwd == vsl_handle_s::FwdShared;      // (the outputs of vsl_forward_shared: vsl_io.v_mask is the (B, T) per-query mask)
     if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, io->inference ? PlanKind::Infer : shared ? PlanKind::TrainShared : PlanKind::Train, h->shared_N)) return rc;      // (its scratch lies where that forward's plan put it)
     ProfScope ps(h, "loss");
-    launch_loss(io->start_logits, io->end_logits, io->h_score, l->start_labels, l->end_labels, l->h_labels, io->v_mask, io->B,
-                io->T, l->inv_batch, l->mask_sum, l->w_loc, l->w_highlight, io->workspace + p->loss_scratch, l->losses,
-                l->d_start_logits, l->d_end_logits, l->d_h_score, (hipStream_t)hip_stream, h->loss_counter);
+    launch_loss(LossArgs{io->start_logits, io->end_logits, io->h_score, l->start_labels, l->end_labels, l->h_labels, io->v_mask, io->B, io->T, l->inv_batch,
+                         l->mask_sum, l->w_loc, l->w_highlight, io->workspace + p->loss_scratch, l->losses, l->d_start_logits, l->d_end_logits, l->d_h_score,
+                         h->loss_counter}, (hipStream_t)hip_stream);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -369,9 +369,9 @@ int vsl_adamw_step(vsl_handle h, float* params, const float* grads, float* exp_a
         sq = h->sq_src;             // (null when some gradient of this configuration does not leave k_reduce: the k_sqsum pass then)
     }
     ProfScope ps(h, "adamw");
-    launch_adamw(params, grads, exp_avg, exp_avg_sq, h->decay_dev, h->opt_scratch, h->param_floats, hp->lr, hp->beta1, hp->beta2,
-                 hp->eps, hp->weight_decay, hp->clip_norm, (float)bc1, (float)std::sqrt(bc2), grad_norm_out, (hipStream_t)hip_stream,
-                 hp->hf_order, sq, h->sq_n);
+    launch_adamw(AdamwArgs{params, grads, exp_avg, exp_avg_sq, h->decay_dev, h->opt_scratch, h->param_floats, hp->clip_norm,
+                           AdamHp{hp->lr, hp->beta1, hp->beta2, hp->eps, hp->weight_decay, (float)bc1, (float)std::sqrt(bc2), hp->hf_order}, grad_norm_out, sq,
+                           h->sq_n}, (hipStream_t)hip_stream);
     if (hipGetLastError() != hipSuccess) return fail("vsl_adamw_step: launch failed");
     return 0;
 }

@@ -24,9 +24,9 @@ void loss_on_side(Ctx& c, Pending& pd) {
     const vsl_loss_io* fl = pd.loss;
     if (!fl) return;
     pd.loss = nullptr;
-    LAUNCH("loss", launch_loss(c.start_logits(), c.end_logits(), c.h_score(), fl->start_labels, fl->end_labels, fl->h_labels, c.v_mask(), c.p->B, c.p->T,
-                               fl->inv_batch, fl->mask_sum, fl->w_loc, fl->w_highlight, c.W(c.p->loss_scratch), fl->losses, fl->d_start_logits,
-                               fl->d_end_logits, fl->d_h_score, c.s, c.h->loss_counter));
+    LAUNCH("loss", launch_loss(LossArgs{c.start_logits(), c.end_logits(), c.h_score(), fl->start_labels, fl->end_labels, fl->h_labels, c.v_mask(), c.p->B, c.p->T,
+                                        fl->inv_batch, fl->mask_sum, fl->w_loc, fl->w_highlight, c.W(c.p->loss_scratch), fl->losses, fl->d_start_logits,
+                                        fl->d_end_logits, fl->d_h_score, c.h->loss_counter}, c.s));
 }
 // Every cross-stream ordering point (event record on the producer + wait on the consumer) leaves a ~6-7 us bubble in the
 // producer stream (rocprofv3 timeline), so weight-gradient batches -- nothing waits for them before the final reduction --
@@ -125,7 +125,7 @@ void enc_bwd(Ctx& c, Pending& pd, const EncP& P, const EncPk& K, const EncWs& w,
     const int ntiles = (R + TILE_M - 1) / TILE_M;
     if (!o.attn_out_done) {
         const AttnOutBwdArgs ao = attn_out_bwd_args(c, P, K, w, dy, dy2, app);
-        LAUNCH("attn_out_bwd", launch_attn_out_bwd(ao.dy, ao.dy2, ao.r_in, ao.ln_g, ao.WTpack, ao.g_o, ao.dr, ao.p_lng, ao.p_lnb, R, ao.d4, ao.d5, c.s));
+        LAUNCH("attn_out_bwd", launch_attn_out_bwd(ao, R, c.s));
     }
     // every head count, every L: key-major dK / dV; dQ as attn_dq_slabs(L) slabs (L > ATTN_SLAB_MAX_L: query-major into slab 0, kernels_attn.hip)
     LAUNCH("attn_bwd", launch_attn_bwd(AttnArgs{c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.W(w.lse), c.W(t.dr), c.W(t.dq), c.W(t.dk), c.W(t.dv),
@@ -225,6 +225,7 @@ void query_bwd(Ctx& c, const float* dy, int64_t dx0_off, WgradBatch& jobs) {
 // vsl_io.fused_loss: the loss is part of this call.  Whole tiles + the caller's mask sum (`inline_fl`): k_loss_fused leaves the dependent chain
 // (nothing on it reads what the kernel writes; run_backward launches it at the end of the query chain) and the consumers compute the seeds from the
 // logits themselves.  Otherwise the loss launches first, here, on the caller's stream, and the seeds are read from memory as they always were.
+struct HlSeed { const int64_t* h_lab; const float* vmask; float w_hl, mask_sum; };     // (the inline highlight seed of CqcatBwdArgs: cqcat_bwd_args copies it in)
 struct LossSeeds {
     const float *s, *e, *h;             // dLoss / d start_logits, end_logits, h_score in memory
     const vsl_loss_io* inline_fl;       // non-null: computed in the consumers from the logits and these labels / weights
@@ -391,15 +392,14 @@ bool transformer_head_bwd(Ctx& c, Pending& pd, const LossSeeds& sd, hipStream_t 
 }
 
 // gating + highlight + CQConcatenate (unless a conv block hosted it: `cqcat_done`), their weight gradients -- the last batch behind the deferred
-// ordering point -- and CQAttention + WeightedPool / pooled-bias backward as four tile-parallel kernels (kernels_bwd.hip), three of them here: dC is
+// ordering point -- and CQAttention + WeightedPool / pooled-bias backward as four tile-parallel kernels (kernels_cq_bwd.hip), three of them here: dC is
 // final; the fourth (launch_cq_bwd_query, same arguments: the returned struct) opens the query chain
 CqBwdArgs fusion_bwd(Ctx& c, Pending& pd, const LossSeeds& sd, bool cqcat_done, hipStream_t sw) {
     const ModelP& P = c.h->P; const ModelPk& K = c.h->K; const Plan& p = *c.p;
     const int B = p.B, T = p.T, R = B * T, nchunk = (R + WG_ROWS - 1) / WG_ROWS;
     if (!cqcat_done) {
         const CqcatBwdArgs a = cqcat_bwd_args(c, sd, c.W(p.g_gated));
-        LAUNCH("cqcat_bwd", launch_cqcat_bwd(a.dg0, a.dg1, a.dg2, a.dh_loss, a.f2, a.hscore, a.wh, a.W1Tpack, a.df2, a.df1, a.p_wh, a.p_bh, R, c.s,
-                                             sd.hl.h_lab ? &sd.hl : nullptr));
+        LAUNCH("cqcat_bwd", launch_cqcat_bwd(a, R, c.s));
     }
     WgradBatch wb = wbatch();
     {   // first half of the (128, 256) CQConcatenate weight: destination rows are strided by 256
@@ -529,9 +529,9 @@ void query_chain_bwd(Ctx& c, Pending& pd, const CqBwdArgs& q, const WgradBatch& 
         }
         float* p_tab = c.slab(P.char_tab, cf.char_size * cf.char_dim, nce);
         float* p_unk = cf.word_table ? nullptr : c.slab(P.unk, cf.word_dim, nce);
-        LAUNCH("embed_bwd", launch_embed_bwd(c.W(p.dE), c.word_ids(), c.char_ids(), c.W(p.E), reinterpret_cast<const int8_t*>(c.W(p.argpos)),
-                                c.P(P.char_tab), c.PK(K.ccw_imgb), c.part_ptr(ow), c.part_ptr(ob), p_tab, p_unk, Rq,
-                                p.Lc, cf.word_dim, cf.char_dim, cf.char_size, c.drop(SITE_WORD), c.drop(SITE_CHAR), c.s));
+        LAUNCH("embed_bwd", launch_embed_bwd(EmbedBwdArgs{c.W(p.dE), c.word_ids(), c.char_ids(), c.W(p.E), reinterpret_cast<const int8_t*>(c.W(p.argpos)),
+                                                          c.P(P.char_tab), c.PK(K.ccw_imgb), c.part_ptr(ow), c.part_ptr(ob), p_tab, p_unk, Rq, p.Lc, cf.word_dim,
+                                                          cf.char_dim, cf.char_size, c.drop(SITE_WORD), c.drop(SITE_CHAR)}, c.s));
     }
     if (cf.word_table)
         LAUNCH("word_table_bwd", launch_word_table_bwd(c.W(p.dE), c.word_ids(), c.grads() + P.unk, Rq, cf.word_size, cf.word_dim, c.drop(SITE_WORD), c.s));
@@ -586,9 +586,9 @@ void run_backward(Ctx& c) {
     // they cover the whole bucket)
     const vsl_adamw& hp = fs->hp;
     const float bc1 = (float)(1.0 - std::pow((double)hp.beta1, (double)hp.step)), bc2s = (float)std::sqrt(1.0 - std::pow((double)hp.beta2, (double)hp.step));
-    LAUNCH("adamw", launch_adamw(fs->params, c.grads(), fs->exp_avg, fs->exp_avg_sq, c.h->decay_dev, c.h->opt_scratch, c.h->param_floats, hp.lr,
-                                 hp.beta1, hp.beta2, hp.eps, hp.weight_decay, hp.clip_norm, bc1, bc2s, fs->grad_norm_out, c.s, hp.hf_order,
-                                 p.sq_cover ? p.sq_dev : nullptr, p.nblocks));
+    LAUNCH("adamw", launch_adamw(AdamwArgs{fs->params, c.grads(), fs->exp_avg, fs->exp_avg_sq, c.h->decay_dev, c.h->opt_scratch, c.h->param_floats, hp.clip_norm,
+                                           AdamHp{hp.lr, hp.beta1, hp.beta2, hp.eps, hp.weight_decay, bc1, bc2s, hp.hf_order}, fs->grad_norm_out,
+                                           p.sq_cover ? p.sq_dev : nullptr, p.nblocks}, c.s));
 }
 
 }  // namespace vsl

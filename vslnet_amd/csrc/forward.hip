@@ -38,8 +38,8 @@ static void enc_fwd(Ctx& c, const EncP& P, const EncPk& K, const EncWs& w, const
     // every other head count, and longer sequences (K / V staged in LDS per 64 queries): the attention core, then the output block
     LAUNCH("attn_fwd", launch_attn_fwd(AttnArgs{c.W(w.q), c.W(w.k), c.W(w.v), mask, c.W(w.att), c.SV(w.lse), nullptr, nullptr, nullptr, nullptr, Bn, L, H, 0,
                                                 c.drop(app * 16 + 5), Drop{}}, c.s));
-    LAUNCH("attn_out_fwd", launch_attn_out_fwd(c.W(w.att), c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob), c.SV(w.r), c.SV(w.h2),
-                        yout, R, c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8), c.s));
+    LAUNCH("attn_out_fwd", launch_attn_out_fwd(AttnOutFwdArgs{c.W(w.att), c.W(w.y[3]), c.P(P.ln2g), c.P(P.ln2b), c.PK(K.o_f), c.P(P.ob), c.SV(w.r), c.SV(w.h2), yout,
+                                                              c.drop(app * 16 + 6), c.drop(app * 16 + 7), c.drop(app * 16 + 8)}, R, c.s));
 }
 
 static CharConvPtrs char_ptrs(const Ctx& c) {
@@ -118,9 +118,10 @@ static void query_branch(Ctx& c, PackWait emb_pack) {
     const Plan& p = *c.p; const vsl_io& io = *c.io;
     const int B = p.B, Lq = p.Lq, Rq = B * Lq;
     const bool wt = cf.word_table != 0;       // trainable word table: its rows 0, 1, 2.. are pad, unk, the vocabulary
-    LAUNCH("embed_fwd", launch_embed_fwd(io.word_ids, io.char_ids, wt ? c.P(P.unk) : io.pad_vec, c.P(P.unk) + (wt ? cf.word_dim : 0), wt ? c.P(P.unk) + 2 * cf.word_dim : io.glove_vec, c.P(P.char_tab), char_ptrs(c), c.PK(K.ccw_img), c.W(p.E),
-                     reinterpret_cast<int8_t*>(c.SV(p.argpos)), Rq, p.Lc, cf.word_dim, cf.char_dim, c.drop(SITE_WORD),
-                     c.drop(SITE_CHAR), c.s));
+    const float* tab = c.P(P.unk);            // (word table: P.unk is its first row)
+    LAUNCH("embed_fwd", launch_embed_fwd(EmbedFwdArgs{io.word_ids, io.char_ids, wt ? tab : io.pad_vec, tab + (wt ? cf.word_dim : 0), wt ? tab + 2 * cf.word_dim : io.glove_vec,
+                                                      c.P(P.char_tab), char_ptrs(c), c.PK(K.ccw_img), c.W(p.E), reinterpret_cast<int8_t*>(c.SV(p.argpos)), Rq, p.Lc,
+                                                      cf.word_dim, cf.char_dim, c.drop(SITE_WORD), c.drop(SITE_CHAR)}, c.s));
     if (emb_pack.ev) {                // behind embed_fwd, which reads the char-conv image alone
         (void)hipStreamWaitEvent(c.s, emb_pack.ev, 0); c.h->mark_waiting(c.s);
         if (emb_pack.rec >= 0) c.h->prof_pending.push_back({c.s, emb_pack.rec});
@@ -165,17 +166,19 @@ static void fuse_and_predict(Ctx& c, CqContext ctx) {
     // one launch and one boundary less on the dependent chain (VSL_CQ_FOLD=0: three launches)
     static const bool fold_on = switch_on("VSL_CQ_FOLD", true);
     const bool cq_fold = fold_on && cq_col_folds(T, Lq);
-    const CqPoolArgs pool{c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb)};
-    LAUNCH("cq_score", launch_cq_score(ctx.C, c.W(p.qe.out), io.q_mask, c.P(P.w4C), c.P(P.w4Q), c.P(P.w4mlu), c.W(p.S), c.W(p.Srow), B, T,
-                    Lq, 0, c.drop(SITE_CQ_C), c.drop(SITE_CQ_Q), c.s, cq_fold ? &pool : nullptr, ctx.vidx));
-    // M = S_col^T C is produced as per-tile partials (the backward's cqP1 arena is free until then) and summed by cq_out
-    if (!cq_fold)
-        LAUNCH("cq_col", launch_cq_col(ctx.C, c.W(p.qe.out), c.W(p.S), io.v_mask, io.q_mask, c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b),
-                      c.SV(p.Scol), c.W(p.cqP1), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb), B, T, Lq, c.s, ctx.vidx));
+    CqFwdArgs cq;
+    cq.C = ctx.C; cq.vidx = ctx.vidx; cq.Qf = c.W(p.qe.out); cq.vmask = io.v_mask; cq.qmask = io.q_mask;
+    cq.w4C = c.P(P.w4C); cq.w4Q = c.P(P.w4Q); cq.w4mlu = c.P(P.w4mlu);
+    cq.S = c.W(p.S); cq.Srow = c.W(p.Srow); cq.Scol = c.SV(p.Scol);
+    cq.Mpart = c.W(p.cqP1); cq.M = c.SV(p.M);       // the per-tile partials of M go where the backward's cqP1 arena is free until then
+    cq.pool = CqPoolArgs{c.P(P.pool_w), c.P(P.cat_w), c.P(P.cat_b), c.SV(p.alpha), c.SV(p.pooled), c.W(p.pb)};
+    cq.Wcqa = c.PK(K.cqa_f); cq.bcqa = c.P(P.cqa_b); cq.W1pack = c.PK(K.cat1_f); cq.wh = c.P(P.hl_w); cq.bh = c.P(P.hl_b);
+    cq.cat = c.SV(p.cat); cq.f1 = c.SV(p.f1); cq.f2 = c.SV(p.f2); cq.hscore = io.h_score; cq.gated = c.W(p.gated);
+    cq.B = B; cq.T = T; cq.Lq = Lq; cq.b_off = 0; cq.dc = c.drop(SITE_CQ_C); cq.dq = c.drop(SITE_CQ_Q); cq.fold = cq_fold;
+    LAUNCH("cq_score", launch_cq_score(cq, c.s));
+    if (!cq_fold) LAUNCH("cq_col", launch_cq_col(cq, c.s));
     // cq_out also carries CQConcatenate + HighLightLayer + gating (row-local on the tile it produces)
-    LAUNCH("cq_out", launch_cq_out(ctx.C, c.W(p.qe.out), c.W(p.Srow), c.W(p.cqP1), c.SV(p.M), c.PK(K.cqa_f), c.P(P.cqa_b), c.SV(p.cat),
-                  c.SV(p.f1), c.PK(K.cat1_f), c.W(p.pb), c.P(P.hl_w), c.P(P.hl_b), io.v_mask, c.SV(p.f2), io.h_score, c.W(p.gated), B, T, Lq,
-                  c.s, cq_fold ? c.W(p.S) : nullptr, cq_fold ? c.SV(p.Scol) : nullptr, ctx.vidx));
+    LAUNCH("cq_out", launch_cq_out(cq, c.s));
     if (cf.predictor == 0) {
         // rnn head (:341-343): start = LSTM_s(x) * mask ; end = LSTM_e(start) * mask ; no LayerNorm in front of the span blocks
         // The recurrence is latency bound (one sample per CU, 0.6 us per step).  Up to RNN_FUSED_MAX_B samples the whole head is ONE launch: start

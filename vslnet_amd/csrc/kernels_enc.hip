@@ -1655,7 +1655,7 @@ __global__ __launch_bounds__(1024 / QB, QB) void k_attn_block_fwd(AttnBlockArgs 
     }
 }
 void launch_attn_block_fwd(const AttnBlockArgs& a, int B, hipStream_t s) {
-    // L <= 128 only: 16 waves (wave = head x 16-query block).  Longer sequences take k_attn_fwd (kernels_attn_h16.hip) + k_attn_out_fwd (kernels_fwd.hip); the 8-wave
+    // L <= 128 only: 16 waves (wave = head x 16-query block).  Longer sequences take k_attn_fwd (kernels_attn_h16.hip) + k_attn_out_fwd (kernels_head.hip); the 8-wave
     // instantiation that served 128 < L <= 256 until round 6 is gone (-0.6 % on configs[2] / [3] without it: profiles/r06_notes.md section 9).
     const dim3 grid((a.L + TILE_M - 1) / TILE_M, B);
     const size_t shm = (size_t)((a.L + 15) & ~15) * sizeof(float);

@@ -24,7 +24,6 @@ struct PackJob {          // one weight -> packed B-operand copy (see common.hpp
 };
 
 struct CharConvPtrs { const float* w[4]; const float* b[4]; };
-struct CharConvGrads { float* w[4]; float* b[4]; };
 
 struct HeadArgs {
     const float* feat;    // (R,128) encoder / rnn features
@@ -149,9 +148,20 @@ void launch_vproj_fwd3(const float* X, const uint16_t* W3, const float* bias, fl
 void launch_linear_fwd3(const float* A, const uint16_t* W3, const float* bias /* nullable */, float* Y, int R, int K, hipStream_t s, int ncols = 128,
                         int seg = 0, int stride = 0, int off = 0);      // ncols: columns of the operand and of Y's rows; seg > 0: rows of one time chunk of a (B, T, .) tensor
 void launch_linear_bwd_data3(const float* G, const uint16_t* WT3, float* dA, int R, int K, int Kc, hipStream_t s);   // Kc: columns of the split pack
-void launch_embed_fwd(const int64_t* word_ids, const int64_t* char_ids, const float* pad_vec, const float* unk_vec,
-                      const float* glove, const float* char_tab, CharConvPtrs cc, const float* wimg, float* E, int8_t* argpos,
-                      int Rq, int Lc, int word_dim, int char_dim, Drop dw, Drop dc, hipStream_t s);
+// word + character embedding of the query words (kernels_embed.hip)
+struct EmbedFwdArgs {
+    const int64_t *word_ids, *char_ids;   // (Rq), (Rq, Lc)
+    const float *pad_vec, *unk_vec, *glove;   // rows 0, 1 and 2.. of the [pad; unk; glove] table (the caller's vectors, or the trainable word table's rows)
+    const float* char_tab;
+    CharConvPtrs cc;                      // the four char convs' weights and biases in the parameter buffer
+    const float* wimg;                    // their weights as the [ci][4 taps][100 channels] image (PackJob type 3)
+    float* E;                             // (Rq, word_dim + 100) out
+    int8_t* argpos;                       // (Rq, 100) arg-max position per channel, saved (nullable: an inference forward does not store it)
+    int Rq, Lc, word_dim, char_dim;
+    Drop dw, dc;
+};
+void launch_embed_fwd(const EmbedFwdArgs& a, hipStream_t s);
+// the Embedding linear at a width the split kernel's 16-wide K steps do not tile (kernels_embed.hip)
 void launch_linear_fwd(const float* A, const float* Wpack, const float* bias, float* Y, int R, int K, hipStream_t s);
 // LN1 + fused QKV projection at the end of the conv-block kernel (row-local on the owner rows)
 struct QkvFuse {
@@ -180,7 +190,7 @@ struct AttnOutBwdArgs {
     float *g_o, *dr, *p_lng, *p_lnb;
     Drop d4, d5;
 };
-// gating + HighLightLayer + CQConcatenate backward of one 32-row tile (kernels_bwd.hip k_cqcat_bwd / tile_bodies.hpp cqcat_bwd_tile)
+// gating + HighLightLayer + CQConcatenate backward of one 32-row tile (kernels_cq_bwd.hip k_cqcat_bwd / tile_bodies.hpp cqcat_bwd_tile)
 struct CqcatBwdArgs {
     const float *dg0, *dg1, *dg2, *dh_loss, *f2, *hscore, *wh, *W1Tpack;
     float *df2, *df1, *p_wh, *p_bh;
@@ -246,10 +256,14 @@ void launch_attn_bwd(const AttnArgs& a, hipStream_t s);
 int attn_bwd_dq_slabs(int L);
 int attn_dq_slabs(int L);
 inline bool attn_heads_supported(int H) { return H == 1 || H == 2 || H == 4 || H == 8 || H == 16; }
-// (r_out / h2_out may be null: an inference forward does not store them)
-void launch_attn_out_fwd(const float* att, const float* x, const float* ln_g, const float* ln_b, const float* Wpack,
-                         const float* bo, float* r_out, float* h2_out, float* y_out, int R, Drop d3, Drop d4, Drop d5,
-                         hipStream_t s);
+// the attention-output block of one encoder application as a launch of its own (a8 :183-190; kernels_head.hip): L > 128 or H != 8
+struct AttnOutFwdArgs {
+    const float *att, *x;                 // (R,128) attention output ; residual input = the conv block's output
+    const float *ln_g, *ln_b, *Wpack, *bo;   // LN2 ; out_layer (forward pack), its bias
+    float *r_out, *h2_out, *y_out;        // saved r = drop(att) + x and h2 = drop(LN2(r)) (nullable: an inference forward does not store them) ; block output
+    Drop d3, d4, d5;
+};
+void launch_attn_out_fwd(const AttnOutFwdArgs& a, int R, hipStream_t s);
 // attention core + output block of one encoder application in one launch (kernels_enc.hip)
 struct AttnBlockArgs {
     const float *Q, *K, *V, *mask, *x;            // q, k, v (R,128) ; key mask (B, L) ; residual input x = conv-block output
@@ -294,32 +308,50 @@ struct QueryFwdArgs {
 };
 bool query_fused_ok(int L, int H, int EW);         // does the sample-local path take this query length / embedding width?
 void launch_query_fwd(const QueryFwdArgs& a, int B, hipStream_t s);
-// the column kernel folded away (cq_col_folds): k_cq_score gets one extra workgroup per sample for the WeightedPool / pooled-bias path (`pool`),
-// k_cq_out computes the sample's column softmax and M itself (S_fold / Scol_fold) and launch_cq_col is not called
-struct CqPoolArgs { const float *pool_w, *Wcat, *bcat; float *alpha, *pooled, *pb; };
+// CQAttention + WeightedPool + CQConcatenate + HighLightLayer + gating (kernels_cq.hip): cq_score, [cq_col,] cq_out read ONE struct, filled once.
+struct CqPoolArgs { const float *pool_w, *Wcat, *bcat; float *alpha, *pooled, *pb; };      // a11's WeightedPool and the pooled half of CQConcatenate's Conv1D
 bool cq_col_folds(int T, int Lq);
-// (nullable in the three CQ launchers -- read by the backward alone: alpha, pooled, Scol / Scol_fold, M, cat_out, out, f2)
-// vidx (nullable, device, B ints; vsl_localize): C is a resident (N, T, 128) encoding and sample b reads the rows of video vidx[b] (0 <= vidx[b] < N is the
-// caller's precondition); every output stays per sample.  nullptr: C is (B, T, 128) -- the instantiations of the training / inference forward.
-void launch_cq_score(const float* C, const float* Qf, const float* qmask, const float* w4C, const float* w4Q,
-                     const float* w4mlu, float* S, float* Srow, int B, int T, int Lq, int b_off, Drop dc, Drop dq,
-                     hipStream_t s, const CqPoolArgs* pool = nullptr, const int* vidx = nullptr);
-void launch_cq_col(const float* C, const float* Qf, const float* S, const float* cmask, const float* qmask,
-                   const float* pool_w, const float* Wcat, const float* bcat, float* Scol, float* Mpart /*[B][ntile][Lq][128]*/,
-                   float* alpha, float* pooled, float* pb, int B, int T, int Lq, hipStream_t s, const int* vidx = nullptr);
-void launch_cq_out(const float* C, const float* Qf, const float* Srow, const float* Mpart, float* M, const float* Wpack,
-                   const float* bias, float* cat_out, float* out, const float* W1pack, const float* pb, const float* wh,
-                   const float* bh, const float* vmask, float* f2, float* hscore, float* gated, int B, int T, int Lq, hipStream_t s,
-                   const float* S_fold = nullptr, float* Scol_fold = nullptr, const int* vidx = nullptr);
+// (nullable -- read by the backward alone, an inference forward does not store them: pool.alpha, pool.pooled, Scol, M, cat, f1, f2)
+struct CqFwdArgs {
+    const float* C;                       // the context: (B, T, 128), or with vidx a resident (N, T, 128) encoding
+    const int* vidx;                      // nullable, device, B ints (vsl_localize / shared step): sample b reads the rows of video vidx[b] (0 <= vidx[b] < N is the
+                                          // caller's precondition); every output stays per sample.  nullptr: the instantiations of the training / inference forward
+    const float* Qf;                      // (B, Lq, 128) encoded query
+    const float *vmask, *qmask;           // (B, T) clip mask, (B, Lq) word mask
+    const float *w4C, *w4Q, *w4mlu;       // trilinear weights
+    float *S, *Srow, *Scol;               // (B, T, Lq) raw score, row softmax, column softmax
+    float *Mpart, *M;                     // [B][ntile][Lq][128] per-tile partials of M = S_col^T C (unfolded column kernel) ; M (B, Lq, 128)
+    CqPoolArgs pool;
+    const float *Wcqa, *bcqa;             // cqa_linear (forward pack, 4d -> d), its bias
+    const float* W1pack;                  // first half of CQConcatenate's (128, 256) weight (forward pack); its pooled half and bias: pool.Wcat / pool.bcat
+    const float *wh, *bh;                 // HighLightLayer
+    float *cat, *f1, *f2;                 // (R, 512) concat tile, A operand of the cqa_linear weight gradient ; (R,128) CQAttention / CQConcatenate output
+    float *hscore, *gated;                // (B, T) ; (R,128) = f2 * hscore
+    int B, T, Lq, b_off;
+    Drop dc, dq;                          // on C and on Qf in the trilinear score
+    int fold;                             // the column kernel folded away (cq_col_folds): k_cq_score gets one extra workgroup per sample for the WeightedPool /
+                                          // pooled-bias path, k_cq_out computes the sample's column softmax and M itself from S and launch_cq_col is not called
+};
+void launch_cq_score(const CqFwdArgs& a, hipStream_t s);
+void launch_cq_col(const CqFwdArgs& a, hipStream_t s);
+void launch_cq_out(const CqFwdArgs& a, hipStream_t s);
 // out (B, T) = vmask (N, T) rows vidx[b]: the per-query copy of a resident encoding's clip mask (vsl_localize)
 void launch_vmask_gather(const float* vmask, const int* vidx, float* out, int B, int T, hipStream_t s);
 void launch_head_fwd(const HeadArgs& a0, const HeadArgs& a1, const float* x, const float* vmask, int R, hipStream_t s);
 
 // ---------------------------------------------------------------- losses / eval
-void launch_loss(const float* sl, const float* el, const float* h, const int64_t* s_lab, const int64_t* e_lab,
-                 const int64_t* h_lab, const float* vmask, int B, int T, float inv_batch, float mask_sum_override,
-                 float w_loc, float w_hl, float* scratch, float* losses /*[4]: loc, hl, total, mask_sum*/, float* d_sl,
-                 float* d_el, float* d_h, hipStream_t s, unsigned* counter = nullptr);
+struct LossArgs {
+    const float *sl, *el, *h;             // (B, T) start / end logits, highlight score
+    const int64_t *s_lab, *e_lab, *h_lab; // (B), (B), (B, T)
+    const float* vmask;                   // (B, T)
+    int B, T;
+    float inv_batch, mask_sum;            // mask_sum > 0: the caller's (global) mask sum ; otherwise the device sums vmask
+    float w_loc, w_hl;
+    float *scratch, *losses;              // 5 B floats (kernels_head.hip) ; [4]: loc, hl, total, mask_sum
+    float *d_sl, *d_el, *d_h;             // gradient seeds (all null: the losses alone)
+    unsigned* counter;                    // arrival counter of the one-launch path (nullable: k_loss_a, then k_loss_c or k_loss_b)
+};
+void launch_loss(const LossArgs& a, hipStream_t s);
 void launch_extract_index(const float* sl, const float* el, int64_t* si, int64_t* ei, int B, int T, hipStream_t s);
 
 // ---------------------------------------------------------------- backward
@@ -369,15 +401,11 @@ bool rnn_fused_ok(int B);
 void launch_rnn_fwd(const RnnFwdArgs& a, hipStream_t s);
 void launch_rnn_bwd(const RnnBwdArgs& a, hipStream_t s);      // one image = W_hh in the register order of k_lstm1_fwd (type 9) / k_lstm1_bwd (type 10)
 void launch_wgrad(const WgradBatch& wb, hipStream_t s);     // kernels_wgrad.hip
-void launch_attn_out_bwd(const float* dy, const float* dy2, const float* r, const float* ln_g, const float* WTpack, float* g_o,
-                         float* dr, float* p_lng, float* p_lnb, int R, Drop d4, Drop d5, hipStream_t s);
+void launch_attn_out_bwd(const AttnOutBwdArgs& a, int R, hipStream_t s);
 void launch_qkv_bwd(const float* dQ, const float* dK, const float* dV, const float* x, const float* dr,
                     const float* ln_g, const uint16_t* WT3 /* split pack of the (384, 128) operand */, float* dx, float* p_lng, float* p_lnb, int R,
                     Drop d1, hipStream_t s, int dq_slabs = 1);
-struct HlSeed { const int64_t* h_lab; const float* vmask; float w_hl, mask_sum; };     // (CqcatBwdArgs' inline highlight seed)
-void launch_cqcat_bwd(const float* dg0, const float* dg1, const float* dg2, const float* dh_loss, const float* f2,
-                      const float* hscore, const float* wh, const float* W1Tpack, float* df2, float* df1, float* p_wh,
-                      float* p_bh, int R, hipStream_t s, const HlSeed* hl = nullptr);
+void launch_cqcat_bwd(const CqcatBwdArgs& a, int R, hipStream_t s);
 struct CqBwdArgs {
     const float *df1, *df2, *C, *Qf, *Srow, *Scol, *M, *alpha, *pooled;      // saved forward tensors / incoming grads
     const float *WcqaT;                                                        // transpose pack of cqa_linear (ncols 512)
@@ -428,26 +456,39 @@ struct QueryBwdArgs {
     int EW, EWc, L, b_off;
 };
 void launch_query_bwd(const QueryBwdArgs& a, int B, hipStream_t s);
-void launch_embed_bwd(const float* dE, const int64_t* word_ids, const int64_t* char_ids, const float* E,
-                      const int8_t* argpos, const float* char_tab, const float* wimg_b /* type-8 pack */,
-                      float* p_cw /*[nchunk][300 char_dim]*/,
-                      float* p_cb /*[nchunk][100]*/, float* p_tab /*[nchunk][char_size*char_dim]*/,
-                      float* p_unk /*[nchunk][word_dim]*/, int Rq, int Lc, int word_dim, int char_dim, int char_size, Drop dw,
-                      Drop dc, hipStream_t s);
+struct EmbedBwdArgs {
+    const float* dE;                      // (Rq, word_dim + 100) grad wrt the concatenated embedding rows
+    const int64_t *word_ids, *char_ids;
+    const float* E;                       // forward output (relu mask of the char channels)
+    const int8_t* argpos;                 // (Rq, 100) saved arg-max positions
+    const float *char_tab, *wimg_b;       // wimg_b: char-conv B-operand image (PackJob type 8)
+    float *p_cw, *p_cb;                   // partial slabs [nchunk][300 char_dim], [nchunk][100]
+    float *p_tab, *p_unk;                 // [nchunk][char_size * char_dim], [nchunk][word_dim] (p_unk nullable: trainable word table -> launch_word_table_bwd)
+    int Rq, Lc, word_dim, char_dim, char_size;
+    Drop dw, dc;
+};
+void launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s);
 void launch_word_table_bwd(const float* dE, const int64_t* word_ids, float* gtab /*(word_size, word_dim) inside the gradient bucket*/, int Rq,
                            int word_size, int word_dim, Drop dw, hipStream_t s);
 void launch_reduce(const float* partial, float* grads, const ReduceSeg* segs_dev, const int* blk2seg_dev, int nblocks,
                    float* sq /* [nblocks]: sum of squares of each block's results */, hipStream_t s);
 // fused optimizer (vsl_adamw_step): sum of squares partials, then clip + AdamW
 constexpr int OPT_BLOCKS = 256;
-void launch_adamw(float* params, const float* grads, float* m, float* v, const uint8_t* decay_mask, float* partials /*[OPT_BLOCKS + 1]*/,
-                  int64_t n, float lr, float b1, float b2, float eps, float wd, float clip, float bc1, float bc2_sqrt,
-                  float* norm_out, hipStream_t s, int hf_order = 0,
-                  const float* sq_from_backward = nullptr /* k_reduce's partials instead of a k_sqsum pass */, int nsq = 0);
+struct AdamHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; int hf_order; };      // bc1 = 1 - b1^step ; bc2_sqrt = sqrt(1 - b2^step)
+struct AdamwArgs {
+    float* params; const float* grads; float *m, *v;
+    const uint8_t* decay_mask;
+    float* partials;                      // [OPT_BLOCKS + 1] scratch of the k_sqsum pass
+    int64_t n;
+    float clip;                           // clip_grad_norm_ bound (<= 0: none)
+    AdamHp hp;
+    float* norm_out;                      // nullable
+    const float* sq_from_backward; int nsq;   // k_reduce's nsq partials instead of a k_sqsum pass (nullable)
+};
+void launch_adamw(const AdamwArgs& a, hipStream_t s);
 constexpr int EMB_CHUNK_MAX = 8;  // most query words per workgroup in the embedding backward
 int embed_bwd_chunk(int Rq, int Lc, int char_dim);      // words per workgroup the launcher uses (the number of partial slabs follows from it)
 constexpr int EB_IMG_Q = 76;      // k-steps of the embedding backward's B-operand image ([channel tile][76][64 lanes], PackJob type 8)
-constexpr int CHARW_TOTAL = 15000;
 
 // A switch of the environment: VSL_X=0 turns off what is on by default, VSL_X=1 turns on what is off, anything else leaves the default.  A call
 // site keeps the answer in a function-local static, so that a process reads each switch once.

@@ -224,7 +224,7 @@ void build_packs(vsl_handle_s* h) {
         h->jobs.push_back(j);
         oc0 += chn[i];
     }
-    // the same weights as the B operands of the embedding backward's dCe product, in lane order (kernels_fwd.hip, type 8)
+    // the same weights as the B operands of the embedding backward's dCe product, in lane order (kernels_params.hip k_pack, type 8)
     K.ccw_imgb = (int)h->pack_floats;
     const int ebn = ((c.char_dim + 15) / 16) * EB_IMG_Q * 64;
     h->pack_floats += ebn;

@@ -77,7 +77,7 @@ __device__ __forceinline__ void attn_out_bwd_tile(const AttnOutBwdArgs& a, const
     ln_bwd_tile(Gs, Xs, lres, a.ln_g, a.dr, a.p_lng, a.p_lnb, r0, R, nullptr, active);
 }
 
-// The loss of one element (kernels_bwd.hip k_loss_*) and its seeds (there, and inline in k_head_bwd / cqcat_bwd_tile): one definition.
+// The loss of one element (kernels_head.hip k_loss_*) and its seeds (there, and inline in k_head_bwd / cqcat_bwd_tile): one definition.
 // CrossEntropy seed of logit x at position t (mean over the batch folded into cs = w_loc * inv_batch)
 __device__ __forceinline__ float loss_ce_seed(float x, float lse, int t, int label, float cs) { return cs * (expf(x - lse) - (t == label ? 1.f : 0.f)); }
 // highlight (weighted BCE, VSLNet_t7.py / layers_t7.py:291-299): weight of label y (:293)
