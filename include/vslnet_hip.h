@@ -73,7 +73,7 @@ typedef struct {
     const float* d_h_score;        /* (B, T) dLoss/dh_score      (nullable = zeros)                                */
     const float* d_start_logits;   /* (B, T)                                                                        */
     const float* d_end_logits;     /* (B, T)                                                                        */
-    float* grads;                  /* flat gradient bucket, same layout as `params` (overwritten, not accumulated) */
+    float* grads;                  /* flat gradient bucket, same layout as `params` (overwritten; vsl_backward_accumulate adds) */
     /* data parallel: index of this shard's first sample in the GLOBAL batch.  The dropout element counters continue
      * from it, so for one seed the masks -- and with the global loss normalisers the summed gradient -- do not depend
      * on how many ranks the batch is split over (shards keep the global padded T / Lq / Lc).  0 = single process.  */
@@ -233,6 +233,25 @@ int64_t vsl_shared_workspace_offset(vsl_handle h, int B, int N, int T, int Lq, i
 int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_stream);
 /* autograd backward of everything in vsl_forward (main_t7.py:110); needs the same io (workspace, seed) */
 int vsl_backward(vsl_handle h, const vsl_io* io, void* hip_stream);
+/* GRADIENT ACCUMULATION: one optimizer step over K micro-batches (no reference counterpart: main_t7.py steps once per batch).  vsl_backward_accumulate is
+ * vsl_backward (sh = NULL, after vsl_forward) or vsl_backward_shared (sh = the step's vsl_shared_io, after vsl_forward_shared) with ONE difference:
+ * what the call would store in io->grads is ADDED to what the bucket holds.  A step is then: the first micro-batch through vsl_backward (it overwrites:
+ * nothing has to be zeroed), every further one through this call, each after its own forward.  With the GLOBAL normalisers in vsl_loss_io, the
+ * micro-batch's first row as vsl_io.sample_offset and one seed for the step, a micro-batch is a data-parallel shard run in sequence: the accumulated
+ * bucket is the gradient of the whole batch up to fp32 summation order.
+ *   - io->grads must hold the running sum on the caller's stream (the earlier calls of the step, enqueued there);
+ *   - add order: every element's new value is  previous + s,  s = what vsl_backward would have stored (the same slab sums in the same order), as one
+ *     fp32 add.  After calls 0 .. K-1 the bucket holds ((g0 + g1) + g2) + ...; there is no float atomic, two runs of a step give identical bits.  With
+ *     word_table = 1 the rows of the table that no word of the micro-batch touches keep their value;
+ *   - fused_loss works as in vsl_backward;
+ *   - fused_step applies clip + AdamW to the ACCUMULATED bucket, with the norm of the accumulated bucket (the reduction records the squares of the
+ *     values it stores).  Setting it is how the caller marks the last micro-batch of the step;
+ *   - early_grads_event (sh = NULL only) is allowed: the early block holds its accumulated value when the event fires;
+ *   - afterwards vsl_adamw_step(norm_from_backward = 1) on that bucket is valid and takes the accumulated norm.
+ * Refused: NULL grads; sh that does not match the handle's last forward (the messages of vsl_backward / vsl_backward_shared); a last forward that saved
+ * nothing.  Workspace needs and plans are those of the micro-batch's own shape: a global batch whose training plan exceeds the 2^31-float limit runs as
+ * micro-batches that fit.  Detect the feature by the presence of the symbol: VSL_ABI_VERSION does not change for an added entry point. */
+int vsl_backward_accumulate(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh /* NULL after vsl_forward */, void* hip_stream);
 /* first float offset of the parameter block whose gradients are final when vsl_io.early_grads_event fires (== vsl_param_floats()
  * when the configuration has no such block: the rnn predictor) */
 int64_t vsl_early_grad_offset(vsl_handle h);

@@ -18,6 +18,11 @@ What differs from the reference, by design:
   * `--data resident` (default): each split is uploaded to HBM once (vslnet_amd/data.py: ResidentSplit) and a batch is a
     device gather with the shapes / contents of the reference's collate functions; `--data loader` keeps the reference's
     host-side collate + per-step H2D copy (measured: 39 ms/step end to end against a 1.2 ms model step);
+  * `--accum_steps K`: one optimizer step over K micro-batches (gradient accumulation).  `--batch_size` stays the GLOBAL batch and the number of
+    steps, the schedule, the seeds and the evaluation cadence do not change; each batch runs as K contiguous pieces, every piece a data-parallel
+    shard run in sequence (global widths and normalisers, dropout counters continued at its first row), the library's backward adding to the flat
+    bucket and the last piece applying clip + AdamW to the sum.  A global batch whose workspace does not fit runs as pieces that do.  Single
+    process, `--optimizer fused`, not with `--share_videos`;
   * `--task synthetic` builds a small learnable dataset in the reference's record format (no dataset files needed).
 """
 import argparse
@@ -80,6 +85,8 @@ def build_parser():
                    '--mode train with --data resident, one process: batches grouped by video (--queries_per_video) and the training step through a '
                    'shared encoding (Engine.forward_shared): the video half runs once per video, forward and backward')
     p.add_argument('--queries_per_video', type=int, default=4, help='--mode train --share_videos: queries of one video per group of the grouped order')
+    p.add_argument('--accum_steps', type=int, default=1, help='gradient accumulation: every global batch of --batch_size runs as this many contiguous '
+                   'micro-batches and ONE optimizer step (1: off).  Single process, --optimizer fused, not with --share_videos')
     p.add_argument('--synthetic_train', type=int, default=512)
     p.add_argument('--synthetic_test', type=int, default=128)
     return p
@@ -102,9 +109,29 @@ def _to_device(batch, device):
     return [t.to(device, non_blocking=True) if torch.is_tensor(t) else t for t in batch]
 
 
+def check_accum(configs, world):
+    """--accum_steps and what it does not combine with.  -> K"""
+    accum = getattr(configs, 'accum_steps', None)
+    accum = 1 if accum is None else int(accum)          # (a configs.json from before the flag has none)
+    if accum < 1:
+        raise ValueError('--accum_steps %d: at least 1' % accum)
+    if accum > 1 and configs.mode.lower() == 'train':
+        if configs.optimizer != 'fused':
+            raise ValueError('--accum_steps > 1 with --optimizer torch is refused: autograd already accumulates into .grad there; '
+                             'the accumulated step is the production path (--optimizer fused)')
+        if world > 1:
+            raise ValueError('--accum_steps > 1 is single-process (world = %d): data parallel x accumulation needs the gradient exchange held back '
+                             'to the last micro-batch' % world)
+        if getattr(configs, 'share_videos', False):
+            raise ValueError('--accum_steps > 1 with --share_videos is refused: the shared step accumulates at the library and Engine level only '
+                             '(Engine.backward(accumulate=True))')
+    return accum
+
+
 def train(configs, dataset, features, device, world, rank, log=print):
     from vslnet_amd.model.VSLNet import VSLNet, build_optimizer_and_scheduler
     model_dir = model_home(configs)
+    accum = check_accum(configs, world)
     gen = torch.Generator().manual_seed(configs.seed)                       # same shuffle on every rank
     share = bool(getattr(configs, 'share_videos', False))
     if share:
@@ -117,12 +144,12 @@ def train(configs, dataset, features, device, world, rank, log=print):
     if configs.data == 'resident':
         train_loader = data.ResidentSplit(dataset['train_set'], features, configs, device, train=True, generator=gen)
         test_loader = data.ResidentSplit(dataset['test_set'], features, configs, device, train=False)
-        shards = (lambda: train_loader.shards(queries_per_video=configs.queries_per_video)) if share else (lambda: train_loader.shards(rank, world))
+        shards = (lambda: train_loader.shards(queries_per_video=configs.queries_per_video)) if share else (lambda: train_loader.shards(rank, world, micro_batches=accum))
         log('dataset resident in HBM: %.1f MiB train, %.1f MiB test' % (train_loader.nbytes() / 2 ** 20, test_loader.nbytes() / 2 ** 20))
     elif configs.data == 'loader':
         train_loader = data.get_train_loader(dataset['train_set'], features, configs, pin=True, generator=gen)
         test_loader = data.get_test_loader(dataset['test_set'], features, configs, pin=True)
-        shards = lambda: data.loader_shards(train_loader, device, rank, world)
+        shards = lambda: data.loader_shards(train_loader, device, rank, world, micro_batches=accum)
     else:
         raise ValueError('Unknown --data {}!!!'.format(configs.data))
     n_batches = len(train_loader)
@@ -173,6 +200,8 @@ def train(configs, dataset, features, device, world, rank, log=print):
                     batch = next(it)
                 except StopIteration:
                     break
+                # --accum_steps K: the K pieces of this global batch (one draw of the order); pieces without rows are skipped
+                micro = [batch] if accum == 1 else [b for b in [batch] + [next(it) for _ in range(accum - 1)] if b['vfeats'].shape[0]]
                 t1 = clock()
                 if trace is not None:
                     trace['batch'] += t1 - t0
@@ -180,21 +209,28 @@ def train(configs, dataset, features, device, world, rank, log=print):
                 if fused:
                     # this rank's rows, padded to the GLOBAL batch widths; the losses are normalised with the global batch
                     inv_batch, mask_sum = dp.global_normalisers(batch['lens_global'])
-                    if batch['vfeats'].shape[0] == 0:
-                        # a rank without rows in this batch: zero bucket, same exchange calls, same (replicated) update
-                        losses, seeds = torch.zeros(4, device=device), None
-                    else:
-                        q_mask = (batch['word_ids'] != 0).float()
-                        if share:       # N videos, B queries: the video half once per video (the engine's backward dispatches on the last forward)
-                            eng.forward_shared(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['video_v_mask'], q_mask,
-                                               batch['video_index'], training=True, seed=(configs.seed << 20) + global_step)
+                    parts = []
+                    for j, batch in enumerate(micro):
+                        if batch['vfeats'].shape[0] == 0:
+                            # a rank without rows in this batch: zero bucket, same exchange calls, same (replicated) update
+                            losses, seeds = torch.zeros(4, device=device), None
                         else:
-                            eng.forward(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['v_mask'], q_mask,
-                                        training=True, seed=(configs.seed << 20) + global_step, sample_offset=batch['row0'])
-                        losses, *seeds = eng.loss(batch['s_labels'], batch['e_labels'], batch['h_labels'], 1.0,
-                                                  configs.highlight_lambda, inv_batch=inv_batch, mask_sum=mask_sum, lazy=True)
-                    dp.backward_exchange_step(eng, xchg, grads, seeds, opt)          # (tests/test_dp_gloo.py drives its multi-rank half on 2 and 3 ranks)
-                    loss_t = losses[2]
+                            q_mask = (batch['word_ids'] != 0).float()
+                            if share:       # N videos, B queries: the video half once per video (the engine's backward dispatches on the last forward)
+                                eng.forward_shared(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['video_v_mask'], q_mask,
+                                                   batch['video_index'], training=True, seed=(configs.seed << 20) + global_step)
+                            else:
+                                eng.forward(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['v_mask'], q_mask,
+                                            training=True, seed=(configs.seed << 20) + global_step, sample_offset=batch['row0'])
+                            losses, *seeds = eng.loss(batch['s_labels'], batch['e_labels'], batch['h_labels'], 1.0,
+                                                      configs.highlight_lambda, inv_batch=inv_batch, mask_sum=mask_sum, lazy=True)
+                        if accum == 1:
+                            dp.backward_exchange_step(eng, xchg, grads, seeds, opt)          # (tests/test_dp_gloo.py drives its multi-rank half on 2 and 3 ranks)
+                        else:       # the first piece overwrites the bucket, the others add to it, the last one applies the step to the sum
+                            dp.backward_exchange_step(eng, xchg, grads, seeds, opt, accumulate=j > 0, update=j == len(micro) - 1)
+                        parts.append(losses[2])
+                    # (the pieces' losses are partial sums of the global loss, as across ranks: added only when the step is logged)
+                    loss_t = parts[0] if len(parts) == 1 else parts
                 else:
                     _, vfeats, vfeat_lens, word_ids, char_ids, s_labels, e_labels, h_labels = batch
                     vfeats, vfeat_lens, word_ids, char_ids, s_labels, e_labels, h_labels = _to_device(
@@ -214,7 +250,7 @@ def train(configs, dataset, features, device, world, rank, log=print):
                 if trace is not None:
                     trace['step_enqueue'] += t2 - t1
                 if global_step % configs.period == 0 or global_step == 1:
-                    lv = float(loss_t.item())
+                    lv = float((torch.stack(loss_t).sum() if isinstance(loss_t, list) else loss_t).item())
                     if world > 1:                                   # local partial sums of the global loss
                         t = torch.tensor([lv], device=device)
                         torch.distributed.all_reduce(t)
@@ -310,6 +346,7 @@ def run(argv=None, log=print):
     parser = build_parser()
     configs = parser.parse_args(argv)
     world, rank, local = _dist_env()
+    check_accum(configs, world)                     # (before the dataset is built: a refused combination costs nothing)
     runner.set_th_config(configs.seed)
     dataset, features = data.load_dataset(configs)
     configs.char_size, configs.word_size = dataset['n_chars'], dataset['n_words']      # main_t7.py:52-53

@@ -1,5 +1,5 @@
 // C ABI of libvslnet_hip.so (declared in include/vslnet_hip.h).  Every entry point checks its arguments and states its own refusals; the five
-// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, vsl_backward / vsl_backward_shared) then go
+// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, the backward's three entry points) then go
 // through ONE path, enqueue(): plan of the shape, the call's context, the CallScope, the sequence of forward.hip / backward.hip, the launch-error
 // check and, for a forward, record_forward(): what it left for the calls behind it.  (layout.hip, plan.hip do the rest; the vsl_profile_* entry
 // points live with the profiler in streams.hip.)  Host code only -- no device code lives here.
@@ -230,11 +230,35 @@ static int check_shared_io(const vsl_io* io, const vsl_shared_io* sh, const char
     return 0;
 }
 
-// the body vsl_backward and vsl_backward_shared (sh != nullptr) share behind their own refusals
-static int backward(vsl_handle_s* h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream, const char* who) {
+// what refuses an ordinary backward (`who` = vsl_backward, or vsl_backward_accumulate without a vsl_shared_io): the last forward saved nothing, or
+// it was a shared one
+static int check_ordinary_saves(vsl_handle_s* h, const vsl_io* io, const char* who) {
+    if (io->inference || io->workspace == h->infer_ws)
+        return fail("%s: the last forward saved nothing (inference mode): run vsl_forward with inference = 0 for a batch that is to be differentiated", who);
+    if (h->last_fwd == vsl_handle_s::FwdShared)
+        return fail("%s: the handle's last forward was vsl_forward_shared: its saves are differentiated by vsl_backward_shared", who);
+    return 0;
+}
+
+// the same for the backward of a shared step (vsl_backward_shared, or vsl_backward_accumulate with a vsl_shared_io)
+static int check_shared_saves(vsl_handle_s* h, const vsl_io* io, const vsl_shared_io* sh, const char* who) {
+    if (int rc = check_shared_io(io, sh, who)) return rc;
+    if (h->last_fwd != vsl_handle_s::FwdShared || io->workspace == h->infer_ws)
+        return fail("%s: the handle's last forward was not vsl_forward_shared (an ordinary forward is differentiated by vsl_backward; an inference forward saved nothing)", who);
+    if (sh->N != h->shared_N) return fail("%s: N=%d, but the last vsl_forward_shared ran over N=%d videos", who, sh->N, h->shared_N);
+    return 0;
+}
+
+// the body the three backward entry points share behind their own refusals (sh != nullptr: a shared step ; accumulate: vsl_backward_accumulate)
+static int backward(vsl_handle_s* h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream, const char* who, bool accumulate = false) {
     if (int rc = check_backward_io(h, io, who)) return rc;
     Plan* p = nullptr;
-    if (int rc = enqueue(h, io, sh ? PlanKind::TrainShared : PlanKind::Train, sh, hip_stream, vsl_handle_s::FwdNone, [&](Ctx& c) { run_backward(c); p = c.p; })) return rc;
+    if (int rc = enqueue(h, io, sh ? PlanKind::TrainShared : PlanKind::Train, sh, hip_stream, vsl_handle_s::FwdNone, [&](Ctx& c) {
+            c.accumulate = accumulate;
+            run_backward(c);
+            p = c.p;
+        })) return rc;
+    // (after an accumulating call too: the reduction recorded the squares of the values it STORED, so they describe the bucket as it now is)
     h->sq_src = p->sq_cover ? p->sq_dev : nullptr; h->sq_n = p->nblocks; h->sq_grads = io->grads;
     return 0;
 }
@@ -259,10 +283,7 @@ int vsl_forward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, 
 
 int vsl_backward_shared(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
-    if (int rc = check_shared_io(io, sh, "vsl_backward_shared")) return rc;
-    if (h->last_fwd != vsl_handle_s::FwdShared || io->workspace == h->infer_ws)
-        return fail("vsl_backward_shared: the handle's last forward was not vsl_forward_shared (an ordinary forward is differentiated by vsl_backward; an inference forward saved nothing)");
-    if (sh->N != h->shared_N) return fail("vsl_backward_shared: N=%d, but the last vsl_forward_shared ran over N=%d videos", sh->N, h->shared_N);
+    if (int rc = check_shared_saves(h, io, sh, "vsl_backward_shared")) return rc;
     return backward(h, io, sh, hip_stream, "vsl_backward_shared");
 }
 
@@ -328,11 +349,16 @@ int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_str
 
 int vsl_backward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
-    if (io->inference || io->workspace == h->infer_ws)
-        return fail("vsl_backward: the last forward saved nothing (inference mode): run vsl_forward with inference = 0 for a batch that is to be differentiated");
-    if (h->last_fwd == vsl_handle_s::FwdShared)
-        return fail("vsl_backward: the handle's last forward was vsl_forward_shared: its saves are differentiated by vsl_backward_shared");
+    if (int rc = check_ordinary_saves(h, io, "vsl_backward")) return rc;
     return backward(h, io, nullptr, hip_stream, "vsl_backward");
+}
+
+// gradient accumulation: the same backward, whose writers of the bucket add to it (sh = NULL after vsl_forward, the step's vsl_shared_io after vsl_forward_shared)
+int vsl_backward_accumulate(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, void* hip_stream) {
+    if (int rc = check_io(h, io)) return rc;
+    if (!io->grads) return fail("vsl_backward_accumulate needs grads: the bucket that holds the running sum");
+    if (int rc = sh ? check_shared_saves(h, io, sh, "vsl_backward_accumulate") : check_ordinary_saves(h, io, "vsl_backward_accumulate")) return rc;
+    return backward(h, io, sh, hip_stream, "vsl_backward_accumulate", true);
 }
 
 int vsl_abi_version(void) { return VSL_ABI_VERSION; }

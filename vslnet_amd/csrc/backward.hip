@@ -534,7 +534,7 @@ void query_chain_bwd(Ctx& c, Pending& pd, const CqBwdArgs& q, const WgradBatch& 
                                                           cf.char_dim, cf.char_size, c.drop(SITE_WORD), c.drop(SITE_CHAR)}, c.s));
     }
     if (cf.word_table)
-        LAUNCH("word_table_bwd", launch_word_table_bwd(c.W(p.dE), c.word_ids(), c.grads() + P.unk, Rq, cf.word_size, cf.word_dim, c.drop(SITE_WORD), c.s));
+        LAUNCH("word_table_bwd", launch_word_table_bwd(c.W(p.dE), c.word_ids(), c.grads() + P.unk, Rq, cf.word_size, cf.word_dim, c.drop(SITE_WORD), c.accumulate, c.s));
     // the loss of vsl_io.fused_loss whose seeds the kernels computed themselves: 64 small workgroups behind the QUERY chain's last kernel (the main
     // stream at T <= 128), in the shadow of the join (at the headline shape that chain ends ~30 us before the video stream's last weight-gradient
     // batch).  On the weight-gradient stream in front of its first batch it took CUs from the chain's 256-workgroup kernels and cost what it saved
@@ -565,7 +565,7 @@ void run_backward(Ctx& c) {
     hipStream_t main_s = c.s;
     c.order2(main_s, sw, sq);
     c.s = sw;
-    LAUNCH("reduce", launch_reduce(c.ws, c.grads(), p.segs_dev, p.blk2seg_dev, p.nblocks_early, p.sq_dev, c.s));
+    LAUNCH("reduce", launch_reduce(c.ws, c.grads(), p.segs_dev, p.blk2seg_dev, p.nblocks_early, p.sq_dev, c.accumulate, c.s));
     // data parallel: the predictor block of the gradient bucket is final now -- the caller's all-reduce of it can start (vslnet_hip.h)
     if (!c.dry && c.io->early_grads_event && cf.predictor == 1) (void)hipEventRecord((hipEvent_t)c.io->early_grads_event, sw);
     // from here the video side and the query side are independent; the longer one keeps the main stream
@@ -579,7 +579,7 @@ void run_backward(Ctx& c) {
     c.s = main_s;
     c.order(sq, c.s);                      // join both side streams before the reduction
     c.order(sw, c.s);
-    LAUNCH("reduce", launch_reduce(c.ws, c.grads(), p.segs_dev, p.blk2seg_dev + 2 * p.nblocks_early, p.nblocks - p.nblocks_early, p.sq_dev + p.nblocks_early, c.s));
+    LAUNCH("reduce", launch_reduce(c.ws, c.grads(), p.segs_dev, p.blk2seg_dev + 2 * p.nblocks_early, p.nblocks - p.nblocks_early, p.sq_dev + p.nblocks_early, c.accumulate, c.s));
     const vsl_fused_step* fs = c.fused_step();
     if (!fs) return;
     // the optimizer step inside the call (vsl_io.fused_step): AdamW behind the reduction (clip norm from the reduction's sums of squares when

@@ -199,6 +199,7 @@ struct Ctx {
     int64_t part_cur = 0;
     std::vector<SlabRec>* recs = nullptr;
     const vsl_shared_io* sh = nullptr;  // vsl_forward_shared / vsl_backward_shared: the videos' index and clip mask (the plan is TrainShared then)
+    bool accumulate = false;            // vsl_backward_accumulate: the writers of the gradient bucket (the two reductions, the trainable word table) add to it
     bool inf() const { return p->kind != PlanKind::Train && p->kind != PlanKind::TrainShared; }
     // a tensor only the backward reads: its address in a training forward, nullptr in an inference forward (the kernels then do not store it)
     float* SV(int64_t off) const { return dry || inf() ? nullptr : ws + off; }

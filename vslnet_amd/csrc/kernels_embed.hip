@@ -470,6 +470,8 @@ void launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s) {
 // and row 0 are zero.  Dense gradient, as torch.optim.AdamW sees it.  One workgroup per occurrence r: it owns the table row only if no
 // earlier row holds the same word, and then adds the occurrences in ascending r -- a fixed order: deterministic without atomics.  The
 // table region is cleared by k_zero4 first (the reduction kernel does not cover it).
+// k_word_table_bwd_acc (vsl_backward_accumulate): nothing is cleared; the owner of a row stores prev + acc (one fp32 add behind the same sum), and a row no word
+// of this batch touches keeps its value.
 // =========================================================================================================
 __global__ __launch_bounds__(256) void k_zero4(float4* __restrict__ dst, int64_t n4) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) dst[e] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -502,7 +504,41 @@ __global__ __launch_bounds__(128) void k_word_table_bwd(const float* __restrict_
         if (c < word_dim) gtab[(size_t)wid * word_dim + c] = acc[j];
     }
 }
-void launch_word_table_bwd(const float* dE, const int64_t* word_ids, float* gtab, int Rq, int word_size, int word_dim, Drop dw, hipStream_t s) {
+// the accumulating form.  A kernel of its own, not an instantiation of a shared body: with the body in a template the compiler lays the plain
+// kernel's exits out differently, and that kernel keeps its machine code (profiles/accum_kernel_resources.txt)
+__global__ __launch_bounds__(128) void k_word_table_bwd_acc(const float* __restrict__ dE, const int64_t* __restrict__ word_ids,
+                                                            float* __restrict__ gtab, int Rq, int word_dim, Drop dw) {
+    const int r = blockIdx.x, tid = threadIdx.x, EW = word_dim + 100;
+    const int64_t wid = word_ids[r];
+    if (wid == 0) return;                              // padding_idx = 0
+    __shared__ int seen;
+    if (tid == 0) seen = 0;
+    __syncthreads();
+    bool mine = false;
+    for (int q = tid; q < r; q += 128) mine |= word_ids[q] == wid;
+    if (mine) seen = 1;
+    __syncthreads();
+    if (seen) return;                                  // an earlier occurrence owns this table row
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};              // word_dim <= 512
+    for (int q = r; q < Rq; ++q)
+        if (word_ids[q] == wid) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = tid + 128 * j;
+                if (c < word_dim) acc[j] += dE[(size_t)q * EW + c] * drop_mul(dw, (uint32_t)(q * word_dim + c));
+            }
+        }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = tid + 128 * j;
+        if (c < word_dim) gtab[(size_t)wid * word_dim + c] = gtab[(size_t)wid * word_dim + c] + acc[j];
+    }
+}
+void launch_word_table_bwd(const float* dE, const int64_t* word_ids, float* gtab, int Rq, int word_size, int word_dim, Drop dw, bool accumulate, hipStream_t s) {
+    if (accumulate) {
+        VSL_LAUNCH(k_word_table_bwd_acc, dim3(Rq), dim3(128), 0, s, dE, word_ids, gtab, Rq, word_dim, dw);
+        return;
+    }
     const int64_t n4 = (int64_t)word_size * word_dim / 4;       // (the flat bucket keeps every parameter 4-float aligned; word_dim % 4 == 0)
     const int zb = (int)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024);
     VSL_LAUNCH(k_zero4, dim3(zb), dim3(256), 0, s, reinterpret_cast<float4*>(gtab), n4);

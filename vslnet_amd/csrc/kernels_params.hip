@@ -100,6 +100,10 @@ void launch_pack(const float* params, float* pack, const PackJob* jobs_dev, int 
 // thread keeps 8 independent 16-byte loads in flight; the 4 group sums are combined through LDS.
 // sq[unit] = sum of squares of the unit's 256 results (also returned, valid in thread 0): every gradient of the bucket leaves this code, so the
 // clip's global norm needs no pass of its own over the bucket (vsl_adamw.norm_from_backward; k_adamw adds the partials in unit order).
+// ACC (vsl_backward_accumulate): the slab sum is formed exactly as without it -- same groups, same order, same LDS combine -- and the bucket's
+// previous value is added LAST, one fp32 add per element: the stored value is prev + sum, and sq[unit] the sum of squares of the STORED values, so
+// the norm k_adamw takes behind the last micro-batch is that of the whole accumulated bucket.  Only elements the plain form writes are read.
+template <bool ACC>
 __device__ __forceinline__ float reduce_unit(const float* __restrict__ ws, float* __restrict__ grads, const ReduceSeg* __restrict__ segs,
                                              const int* __restrict__ blk2seg, float* __restrict__ sq, int unit, float4 (&part)[4][64]) {
     const int si = blk2seg[2 * unit], off = blk2seg[2 * unit + 1];
@@ -141,6 +145,10 @@ __device__ __forceinline__ float reduce_unit(const float* __restrict__ ws, float
         if (grp == 0 && i < n) {
             const float4 b1 = part[1][l4], b2 = part[2][l4], b3 = part[3][l4];
             acc.x += (b1.x + b2.x) + b3.x; acc.y += (b1.y + b2.y) + b3.y; acc.z += (b1.z + b2.z) + b3.z; acc.w += (b1.w + b2.w) + b3.w;
+            if constexpr (ACC) {
+                const float4 pv = *reinterpret_cast<const float4*>(grads + dst + (i / rl) * ds + (i % rl));
+                acc.x = pv.x + acc.x; acc.y = pv.y + acc.y; acc.z = pv.z + acc.z; acc.w = pv.w + acc.w;
+            }
             *reinterpret_cast<float4*>(grads + dst + (i / rl) * ds + (i % rl)) = acc;
         } else acc = make_float4(0.f, 0.f, 0.f, 0.f);
         float q = 0.f;
@@ -180,7 +188,8 @@ __device__ __forceinline__ float reduce_unit(const float* __restrict__ ws, float
             sp[grp * 64 + l4] = a;
             __syncthreads();
             if (grp == 0 && e < n) {
-                const float r = (sp[l4] + sp[64 + l4]) + (sp[128 + l4] + sp[192 + l4]);
+                float r = (sp[l4] + sp[64 + l4]) + (sp[128 + l4] + sp[192 + l4]);
+                if constexpr (ACC) r = grads[dst + (e / rl) * ds + (e % rl)] + r;
                 grads[dst + (e / rl) * ds + (e % rl)] = r;
                 q2 += r * r;
             }
@@ -196,11 +205,18 @@ __global__ __launch_bounds__(256) void k_reduce(const float* __restrict__ ws, fl
                                                 const ReduceSeg* __restrict__ segs, const int* __restrict__ blk2seg,
                                                 float* __restrict__ sq) {
     __shared__ float4 part[4][64];
-    (void)reduce_unit(ws, grads, segs, blk2seg, sq, blockIdx.x, part);
+    (void)reduce_unit<false>(ws, grads, segs, blk2seg, sq, blockIdx.x, part);
+}
+__global__ __launch_bounds__(256) void k_reduce_acc(const float* __restrict__ ws, float* __restrict__ grads,
+                                                    const ReduceSeg* __restrict__ segs, const int* __restrict__ blk2seg,
+                                                    float* __restrict__ sq) {
+    __shared__ float4 part[4][64];
+    (void)reduce_unit<true>(ws, grads, segs, blk2seg, sq, blockIdx.x, part);
 }
 void launch_reduce(const float* partial, float* grads, const ReduceSeg* segs_dev, const int* blk2seg_dev, int nblocks,
-                   float* sq, hipStream_t s) {
-    VSL_LAUNCH(k_reduce, dim3(nblocks), dim3(256), 0, s, partial, grads, segs_dev, blk2seg_dev, sq);
+                   float* sq, bool accumulate, hipStream_t s) {
+    if (accumulate) VSL_LAUNCH(k_reduce_acc, dim3(nblocks), dim3(256), 0, s, partial, grads, segs_dev, blk2seg_dev, sq);
+    else VSL_LAUNCH(k_reduce, dim3(nblocks), dim3(256), 0, s, partial, grads, segs_dev, blk2seg_dev, sq);
 }
 
 // =========================================================================================================

@@ -469,9 +469,10 @@ struct EmbedBwdArgs {
 };
 void launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s);
 void launch_word_table_bwd(const float* dE, const int64_t* word_ids, float* gtab /*(word_size, word_dim) inside the gradient bucket*/, int Rq,
-                           int word_size, int word_dim, Drop dw, hipStream_t s);
+                           int word_size, int word_dim, Drop dw, bool accumulate /* add to the rows the batch touches, leave the others */, hipStream_t s);
 void launch_reduce(const float* partial, float* grads, const ReduceSeg* segs_dev, const int* blk2seg_dev, int nblocks,
-                   float* sq /* [nblocks]: sum of squares of each block's results */, hipStream_t s);
+                   float* sq /* [nblocks]: sum of squares of each block's results */, bool accumulate /* grads += the sums ; sq of the stored values */,
+                   hipStream_t s);
 // fused optimizer (vsl_adamw_step): sum of squares partials, then clip + AdamW
 constexpr int OPT_BLOCKS = 256;
 struct AdamHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; int hf_order; };      // bc1 = 1 - b1^step ; bc2_sqrt = sqrt(1 - b2^step)

@@ -268,13 +268,22 @@ class ResidentSplit:
         gid = np.concatenate([np.full(len(groups[g]), k, dtype=np.int64) for k, g in enumerate(pick)])
         return order, gid
 
-    def shards(self, rank=0, world=1, order=None, queries_per_video=None):
+    def shards(self, rank=0, world=1, order=None, queries_per_video=None, micro_batches=1):
         """One dict per GLOBAL batch: this rank's rows on the device + what the losses need about the whole batch.
         queries_per_video=K (single process): the GROUPED order for the training step through a shared encoding (Engine.forward_shared) -- each
         video's records shuffled and cut into groups of at most K, the groups shuffled and concatenated up to batch_size (a group that crosses a
         batch boundary continues as a smaller group of the next batch).  The dict then holds one row of `vfeats` (N, T, Dv) and `video_v_mask` (N, T)
         per group and `video_index` (B, int32, device) = the row of each query; `v_mask` stays the (B, T) per-query mask.  Every record appears
-        once per epoch; K = 1 gives N = B, today's content."""
+        once per epoch; K = 1 gives N = B, today's content.
+        micro_batches=K > 1 (single process; gradient accumulation): K dicts per global batch instead of one, from ONE draw of the order -- piece j
+        holds rows dp.micro_slices(B, K)[j] of the batch, padded to the batch's global T / Lq / Lc, with `row0` = its first row and `lens_global`
+        of the whole batch: what rank j of K would get.  A piece without rows (K > B: the last batch of an epoch) is yielded too, empty."""
+        K = int(micro_batches)
+        if K < 1:
+            raise ValueError('shards(micro_batches=%d): at least one' % K)
+        if K > 1 and (world != 1 or queries_per_video is not None):
+            raise ValueError('shards(micro_batches=...) is single-process and not for the grouped order: data parallel and the shared encoding do not accumulate here')
+        pieces = [(rank, world)] if K == 1 else [(j, K) for j in range(K)]
         if queries_per_video is not None:
             if world != 1 or order is not None:
                 raise ValueError('shards(queries_per_video=...) is the single-process grouped order: data parallel through a shared encoding is not supported')
@@ -287,18 +296,19 @@ class ResidentSplit:
             idx = order[a:a + bs]
             lens = self.lens[idx]
             T, Lq, Lc = int(lens.max()), int(self.nwords[idx].max()), int(self.nchars[idx].max())
-            base, rem = divmod(len(idx), world)
-            lo = rank * base + min(rank, rem)
-            hi = lo + base + (1 if rank < rem else 0)
-            idx_dev = d_order[a + lo:a + hi]
-            g = self._gather(idx_dev, T, Lq, Lc)
-            l_dev = self.d_lens[idx_dev]
-            v_mask = (torch.arange(T, device=self.device)[None, :] < l_dev[:, None]).float()
-            b = {'records': [self.records[i] for i in idx[lo:hi]], 'lens_global': lens, 'row0': lo, 'vfeats': g[0], 'v_mask': v_mask,
-                 'word_ids': g[1], 'char_ids': g[2]}
-            if self.train:
-                b.update(s_labels=g[3], e_labels=g[4], h_labels=g[5])
-            yield b
+            for piece, of in pieces:
+                base, rem = divmod(len(idx), of)
+                lo = piece * base + min(piece, rem)
+                hi = lo + base + (1 if piece < rem else 0)
+                idx_dev = d_order[a + lo:a + hi]
+                g = self._gather(idx_dev, T, Lq, Lc)
+                l_dev = self.d_lens[idx_dev]
+                v_mask = (torch.arange(T, device=self.device)[None, :] < l_dev[:, None]).float()
+                b = {'records': [self.records[i] for i in idx[lo:hi]], 'lens_global': lens, 'row0': lo, 'vfeats': g[0], 'v_mask': v_mask,
+                     'word_ids': g[1], 'char_ids': g[2]}
+                if self.train:
+                    b.update(s_labels=g[3], e_labels=g[4], h_labels=g[5])
+                yield b
 
     def _grouped_shards(self, K):
         order, gid = self._grouped_order(K)
@@ -328,23 +338,29 @@ class ResidentSplit:
             yield head + ((b['s_labels'], b['e_labels'], b['h_labels']) if self.train else ())
 
 
-def loader_shards(loader, device, rank=0, world=1):
-    """The same dicts as ResidentSplit.shards from a host-side DataLoader (collate on the host, H2D copy per step)."""
+def loader_shards(loader, device, rank=0, world=1, micro_batches=1):
+    """The same dicts as ResidentSplit.shards from a host-side DataLoader (collate on the host, H2D copy per step); micro_batches=K > 1 (single
+    process): the K pieces of every collated batch, as there."""
+    K = int(micro_batches)
+    if K < 1 or (K > 1 and world != 1):
+        raise ValueError('loader_shards(micro_batches=%d, world=%d): at least one piece, and more than one in a single process only' % (K, world))
+    pieces = [(rank, world)] if K == 1 else [(j, K) for j in range(K)]
     for batch in loader:
         records, vfeats, lens = batch[0], batch[1], batch[2]
         n = vfeats.shape[0]
-        base, rem = divmod(n, world)
-        lo = rank * base + min(rank, rem)
-        sl = slice(lo, lo + base + (1 if rank < rem else 0))
-        mv = lambda t: t[sl].to(device, non_blocking=True).contiguous()
-        l_dev = lens[sl].to(device, non_blocking=True)
         T = int(lens.max())
-        b = {'records': list(records[sl]), 'lens_global': lens.numpy(), 'row0': lo, 'vfeats': mv(vfeats),
-             'v_mask': (torch.arange(T, device=device)[None, :] < l_dev[:, None]).float(),
-             'word_ids': mv(batch[3]), 'char_ids': mv(batch[4])}
-        if len(batch) > 5:
-            b.update(s_labels=mv(batch[5]), e_labels=mv(batch[6]), h_labels=mv(batch[7]))
-        yield b
+        for piece, of in pieces:
+            base, rem = divmod(n, of)
+            lo = piece * base + min(piece, rem)
+            sl = slice(lo, lo + base + (1 if piece < rem else 0))
+            mv = lambda t: t[sl].to(device, non_blocking=True).contiguous()
+            l_dev = lens[sl].to(device, non_blocking=True)
+            b = {'records': list(records[sl]), 'lens_global': lens.numpy(), 'row0': lo, 'vfeats': mv(vfeats),
+                 'v_mask': (torch.arange(T, device=device)[None, :] < l_dev[:, None]).float(),
+                 'word_ids': mv(batch[3]), 'char_ids': mv(batch[4])}
+            if len(batch) > 5:
+                b.update(s_labels=mv(batch[5]), e_labels=mv(batch[6]), h_labels=mv(batch[7]))
+            yield b
 
 
 # ------------------------------------------------------------------------------------------------ datasets

@@ -23,6 +23,14 @@ def shard_slice(global_batch, rank, world):
     return slice(lo, lo + base + (1 if rank < rem else 0))
 
 
+def micro_slices(n_rows, K):
+    """The rows of the K micro-batches of a batch of `n_rows`: the contiguous cuts of `shard_slice` for K pieces (sizes differ by at most one, the
+    larger ones first; K > n_rows leaves the last pieces empty).  A micro-batch is a data-parallel shard run in sequence."""
+    if K < 1:
+        raise ValueError('micro_slices: K=%d pieces (at least one)' % K)
+    return [shard_slice(n_rows, j, K) for j in range(K)]
+
+
 def shard_batch(batch, rank, world):
     """Slice every per-sample tensor of a collated batch (dict of tensors with leading dim B).  The padded widths are left
     untouched: the shard keeps the global max T / Lq / Lc."""
@@ -123,12 +131,29 @@ def backward_and_exchange(engine, xchg, grads, seeds):
     return multi
 
 
-def backward_exchange_step(engine, xchg, grads, seeds, opt):
+def backward_exchange_step(engine, xchg, grads, seeds, opt, accumulate=False, update=True):
     """One training step from the loss seeds on: backward, gradient exchange, clip + AdamW -- what `main.train` and `bench.py` run.
     One process with rows in the batch: the update is issued by the backward itself, behind its final reduction (`Engine.backward(fused_step=...)`).
-    More than one rank: `backward_and_exchange`, then the two-kernel step on the SUMMED bucket."""
+    More than one rank: `backward_and_exchange`, then the two-kernel step on the SUMMED bucket.
+    Gradient accumulation (one process; `main.py --accum_steps`): a step over K micro-batches is K calls, each behind its own forward and loss --
+      `update=False`: the backward alone -- no exchange, no `opt.fused_step()`, `opt.t` does not advance;
+      `accumulate=True`: the backward ADDS to `grads` (`Engine.backward(accumulate=True)`); the first non-empty micro-batch of a step runs with
+      accumulate=False and overwrites the bucket, so nothing is zeroed between steps;
+      the last micro-batch runs with `update=True`: clip + AdamW on the accumulated bucket, inside that backward."""
     import torch.distributed as dist
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(xchg.group if xchg is not None else None) > 1
+    if accumulate or not update:
+        if multi or xchg is not None:
+            raise ValueError('gradient accumulation is single-process: data parallel x accumulation needs the exchange held back to the last micro-batch')
+        if seeds is None:
+            raise ValueError('gradient accumulation: a micro-batch without rows is skipped by the caller, not passed here')
+        if not update:
+            engine.backward(seeds[0], seeds[1], seeds[2], grads, accumulate=accumulate)
+            return
+        if opt.engine is None or not getattr(engine, 'has_fused_io', False):
+            raise ValueError('gradient accumulation: the last micro-batch applies the fused step, which needs the GPU engine')
+        engine.backward(seeds[0], seeds[1], seeds[2], grads, fused_step=opt.fused_step(), accumulate=True)
+        return
     if not multi and xchg is None and seeds is not None and opt.engine is not None and getattr(engine, 'has_fused_io', False):
         engine.backward(seeds[0], seeds[1], seeds[2], grads, fused_step=opt.fused_step())
         return

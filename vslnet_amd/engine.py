@@ -91,7 +91,8 @@ ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count',
                'vsl_adamw_step', 'vsl_workspace_offset', 'vsl_profile_select', 'vsl_profile_read', 'vsl_profile_launch', 'vsl_abi_version',
                'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats',
                'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize',
-               'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset']
+               'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset',
+               'vsl_backward_accumulate']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -147,6 +148,8 @@ def load_library():
         lib.vsl_backward_shared.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
         lib.vsl_shared_workspace_offset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
         lib.vsl_shared_workspace_offset.restype = C.c_int64
+    if hasattr(lib, 'vsl_backward_accumulate'):              # (likewise: gradient accumulation)
+        lib.vsl_backward_accumulate.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
     lib.vsl_loss.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_loss_io), C.c_void_p]
     lib.vsl_backward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -227,6 +230,9 @@ class Engine:
         self.has_shared_video = hasattr(self.lib, 'vsl_encode_video') and hasattr(self.lib, 'vsl_localize')
         # vsl_forward_shared / vsl_backward_shared: a training step over N videos and B queries.  An older build has neither; forward_shared then raises
         self.has_shared_train = hasattr(self.lib, 'vsl_forward_shared') and hasattr(self.lib, 'vsl_backward_shared')
+        # vsl_backward_accumulate: a backward that adds to the gradient bucket (one optimizer step over K micro-batches).  An older build lacks it;
+        # backward(accumulate=True) then raises
+        self.has_grad_accumulation = hasattr(self.lib, 'vsl_backward_accumulate')
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -605,12 +611,18 @@ class Engine:
         """First float offset of the block of `grads` that is final when `backward(..., early_event=)` fires its event."""
         return int(self.lib.vsl_early_grad_offset(self.h))
 
-    def backward(self, d_h, d_sl, d_el, grads, early_event=None, fused_step=None):
+    def backward(self, d_h, d_sl, d_el, grads, early_event=None, fused_step=None, accumulate=False):
         """Backward of the LAST forward (forward() or forward_shared()); writes the flat gradient bucket `grads` (same layout as the params).
         `early_event` (torch.cuda.Event, data parallel): recorded by the library as soon as grads[early_grad_offset():] is final.
         `fused_step` (single process; `FlatAdamW.fused_step()`): dict(flat, exp_avg, exp_avg_sq, lr, step, betas, eps, weight_decay, clip_norm,
         hf_order[, grad_norm_out]) -- this optimizer step is applied inside the backward's last launch (final reduction + clip + AdamW in one
-        kernel); equivalent to backward() followed by adamw_step(..., norm_from_backward=True)."""
+        kernel); equivalent to backward() followed by adamw_step(..., norm_from_backward=True).
+        `accumulate=True` (vsl_backward_accumulate): the gradients are ADDED to what `grads` holds, one fp32 add per element behind the same sums
+        (grads = grads + g).  One optimizer step over K micro-batches is the first one with accumulate=False (it overwrites: nothing is zeroed), the
+        others with accumulate=True, the last of them with `fused_step`: clip and AdamW then act on the accumulated bucket and its norm.  The
+        micro-batches take the global loss normalisers and their first row as forward()'s `sample_offset`, like data-parallel shards."""
+        if accumulate and not self.has_grad_accumulation:
+            raise VslError('backward(accumulate=True): the loaded library has no gradient accumulation (vsl_backward_accumulate is missing)')
         io = self._last
         if io is not None and io.inference:
             raise VslError('backward(): the last forward was an inference forward, which saved nothing; run forward(inference=False) on the batch')
@@ -655,7 +667,9 @@ class Engine:
             io.fused_step = C.cast(C.pointer(fs), C.c_void_p)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         try:
-            if self._last_shared is not None:
+            if accumulate:
+                self._call(self.lib.vsl_backward_accumulate(self.h, C.byref(io), C.byref(self._last_shared) if self._last_shared is not None else None, stream))
+            elif self._last_shared is not None:
                 self._call(self.lib.vsl_backward_shared(self.h, C.byref(io), C.byref(self._last_shared), stream))
             else:
                 self._call(self.lib.vsl_backward(self.h, C.byref(io), stream))
