@@ -264,6 +264,31 @@ uint64_t vsl_debug_rnn_launches(uint64_t n);
 int vsl_extract_index(vsl_handle h, const float* start_logits, const float* end_logits, int B, int T,
                       int64_t* start_index, int64_t* end_index, void* hip_stream);
 
+/* THE K BEST MOMENTS PER QUERY: greedy selection with temporal non-maximum suppression (no reference counterpart: extract_index returns one span).
+ * For sample b, L = valid_len[b] clamped into [1, T] (T without valid_len):
+ *   - candidates: every span (s, e), 0 <= s <= e < L, and e - s + 1 <= max_span when max_span > 0;
+ *   - score = start_logits[b][s] + end_logits[b][e], ONE fp32 addition.  extract_index ranks by softmax(sl)[s] softmax(el)[e] = exp(score - lse_s - lse_e)
+ *     and the normalisers are constant per sample: the order by score is the order by that product, exact and free of exp;
+ *   - order: score descending, then start ascending, then end ascending (the first maximum in row-major order, extract_index's tie rule);
+ *   - K rounds; each takes the first candidate in that order that is neither chosen nor suppressed by an earlier choice;
+ *   - (s, e) is suppressed by a chosen (s', e') iff, as clip intervals [s, e + 1),  inter = max(0, min(e, e') - max(s, s') + 1),
+ *     uni = (e - s + 1) + (e' - s' + 1) - inter,  inter > 0 && (float)inter > nms_iou * (float)uni  (one fp32 multiply).  nms_iou = 1 suppresses
+ *     nothing (plain top-K), nms_iou = 0 keeps mutually disjoint spans only;
+ *   - outputs (B, K): start_index, end_index, score (the logit sum), prob = expf(score - lse_s - lse_e) with both log-sum-exps over the sample's T
+ *     logits as the reference's softmax runs (nullable), and count (B) = rounds that found a candidate (nullable).  Slots from count[b] on hold
+ *     -1, -1, -inf, 0.
+ * Limits: 1 <= K <= 32, 1 <= T <= 4096, B >= 1, max_span >= 0, 0 <= nms_iou <= 1.  NaN logits give an unspecified choice (every loop is bounded).
+ * A free-standing call like vsl_extract_index: it reads no plan and no workspace and is legal after any kind of forward; one workgroup per sample,
+ * the (T, T) scores are never materialised.  Detect the feature by the presence of the symbol: VSL_ABI_VERSION does not change for an added entry point. */
+typedef struct vsl_topk_io {               /* zero-initialise; new fields are appended */
+    const float* start_logits; const float* end_logits;   /* (B, T) */
+    const int32_t* valid_len;                             /* (B,) or NULL = T */
+    int B, T, K; float nms_iou; int max_span;             /* max_span 0 = unlimited */
+    int64_t* start_index; int64_t* end_index;             /* (B, K) */
+    float* score; float* prob; int32_t* count;            /* (B, K), (B, K) or NULL, (B,) or NULL */
+} vsl_topk_io;
+int vsl_extract_topk(vsl_handle h, const vsl_topk_io* io, void* hip_stream);
+
 /* Optimizer step on the flat buckets: clip_grad_norm_(grads, clip_norm) (main_t7.py:111) followed by AdamW with decoupled
  * weight decay (build_optimizer_and_scheduler, VSLNet_t7.py:8-17: no decay for names containing "bias", "layer_norm" or
  * "LayerNorm" -- the library derives that mask from its own parameter names).  Two kernels (one with norm_from_backward), no host synchronisation: the

@@ -23,6 +23,10 @@ What differs from the reference, by design:
     shard run in sequence (global widths and normalisers, dropout counters continued at its first row), the library's backward adding to the flat
     bucket and the last piece applying clip + AdamW to the sum.  A global batch whose workspace does not fit runs as pieces that do.  Single
     process, `--optimizer fused`, not with `--share_videos`;
+  * `--topk K` (with `--nms_iou`, `--max_span`): every evaluation -- `--mode test` and the ones inside training, with and without `--share_videos` --
+    also asks the library for the K best moments per query (greedy temporal NMS, vsl_extract_topk) and reports Rank@K at IoU 0.3 / 0.5 / 0.7 and the
+    best-of-K mean IoU beside the Rank@1 numbers, which stay those of extract_index.  0 (default): off, the output is what it was.  Like the other
+    flags they go into configs.json and come back as defaults in --mode test (trained with --topk 5: Rank@5 there unless --topk 0 is given);
   * `--task synthetic` builds a small learnable dataset in the reference's record format (no dataset files needed).
 """
 import argparse
@@ -87,6 +91,10 @@ def build_parser():
     p.add_argument('--queries_per_video', type=int, default=4, help='--mode train --share_videos: queries of one video per group of the grouped order')
     p.add_argument('--accum_steps', type=int, default=1, help='gradient accumulation: every global batch of --batch_size runs as this many contiguous '
                    'micro-batches and ONE optimizer step (1: off).  Single process, --optimizer fused, not with --share_videos')
+    p.add_argument('--topk', type=int, default=0, help='evaluations also report Rank@K over the K best moments per query (1..32; 0: off)')
+    p.add_argument('--nms_iou', type=float, default=0.5, help='--topk: a candidate whose temporal IoU with an already chosen moment exceeds this is suppressed '
+                   '(1.0: plain top-K, 0.0: disjoint moments only)')
+    p.add_argument('--max_span', type=int, default=0, help='--topk: longest candidate moment in clips (0: unlimited)')
     p.add_argument('--synthetic_train', type=int, default=512)
     p.add_argument('--synthetic_test', type=int, default=128)
     return p
@@ -128,10 +136,26 @@ def check_accum(configs, world):
     return accum
 
 
+def topk_of(configs):
+    """--topk / --nms_iou / --max_span -> the `topk` argument of the evaluation loops (None: off; a configs.json from before the flags has none)"""
+    k = int(getattr(configs, 'topk', 0) or 0)
+    if k == 0:
+        return None
+    if not 1 <= k <= 32:
+        raise ValueError('--topk %d: between 1 and 32 (0: off)' % k)
+    nms_iou, max_span = float(getattr(configs, 'nms_iou', 0.5)), int(getattr(configs, 'max_span', 0) or 0)
+    if not 0.0 <= nms_iou <= 1.0:
+        raise ValueError('--nms_iou %g: between 0 and 1' % nms_iou)
+    if max_span < 0:
+        raise ValueError('--max_span %d: at least 0 (0: unlimited)' % max_span)
+    return runner.TopK(k, nms_iou, max_span)
+
+
 def train(configs, dataset, features, device, world, rank, log=print):
     from vslnet_amd.model.VSLNet import VSLNet, build_optimizer_and_scheduler
     model_dir = model_home(configs)
     accum = check_accum(configs, world)
+    topk = topk_of(configs)
     gen = torch.Generator().manual_seed(configs.seed)                       # same shuffle on every rank
     share = bool(getattr(configs, 'share_videos', False))
     if share:
@@ -268,14 +292,16 @@ def train(configs, dataset, features, device, world, rank, log=print):
                         # all-reduce until the communicator times out.
                         try:
                             model.eval()
-                            r1i3, r1i5, r1i7, mi, score_str = runner.eval_test(model, test_loader, device, 'test', epoch + 1, global_step)
+                            r1i3, r1i5, r1i7, mi, score_str, *rank_k = runner.eval_test(model, test_loader, device, 'test', epoch + 1, global_step, topk=topk)
                             t4 = clock()
                             if trace is not None:
                                 trace['eval'] += t4 - t3
                             log('Epoch: %2d | Step: %5d | r1i3: %.2f | r1i5: %.2f | r1i7: %.2f | mIoU: %.2f' % (epoch + 1, global_step, r1i3, r1i5, r1i7, mi))
+                            if rank_k:
+                                log('                         | rank@%(k)d i3: %(r_k_i3).2f | i5: %(r_k_i5).2f | i7: %(r_k_i7).2f | best-of-%(k)d mIoU: %(mIoU_k).2f' % rank_k[0])
                             score_writer.write(score_str)
                             score_writer.flush()
-                            history.append((global_step, {'r1i3': r1i3, 'r1i5': r1i5, 'r1i7': r1i7, 'mIoU': mi}))
+                            history.append((global_step, dict({'r1i3': r1i3, 'r1i5': r1i5, 'r1i7': r1i7, 'mIoU': mi}, **(rank_k[0] if rank_k else {}))))
                             if r1i7 >= best_r1i7:
                                 best_r1i7 = r1i7
                                 ckpt.save_flat(model, os.path.join(model_dir, '{}_{}.t7'.format(configs.model_name, global_step)), model_dir,
@@ -327,6 +353,7 @@ def test(configs, parser, argv, dataset, features, device, log=print):
     model = VSLNet(configs=configs, word_vectors=dataset['word_vector']).to(device)
     model.load_state_dict(torch.load(runner.get_last_checkpoint(model_dir, suffix='t7'), map_location=device))
     model.eval()
+    topk = topk_of(configs)
     if configs.data == 'resident':
         loader = data.ResidentSplit(dataset['test_set'], features, configs, device, train=False)
     else:
@@ -334,12 +361,17 @@ def test(configs, parser, argv, dataset, features, device, log=print):
     if getattr(configs, 'share_videos', False):
         if configs.data != 'resident':
             raise ValueError('--share_videos needs --data resident (the encoding is computed over the split held in device memory)')
-        r1i3, r1i5, r1i7, mi, _ = runner.eval_test_shared(model, loader, device, mode='test')
+        r1i3, r1i5, r1i7, mi, _, *rank_k = runner.eval_test_shared(model, loader, device, mode='test', topk=topk)
     else:
-        r1i3, r1i5, r1i7, mi, _ = runner.eval_test(model, loader, device, mode='test')
-    for name, v in (('Rank@1, IoU=0.3', r1i3), ('Rank@1, IoU=0.5', r1i5), ('Rank@1, IoU=0.7', r1i7), ('mean IoU'.ljust(15), mi)):
+        r1i3, r1i5, r1i7, mi, _, *rank_k = runner.eval_test(model, loader, device, mode='test', topk=topk)
+    rows = [('Rank@1, IoU=0.3', r1i3), ('Rank@1, IoU=0.5', r1i5), ('Rank@1, IoU=0.7', r1i7), ('mean IoU'.ljust(15), mi)]
+    if rank_k:
+        k = rank_k[0]['k']
+        rows += [('Rank@%d, IoU=0.3' % k, rank_k[0]['r_k_i3']), ('Rank@%d, IoU=0.5' % k, rank_k[0]['r_k_i5']), ('Rank@%d, IoU=0.7' % k, rank_k[0]['r_k_i7']),
+                 ('best-of-%d mean IoU' % k, rank_k[0]['mIoU_k'])]
+    for name, v in rows:
         log('\x1b[1;31m{}:\t{:.2f}\x1b[0m'.format(name, v))
-    return {'r1i3': r1i3, 'r1i5': r1i5, 'r1i7': r1i7, 'mIoU': mi}
+    return dict({'r1i3': r1i3, 'r1i5': r1i5, 'r1i7': r1i7, 'mIoU': mi}, **(rank_k[0] if rank_k else {}))
 
 
 def run(argv=None, log=print):
@@ -347,6 +379,7 @@ def run(argv=None, log=print):
     configs = parser.parse_args(argv)
     world, rank, local = _dist_env()
     check_accum(configs, world)                     # (before the dataset is built: a refused combination costs nothing)
+    topk_of(configs)
     runner.set_th_config(configs.seed)
     dataset, features = data.load_dataset(configs)
     configs.char_size, configs.word_size = dataset['n_chars'], dataset['n_words']      # main_t7.py:52-53

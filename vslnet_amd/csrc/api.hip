@@ -383,6 +383,21 @@ int vsl_extract_index(vsl_handle h, const float* start_logits, const float* end_
     return 0;
 }
 
+int vsl_extract_topk(vsl_handle h, const vsl_topk_io* io, void* hip_stream) {
+    if (!h || !io) return fail("vsl_extract_topk: null argument");
+    if (!io->start_logits || !io->end_logits) return fail("vsl_extract_topk: null logits");
+    if (io->B < 1) return fail("vsl_extract_topk: B=%d must be at least 1", io->B);
+    if (io->T < 1 || io->T > MAX_L) return fail("vsl_extract_topk: T=%d must be in [1, %d]", io->T, MAX_L);
+    if (io->K < 1 || io->K > TOPK_MAX_K) return fail("vsl_extract_topk: K=%d must be in [1, %d]", io->K, TOPK_MAX_K);
+    if (io->max_span < 0) return fail("vsl_extract_topk: max_span=%d must be >= 0 (0 = unlimited)", io->max_span);
+    if (!(io->nms_iou >= 0.f && io->nms_iou <= 1.f)) return fail("vsl_extract_topk: nms_iou=%g must be in [0, 1]", (double)io->nms_iou);
+    if (!io->start_index || !io->end_index || !io->score) return fail("vsl_extract_topk: start_index, end_index and score are required outputs");
+    launch_extract_topk(TopkArgs{io->start_logits, io->end_logits, io->valid_len, io->B, io->T, io->K, io->nms_iou, io->max_span, io->start_index,
+                                 io->end_index, io->score, io->prob, io->count}, (hipStream_t)hip_stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 int vsl_adamw_step(vsl_handle h, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const vsl_adamw* hp,
                    float* grad_norm_out, void* hip_stream) {
     if (!h || !params || !grads || !exp_avg || !exp_avg_sq || !hp) return fail("vsl_adamw_step: null argument");

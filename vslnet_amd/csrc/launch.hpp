@@ -353,6 +353,19 @@ struct LossArgs {
 };
 void launch_loss(const LossArgs& a, hipStream_t s);
 void launch_extract_index(const float* sl, const float* el, int64_t* si, int64_t* ei, int B, int T, hipStream_t s);
+// top-K spans per sample by greedy selection with temporal NMS (kernels_topk.hip; the semantics: include/vslnet_hip.h, vsl_extract_topk)
+struct TopkArgs {
+    const float *sl, *el;                 // (B, T) start / end logits
+    const int32_t* valid_len;             // (B), nullable = T; clamped into [1, T]
+    int B, T, K;                          // 1 <= K <= 32, T <= MAX_L
+    float nms_iou;                        // in [0, 1]; 1 suppresses nothing
+    int max_span;                         // 0 = unlimited
+    int64_t *start_index, *end_index;     // (B, K)
+    float *score, *prob;                  // (B, K); prob nullable
+    int32_t* count;                       // (B), nullable
+};
+constexpr int TOPK_MAX_K = 32;
+void launch_extract_topk(const TopkArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- backward
 // fuse != nullptr: the end head's workgroups continue with that attention-output backward on their own tile of dfeat (which is then NOT stored)

@@ -6,6 +6,7 @@ if the shared library is missing or no MI355X is visible, construction raises.
 """
 import ctypes as C
 import os
+from collections import namedtuple
 from types import SimpleNamespace
 
 import torch
@@ -82,6 +83,17 @@ class vsl_fused_step(C.Structure):
     _fields_ = [('params', C.c_void_p), ('exp_avg', C.c_void_p), ('exp_avg_sq', C.c_void_p), ('hp', vsl_adamw), ('grad_norm_out', C.c_void_p)]
 
 
+class vsl_topk_io(C.Structure):
+    _fields_ = [('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('valid_len', C.c_void_p),
+                ('B', C.c_int), ('T', C.c_int), ('K', C.c_int), ('nms_iou', C.c_float), ('max_span', C.c_int),
+                ('start_index', C.c_void_p), ('end_index', C.c_void_p), ('score', C.c_void_p), ('prob', C.c_void_p), ('count', C.c_void_p)]
+
+
+# what Engine.extract_topk returns: (B, K) int64 start / end, (B, K) fp32 score (the logit sum) and prob (None without want_prob), (B,) int32 count;
+# slots from count[b] on hold -1, -1, -inf, 0
+TopkSpans = namedtuple('TopkSpans', 'start end score prob count')
+
+
 class VslError(RuntimeError):
     pass
 
@@ -92,7 +104,7 @@ ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count',
                'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats',
                'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize',
                'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset',
-               'vsl_backward_accumulate']
+               'vsl_backward_accumulate', 'vsl_extract_topk']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -150,6 +162,8 @@ def load_library():
         lib.vsl_shared_workspace_offset.restype = C.c_int64
     if hasattr(lib, 'vsl_backward_accumulate'):              # (likewise: gradient accumulation)
         lib.vsl_backward_accumulate.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
+    if hasattr(lib, 'vsl_extract_topk'):                     # (likewise: top-K spans with temporal NMS)
+        lib.vsl_extract_topk.argtypes = [C.c_void_p, C.POINTER(vsl_topk_io), C.c_void_p]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
     lib.vsl_loss.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_loss_io), C.c_void_p]
     lib.vsl_backward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -233,6 +247,8 @@ class Engine:
         # vsl_backward_accumulate: a backward that adds to the gradient bucket (one optimizer step over K micro-batches).  An older build lacks it;
         # backward(accumulate=True) then raises
         self.has_grad_accumulation = hasattr(self.lib, 'vsl_backward_accumulate')
+        # vsl_extract_topk: the K best spans per sample with temporal NMS.  An older build lacks it; extract_topk then raises
+        self.has_topk = hasattr(self.lib, 'vsl_extract_topk')
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -735,6 +751,37 @@ class Engine:
         self._call(self.lib.vsl_extract_index(self.h, _ptr(start_logits), _ptr(end_logits), B, T, _ptr(idx[0]),
                                               _ptr(idx[1]), stream))
         return idx[0], idx[1]
+
+    def extract_topk(self, start_logits, end_logits, k, nms_iou=1.0, max_span=0, lengths=None, v_mask=None, want_prob=True):
+        """The k best spans per sample by greedy selection with temporal NMS (include/vslnet_hip.h, vsl_extract_topk; the written specification:
+        vslnet_amd.spans.topk_spans_reference) -> TopkSpans.  Candidates are the spans inside the sample's valid length: `lengths` (B,) integers, or
+        `v_mask` (B, T), a prefix mask (convert_length_to_mask) whose row sums are the lengths; neither: T.  nms_iou = 1 is plain top-k."""
+        if not self.has_topk:
+            raise VslError('the loaded library has no top-k span extraction (vsl_extract_topk is missing)')
+        if lengths is not None and v_mask is not None:
+            raise ValueError('extract_topk: give lengths or v_mask, not both')
+        B, T = start_logits.shape
+        _chk(start_logits, torch.float32, (B, T), 'start_logits')
+        _chk(end_logits, torch.float32, (B, T), 'end_logits')
+        if v_mask is not None:
+            _chk(v_mask, torch.float32, (B, T), 'v_mask')
+            lengths = v_mask.sum(dim=1).to(torch.int32)
+        elif lengths is not None:
+            lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int32).contiguous()
+            _chk(lengths, torch.int32, (B,), 'lengths')
+        k, max_span = int(k), int(max_span)
+        for name, v in (('k', k), ('max_span', max_span)):   # (ctypes would wrap them: max_span = 2 ** 32 must not arrive as 0 = unlimited; the library checks the ranges)
+            if not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError('extract_topk: %s=%d is not a C int' % (name, v))
+        idx = torch.empty(2, B, max(k, 0), dtype=torch.int64, device=self.device)
+        val = torch.empty(2 if want_prob else 1, B, max(k, 0), dtype=torch.float32, device=self.device)
+        count = torch.empty(B, dtype=torch.int32, device=self.device)
+        io = vsl_topk_io(start_logits.data_ptr(), end_logits.data_ptr(), lengths.data_ptr() if lengths is not None else None, B, T, k,
+                         float(nms_iou), max_span, idx[0].data_ptr(), idx[1].data_ptr(), val[0].data_ptr(),
+                         val[1].data_ptr() if want_prob else None, count.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_extract_topk(self.h, C.byref(io), stream))
+        return TopkSpans(idx[0], idx[1], val[0], val[1] if want_prob else None, count)
 
 
 def flat_from_state_dict(engine, sd):

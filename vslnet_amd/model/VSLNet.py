@@ -272,6 +272,12 @@ class VSLNet(nn.Module):
         self._engine_for(start_logits.device)
         return self._engine.extract_index(start_logits.detach().contiguous(), end_logits.detach().contiguous())
 
+    def extract_topk(self, start_logits, end_logits, k, nms_iou=1.0, max_span=0, lengths=None, v_mask=None, want_prob=True):
+        """The k best moments per query with temporal NMS (Engine.extract_topk) -> TopkSpans(start, end, score, prob, count); no reference counterpart."""
+        self._engine_for(start_logits.device)
+        return self._engine.extract_topk(start_logits.detach().contiguous(), end_logits.detach().contiguous(), k, nms_iou=nms_iou, max_span=max_span,
+                                         lengths=lengths, v_mask=None if v_mask is None else v_mask.detach().contiguous().float(), want_prob=want_prob)
+
     def compute_highlight_loss(self, scores, labels, mask):
         B = scores.shape[0]
         z = torch.zeros(B, dtype=torch.int64, device=scores.device)

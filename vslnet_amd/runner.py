@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .data import index_to_time
+from .spans import TopK, spans_to_times           # noqa: F401  (TopK re-exported: the `topk` argument of eval_test / eval_test_shared)
 from .synthetic import convert_length_to_mask     # noqa: F401  (re-exported: runner_utils_t7.py:48-52)
 
 
@@ -176,11 +177,45 @@ def summarise(ious, epoch=None, global_step=None):
     return r1i3, r1i5, r1i7, mi, text
 
 
-def eval_test(model, data_loader, device, mode='test', epoch=None, global_step=None):
+def best_iou_of_spans(start, end, count, record):
+    """The best IoU with the record's ground truth over the first `count` spans of one sample (0 when there is none)."""
+    gt = [record['s_time'], record['e_time']]
+    return max([calculate_iou([st, et], gt) for st, et in spans_to_times(start, end, count, record['v_len'], record['duration'])], default=0.0)
+
+
+def summarise_topk(best_ious, k):
+    """Rank@K: the share of samples whose best IoU over their K spans reaches the threshold -> ({'k', 'r_k_i3', 'r_k_i5', 'r_k_i7', 'mIoU_k'}, text line)."""
+    r3, r5, r7 = (calculate_iou_accuracy(best_ious, t) for t in (0.3, 0.5, 0.7))
+    mi = float(np.mean(best_ious) * 100.0)
+    text = 'Rank@{k}, IoU=0.3: {:.2f}\tIoU=0.5: {:.2f}\tIoU=0.7: {:.2f}\tbest-of-{k} mean IoU: {:.2f}\n'.format(r3, r5, r7, mi, k=k)
+    return {'k': k, 'r_k_i3': r3, 'r_k_i5': r5, 'r_k_i7': r7, 'mIoU_k': mi}, text
+
+
+def _spans_to_host(s_idx, e_idx, spans):
+    """The indices of extract_index and, with `spans`, the (B, K) starts / ends and the counts of extract_topk, in ONE device-to-host copy."""
+    if spans is None:
+        idx = torch.stack([s_idx, e_idx]).cpu().numpy()
+        return idx[0], idx[1], None
+    K = spans.start.shape[1]
+    out = torch.cat([s_idx[:, None], e_idx[:, None], spans.start, spans.end, spans.count[:, None].long()], dim=1).cpu().numpy()
+    return out[:, 0], out[:, 1], (out[:, 2:2 + K], out[:, 2 + K:2 + 2 * K], out[:, 2 + 2 * K])
+
+
+def _finish(ious, best, topk, epoch, global_step):
+    out = summarise(ious, epoch, global_step)
+    if topk is None:
+        return out
+    stats, line = summarise_topk(best, topk.k)
+    return out[:4] + (out[4] + line, stats)
+
+
+def eval_test(model, data_loader, device, mode='test', epoch=None, global_step=None, topk=None):
     """runner_utils_t7.py:71-101.  The batch is moved with non-blocking copies (pinned staging when the loader pins), the
-    indices of the whole batch come back in one D2H copy."""
+    indices of the whole batch come back in one D2H copy.
+    `topk` (a TopK(k, nms_iou, max_span); no reference counterpart): the loop also asks for the k best moments per query (VSLNet.extract_topk) and
+    returns a sixth value, the Rank@K dict of summarise_topk, with one more line in the text; the first four values stay those of extract_index."""
     del mode
-    ious = []
+    ious, best = [], []
     with torch.no_grad():
         for records, vfeats, vfeat_lens, word_ids, char_ids in data_loader:
             vfeats, vfeat_lens = vfeats.to(device, non_blocking=True), vfeat_lens.to(device, non_blocking=True)
@@ -189,22 +224,27 @@ def eval_test(model, data_loader, device, mode='test', epoch=None, global_step=N
             video_mask = convert_length_to_mask(vfeat_lens)
             _, start_logits, end_logits = model(word_ids, char_ids, vfeats, video_mask, query_mask)
             s_idx, e_idx = model.extract_index(start_logits, end_logits)
-            idx = torch.stack([s_idx, e_idx]).cpu().numpy()
-            for r, si, ei in zip(records, idx[0], idx[1]):
+            spans = None if topk is None else model.extract_topk(start_logits, end_logits, topk.k, nms_iou=topk.nms_iou, max_span=topk.max_span,
+                                                                 v_mask=video_mask, want_prob=False)
+            s_host, e_host, sp = _spans_to_host(s_idx, e_idx, spans)
+            for n, (r, si, ei) in enumerate(zip(records, s_host, e_host)):
                 st, et = index_to_time(int(si), int(ei), r['v_len'], r['duration'])
                 ious.append(calculate_iou([st, et], [r['s_time'], r['e_time']]))
-    return summarise(ious, epoch, global_step)
+                if sp is not None:
+                    best.append(best_iou_of_spans(sp[0][n], sp[1][n], sp[2][n], r))
+    return _finish(ious, best, topk, epoch, global_step)
 
 
-def eval_test_shared(model, split, device, mode='test', epoch=None, global_step=None, videos_per_call=64):
+def eval_test_shared(model, split, device, mode='test', epoch=None, global_step=None, videos_per_call=64, topk=None):
     """eval_test over a `data.ResidentSplit` with every video encoded ONCE (split.encode -> VSLNet.encode_video) and each batch of records
     localised against that resident encoding (VSLNet.localize with the records' video indices): no (B, T, Dv) feature block is gathered and
-    VisualProjection + the video pass of the feature encoder run once per video instead of once per record.  Returns what eval_test returns.
+    VisualProjection + the video pass of the feature encoder run once per video instead of once per record.  Returns what eval_test returns
+    (`topk` as there; the valid lengths are the split's clips per record).
     An encoding belongs to its padded T, so every batch runs at the split's Tmax: the numbers are those of evaluating with every batch padded to
     Tmax -- what `model(...)` gives on `split.feats[:, :Tmax][vid]` -- not to the batch maximum as eval_test pads; the two differ, because the
     conv block's zero padding at the sequence end turns into pad-row values that the attention spreads to every row."""
     del mode, device
-    ious = []
+    ious, best = [], []
     bs, n = split.batch_size, len(split.records)
     with torch.no_grad():
         enc = split.encode(model, videos_per_call=videos_per_call)
@@ -218,9 +258,13 @@ def eval_test_shared(model, split, device, mode='test', epoch=None, global_step=
             query_mask = (word_ids != 0).float()
             _, start_logits, end_logits = model.localize(enc, split.vid_of[idx], word_ids, char_ids, query_mask, T=enc.T)
             s_idx, e_idx = model.extract_index(start_logits, end_logits)
-            out = torch.stack([s_idx, e_idx]).cpu().numpy()
-            for i, si, ei in zip(idx, out[0], out[1]):
+            spans = None if topk is None else model.extract_topk(start_logits, end_logits, topk.k, nms_iou=topk.nms_iou, max_span=topk.max_span,
+                                                                 lengths=torch.index_select(split.d_lens, 0, idx_dev), want_prob=False)
+            s_host, e_host, sp = _spans_to_host(s_idx, e_idx, spans)
+            for m, (i, si, ei) in enumerate(zip(idx, s_host, e_host)):
                 r = split.records[i]
                 st, et = index_to_time(int(si), int(ei), r['v_len'], r['duration'])
                 ious.append(calculate_iou([st, et], [r['s_time'], r['e_time']]))
-    return summarise(ious, epoch, global_step)
+                if sp is not None:
+                    best.append(best_iou_of_spans(sp[0][m], sp[1][m], sp[2][m], r))
+    return _finish(ious, best, topk, epoch, global_step)

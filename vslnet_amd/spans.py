@@ -1,0 +1,61 @@
+"""Top-K moments per query: the written specification of `vsl_extract_topk` (include/vslnet_hip.h) as brute-force numpy, and the conversion of
+its spans to seconds.  `topk_spans_reference` is what the tests compare the kernel with; the library never calls it."""
+from collections import namedtuple
+
+import numpy as np
+
+from .data import index_to_time
+
+# the evaluation loops' switch (runner.eval_test / eval_test_shared, main.py --topk / --nms_iou / --max_span)
+TopK = namedtuple('TopK', 'k nms_iou max_span')
+TopK.__new__.__defaults__ = (1.0, 0)
+
+
+def suppressed(s, e, cs, ce, nms_iou):
+    """Is the candidate span (s, e) suppressed by the chosen (cs, ce)?  Spans are clip intervals [s, e + 1); the compare is the kernel's: two
+    integers exact in float32 and ONE float32 multiply."""
+    inter = max(0, min(e, ce) - max(s, cs) + 1)
+    uni = (e - s + 1) + (ce - cs + 1) - inter
+    return inter > 0 and bool(np.float32(inter) > np.float32(nms_iou) * np.float32(uni))
+
+
+def topk_spans_reference(sl, el, k, nms_iou=1.0, max_span=0, lengths=None):
+    """(B, T) float32 logits -> start, end (B, k) int64, score (B, k) float32, prob (B, k) float64, count (B,) int32.
+    Per sample, L = lengths[b] clamped into [1, T] (T without lengths); candidates (s, e), 0 <= s <= e < L, e - s + 1 <= max_span when max_span > 0;
+    score = sl[s] + el[e] as one float32 addition; k greedy rounds, each taking the first maximum in row-major order of the candidates that are
+    neither chosen nor suppressed by an earlier choice (`suppressed`).  prob = exp(score - lse(sl) - lse(el)) in float64 over the sample's T
+    logits.  Slots from count on hold -1, -1, -inf, 0."""
+    sl, el = np.ascontiguousarray(sl, dtype=np.float32), np.ascontiguousarray(el, dtype=np.float32)
+    B, T = sl.shape
+    start, end = np.full((B, k), -1, dtype=np.int64), np.full((B, k), -1, dtype=np.int64)
+    score, prob = np.full((B, k), -np.inf, dtype=np.float32), np.zeros((B, k), dtype=np.float64)
+    count = np.zeros(B, dtype=np.int32)
+    si, ei = np.arange(T)[:, None], np.arange(T)[None, :]
+    for b in range(B):
+        L = T if lengths is None else min(max(int(lengths[b]), 1), T)
+        live = (si <= ei) & (ei < L)
+        if max_span > 0:
+            live &= ei - si + 1 <= max_span
+        sc = sl[b][:, None] + el[b][None, :]                     # float32 + float32 -> float32: one rounding
+        lse = [float(np.log(np.exp(x.astype(np.float64) - float(x.max())).sum()) + float(x.max())) for x in (sl[b], el[b])]
+        ln = (ei - si + 1).astype(np.float32)
+        for r in range(k):
+            if not live.any():
+                break
+            pick = int(np.argmax(np.where(live, sc, -np.inf)))   # argmax: the first maximum in row-major order (start ascending, then end ascending)
+            if not live.reshape(-1)[pick]:                       # (every live score is -inf: the first live candidate)
+                pick = int(np.flatnonzero(live)[0])
+            cs, ce = divmod(pick, T)
+            start[b, r], end[b, r], score[b, r] = cs, ce, sc[cs, ce]
+            prob[b, r] = np.exp(float(sc[cs, ce]) - lse[0] - lse[1])
+            count[b] = r + 1
+            live[cs, ce] = False
+            inter = np.maximum(0, np.minimum(ei, ce) - np.maximum(si, cs) + 1)
+            uni = ln + np.float32(ce - cs + 1) - inter.astype(np.float32)
+            live &= ~((inter > 0) & (inter.astype(np.float32) > np.float32(nms_iou) * uni))
+    return start, end, score, prob, count
+
+
+def spans_to_times(start, end, count, v_len, duration):
+    """The first `count` spans of one sample (clip indices) -> [(start_time, end_time)] in seconds, through data.index_to_time."""
+    return [index_to_time(int(s), int(e), v_len, duration) for s, e in zip(start[:int(count)], end[:int(count)])]
