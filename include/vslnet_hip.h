@@ -252,6 +252,24 @@ int vsl_backward(vsl_handle h, const vsl_io* io, void* hip_stream);
  * nothing.  Workspace needs and plans are those of the micro-batch's own shape: a global batch whose training plan exceeds the 2^31-float limit runs as
  * micro-batches that fit.  Detect the feature by the presence of the symbol: VSL_ABI_VERSION does not change for an added entry point. */
 int vsl_backward_accumulate(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh /* NULL after vsl_forward */, void* hip_stream);
+/* GRADIENT WITH RESPECT TO THE VIDEO FEATURES (what autograd returns as video_features.grad when the features require grad: a trainable adapter in
+ * front of the model, an adversarial perturbation, a saliency map).  vsl_backward stops one product short of it: it leaves d_video_affine, the
+ * gradient of VisualProjection's output, in the workspace.  This call computes
+ *     d_video_features[r][c] = m(r, c) * sum_{j < 128} d_video_affine[r][j] * W[j][c],      W = video_affine.linear.conv1d.weight as (128, video_feature_dim),
+ * m = the multiplier VisualProjection's dropout applied to feature (r, c) in the forward of this io (same seed, same sample_offset; 1 with
+ * training = 0 or drop_rate 0): dropped features get exactly 0, padded clips get the (generally non-zero) gradient autograd gives them.
+ *   - output: (B, T, video_feature_dim) fp32; after a shared step (N, T, video_feature_dim): the gradient of each VIDEO, summed over its queries in
+ *     ascending b.  With video_features_bf16 it is the fp32 gradient with respect to the widened features (the call never reads the features);
+ *   - legal after vsl_backward, vsl_backward_shared or vsl_backward_accumulate of the same io on the same stream, until the next forward of the
+ *     handle; with accumulation each micro-batch's call gives that micro-batch's rows.  It reads io->params, io->workspace, training, seed and
+ *     sample_offset, writes nothing but the output, and may be repeated (identical bits);
+ *   - ONE launch on the caller's stream (ledger label "vproj_dx"), fp32-grade: the fp32-input MFMA, a 128-term fmaf chain per element.  No plan
+ *     grows for it and vsl_forward / vsl_backward launch nothing for it: a caller who never asks pays nothing.
+ * Refused (vsl_last_error names the reason): a NULL output; no backward since the handle's last forward; a last forward that saved nothing
+ * (inference, vsl_encode_video, vsl_localize); an `sh` that does not match the last forward (the messages of vsl_backward / vsl_backward_shared); a last
+ * backward that applied fused_step -- the weight this product needs has been overwritten: run the backward without it, this call, then vsl_adamw_step.
+ * Detect the feature by the presence of the symbol: VSL_ABI_VERSION does not change for an added entry point. */
+int vsl_input_grads(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh /* NULL after vsl_forward */, float* d_video_features, void* hip_stream);
 /* first float offset of the parameter block whose gradients are final when vsl_io.early_grads_event fires (== vsl_param_floats()
  * when the configuration has no such block: the rnn predictor) */
 int64_t vsl_early_grad_offset(vsl_handle h);

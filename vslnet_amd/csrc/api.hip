@@ -1,5 +1,5 @@
-// C ABI of libvslnet_hip.so (declared in include/vslnet_hip.h).  Every entry point checks its arguments and states its own refusals; the five
-// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, the backward's three entry points) then go
+// C ABI of libvslnet_hip.so (declared in include/vslnet_hip.h).  Every entry point checks its arguments and states its own refusals; the ones
+// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, the backward's three entry points, vsl_input_grads) then go
 // through ONE path, enqueue(): plan of the shape, the call's context, the CallScope, the sequence of forward.hip / backward.hip, the launch-error
 // check and, for a forward, record_forward(): what it left for the calls behind it.  (layout.hip, plan.hip do the rest; the vsl_profile_* entry
 // points live with the profiler in streams.hip.)  Host code only -- no device code lives here.
@@ -29,6 +29,7 @@ static int workspace_floats(vsl_handle_s* h, PlanKind kind, int B, int T, int Lq
 // saved-path forward in that same workspace.
 static void record_forward(vsl_handle_s* h, vsl_handle_s::LastFwd kind, const float* workspace, int shared_N) {
     h->last_fwd = kind;
+    h->bwd_ws = nullptr; h->bwd_stepped = false;
     if (kind == vsl_handle_s::FwdShared) h->shared_N = shared_N;
     if (kind == vsl_handle_s::FwdInfer) h->infer_ws = workspace;
     else if (h->infer_ws == workspace) h->infer_ws = nullptr;
@@ -260,6 +261,7 @@ static int backward(vsl_handle_s* h, const vsl_io* io, const vsl_shared_io* sh, 
         })) return rc;
     // (after an accumulating call too: the reduction recorded the squares of the values it STORED, so they describe the bucket as it now is)
     h->sq_src = p->sq_cover ? p->sq_dev : nullptr; h->sq_n = p->nblocks; h->sq_grads = io->grads;
+    h->bwd_ws = io->workspace; h->bwd_stepped = io->fused_step != nullptr;
     return 0;
 }
 
@@ -359,6 +361,21 @@ int vsl_backward_accumulate(vsl_handle h, const vsl_io* io, const vsl_shared_io*
     if (!io->grads) return fail("vsl_backward_accumulate needs grads: the bucket that holds the running sum");
     if (int rc = sh ? check_shared_saves(h, io, sh, "vsl_backward_accumulate") : check_ordinary_saves(h, io, "vsl_backward_accumulate")) return rc;
     return backward(h, io, sh, hip_stream, "vsl_backward_accumulate", true);
+}
+
+// the gradient with respect to the video features, behind a backward of the same io: one launch (backward.hip run_input_grads)
+int vsl_input_grads(vsl_handle h, const vsl_io* io, const vsl_shared_io* sh, float* d_video_features, void* hip_stream) {
+    if (int rc = check_io(h, io)) return rc;
+    if (!d_video_features) return fail("vsl_input_grads: d_video_features is NULL (the (B, T, video_feature_dim) output; (N, T, video_feature_dim) after a shared step)");
+    if (int rc = sh ? check_shared_saves(h, io, sh, "vsl_input_grads") : check_ordinary_saves(h, io, "vsl_input_grads")) return rc;
+    if (!h->bwd_ws)
+        return fail("vsl_input_grads: no backward has run since the handle's last forward: the gradient of VisualProjection's output is not there yet "
+                    "(call vsl_backward, vsl_backward_shared or vsl_backward_accumulate on this io first)");
+    if (h->bwd_ws != io->workspace) return fail("vsl_input_grads: vsl_io.workspace is not the workspace the last backward ran in");
+    if (h->bwd_stepped)
+        return fail("vsl_input_grads: the last backward applied fused_step: VisualProjection's weight has been overwritten by the update.  Run the "
+                    "backward without fused_step, then vsl_input_grads, then vsl_adamw_step");
+    return enqueue(h, io, sh ? PlanKind::TrainShared : PlanKind::Train, sh, hip_stream, vsl_handle_s::FwdNone, [&](Ctx& c) { run_input_grads(c, d_video_features); });
 }
 
 int vsl_abi_version(void) { return VSL_ABI_VERSION; }

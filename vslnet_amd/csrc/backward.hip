@@ -591,4 +591,13 @@ void run_backward(Ctx& c) {
                                            p.sq_cover ? p.sq_dev : nullptr, p.nblocks}, c.s));
 }
 
+// vsl_input_grads: dX = dropmask * (d_video_affine W) over the rows of the plan's video half (N T in a shared step, where dvf already holds each
+// video's gradient summed over its queries).  Reads what run_backward left at p.dvf and VisualProjection's weight as the parameter bucket holds
+// it; allocates nothing, so a plan never sees this launch.
+void run_input_grads(Ctx& c, float* d_video_features) {
+    const Plan& p = *c.p;
+    LAUNCH("vproj_dx", launch_vproj_dx(VprojDxArgs{c.W(p.dvf), c.P(c.h->P.va_w), d_video_features, p.NV() * p.T, c.h->cfg.video_feature_dim,
+                                                   c.drop(SITE_VIS), c.h->cus}, c.s));
+}
+
 }  // namespace vsl

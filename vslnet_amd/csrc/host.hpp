@@ -129,6 +129,11 @@ struct vsl_handle_s {
     LastFwd last_fwd = FwdNone;          // its kind: vsl_backward / vsl_backward_shared refuse the other kind's saves, vsl_loss finds its scratch in that plan, and after
                                          // FwdInfer (inference forward, vsl_encode_video, vsl_localize) vsl_workspace_offset has nothing to point at
     int shared_N = 0;                    // N of the last vsl_forward_shared
+    // what the backward entry points left since that forward (api.hip backward; cleared by record_forward): vsl_input_grads reads d_video_affine out
+    // of the workspace and VisualProjection's weight out of vsl_io.params, so it needs a backward behind the forward, in that workspace, that has not
+    // stepped the parameters
+    const void* bwd_ws = nullptr;        // workspace of the last backward since the last forward (nullptr: none yet)
+    bool bwd_stepped = false;            // ... and it applied vsl_io.fused_step
     uint64_t plan_clock = 0;
     // side streams for the independent chains (query branch, weight gradients) + fork/join events
     hipStream_t side[2] = {nullptr, nullptr};
@@ -311,5 +316,6 @@ unsigned rnn_epoch(long long* gen = nullptr);
 void rnn_granules_fresh(Ctx& c, Plan& p, long long gen);
 // backward.hip
 void run_backward(Ctx& c);                      // the ordinary step, or (plan TrainShared, c.sh set unless dry) the step through a shared encoding
+void run_input_grads(Ctx& c, float* d_video_features);     // vsl_input_grads: one launch on c.s behind a backward of the same io
 
 }  // namespace vsl

@@ -483,6 +483,16 @@ struct EmbedBwdArgs {
 void launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s);
 void launch_word_table_bwd(const float* dE, const int64_t* word_ids, float* gtab /*(word_size, word_dim) inside the gradient bucket*/, int Rq,
                            int word_size, int word_dim, Drop dw, bool accumulate /* add to the rows the batch touches, leave the others */, hipStream_t s);
+// VisualProjection's data gradient (kernels_vproj_dx.hip; vsl_input_grads): dX (R, Dv) = m * (G W), m = the forward's dropout multiplier of each feature
+struct VprojDxArgs {
+    const float* G;                       // (R, 128) grad wrt VisualProjection's output (the plan's dvf)
+    const float* W;                       // (128, Dv) the Conv1D weight, unpacked, in the parameter bucket
+    float* dX;                            // (R, Dv) out
+    int R, Dv;                            // Dv: a multiple of 4, any size
+    Drop dp;                              // the forward's SITE_VIS
+    int cus;                              // CUs of the device (0: unknown): sizes the grid's second dimension
+};
+void launch_vproj_dx(const VprojDxArgs& a, hipStream_t s);
 void launch_reduce(const float* partial, float* grads, const ReduceSeg* segs_dev, const int* blk2seg_dev, int nblocks,
                    float* sq /* [nblocks]: sum of squares of each block's results */, bool accumulate /* grads += the sums ; sq of the stored values */,
                    hipStream_t s);

@@ -104,7 +104,7 @@ ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count',
                'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats',
                'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize',
                'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset',
-               'vsl_backward_accumulate', 'vsl_extract_topk']
+               'vsl_backward_accumulate', 'vsl_extract_topk', 'vsl_input_grads']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -164,6 +164,8 @@ def load_library():
         lib.vsl_backward_accumulate.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
     if hasattr(lib, 'vsl_extract_topk'):                     # (likewise: top-K spans with temporal NMS)
         lib.vsl_extract_topk.argtypes = [C.c_void_p, C.POINTER(vsl_topk_io), C.c_void_p]
+    if hasattr(lib, 'vsl_input_grads'):                      # (likewise: the gradient with respect to the video features)
+        lib.vsl_input_grads.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p, C.c_void_p]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
     lib.vsl_loss.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_loss_io), C.c_void_p]
     lib.vsl_backward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -249,6 +251,8 @@ class Engine:
         self.has_grad_accumulation = hasattr(self.lib, 'vsl_backward_accumulate')
         # vsl_extract_topk: the K best spans per sample with temporal NMS.  An older build lacks it; extract_topk then raises
         self.has_topk = hasattr(self.lib, 'vsl_extract_topk')
+        # vsl_input_grads: the gradient with respect to the video features, one launch behind a backward.  An older build lacks it; input_grads then raises
+        self.has_input_grads = hasattr(self.lib, 'vsl_input_grads')
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -692,6 +696,32 @@ class Engine:
         finally:
             io.fused_step = io.fused_loss = None          # (`fs` / the loss struct live until here; the library reads them during the call only)
         return grads
+
+    def input_grads(self, out=None):
+        """The gradient of the loss with respect to the video features of the LAST forward, behind its backward() (vsl_input_grads): -> fp32
+        (B, T, video_feature_dim); after forward_shared (N, T, video_feature_dim), each video's gradient summed over its queries.  It is
+        dropmask * (d_video_affine @ W) with the forward's own VisualProjection dropout mask: dropped features get exactly 0, padded clips their
+        (non-zero) gradient.  One launch; nothing else of the step changes, and backward() launches nothing for it.  With bfloat16 features it is the
+        fp32 gradient with respect to the widened features.  After backward(accumulate=True) it holds that micro-batch's rows.  `out`: a contiguous
+        fp32 cuda tensor of that shape to write into.
+        Raises VslError when no backward has run since the last forward, when that forward saved nothing (inference, encode_video, localize), and
+        when the last backward() had `fused_step` (the weight the product needs has been updated: call backward() without it, input_grads(), then
+        adamw_step(norm_from_backward=True))."""
+        if not self.has_input_grads:
+            raise VslError('the loaded library has no input gradients (vsl_input_grads is missing)')
+        io = self._last
+        if io is None:
+            raise VslError('input_grads(): no forward has run on this engine')
+        if io.inference:
+            raise VslError('input_grads(): the last forward was an inference forward (or encode_video / localize), which saved nothing')
+        sh = self._last_shared
+        shape = (sh.N if sh is not None else io.B, io.T, self.cfg.video_feature_dim)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _chk(out, torch.float32, shape, 'out')
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_input_grads(self.h, C.byref(io), C.byref(sh) if sh is not None else None, _ptr(out), stream))
+        return out
 
     def profile_select(self, kernel):
         """Time launches of `kernel` ('*' = all, None = off) with HIP events on the launch stream."""

@@ -13,7 +13,7 @@ training all-reduces as a single RCCL call (vslnet_amd/dp.py).
 import torch
 import torch.nn as nn
 
-from ..engine import Engine
+from ..engine import Engine, VslError
 from .layers import (Embedding, VisualProjection, FeatureEncoder, CQAttention, CQConcatenate, ConditionedPredictor,
                      HighLightLayer)
 
@@ -36,6 +36,18 @@ def build_optimizer_and_scheduler(model, configs):
     return optimizer, torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda)
 
 
+def _feature_grad(ctx, model):
+    """grad of the loss wrt the caller's `video_features` (behind the engine's backward): None unless autograd asks for it -- nothing extra is
+    launched then -- otherwise Engine.input_grads() in the caller's dtype and shape.  A library without the entry point raises: a silent None
+    would leave an adapter in front of the model untrained."""
+    if not ctx.needs_input_grad[3]:
+        return None
+    eng = model._engine
+    if not eng.has_input_grads:
+        raise VslError('video_features requires grad, but the loaded library has no input gradients (vsl_input_grads is missing)')
+    return eng.input_grads().view(ctx.vf_shape).to(ctx.vf_dtype)
+
+
 class _ForwardFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, word_ids, char_ids, vfeats, v_mask, q_mask, *params):
@@ -47,6 +59,7 @@ class _ForwardFn(torch.autograd.Function):
                                 vfeats.contiguous().float(), v_mask.contiguous().float(), q_mask.contiguous().float(),
                                 training=model.training, seed=(model._seed << 20) + model._step)
         ctx.model, ctx.token = model, model._step
+        ctx.vf_shape, ctx.vf_dtype = vfeats.shape, vfeats.dtype
         return h, sl, el
 
     @staticmethod
@@ -59,7 +72,7 @@ class _ForwardFn(torch.autograd.Function):
         # zeroed nor copied
         g = model._engine.backward(d_h.contiguous(), d_sl.contiguous(), d_el.contiguous(), torch.empty_like(model._flat_grad))
         views = model._engine.views(g)
-        return (None,) * 6 + tuple(views[n] for n in model._flat_names)
+        return (None, None, None, _feature_grad(ctx, model), None, None) + tuple(views[n] for n in model._flat_names)
 
 
 class _SharedForwardFn(torch.autograd.Function):
@@ -76,6 +89,7 @@ class _SharedForwardFn(torch.autograd.Function):
                                        v_mask.contiguous().float(), q_mask.contiguous().float(), video_index, training=model.training,
                                        seed=(model._seed << 20) + model._step)
         ctx.model, ctx.token = model, model._step
+        ctx.vf_shape, ctx.vf_dtype = vfeats.shape, vfeats.dtype
         return h, sl, el
 
     @staticmethod
@@ -86,7 +100,7 @@ class _SharedForwardFn(torch.autograd.Function):
                                'saved activations of the latest forward only')
         g = model._engine.backward(d_h.contiguous(), d_sl.contiguous(), d_el.contiguous(), torch.empty_like(model._flat_grad))
         views = model._engine.views(g)
-        return (None,) * 7 + tuple(views[n] for n in model._flat_names)
+        return (None, None, None, _feature_grad(ctx, model), None, None, None) + tuple(views[n] for n in model._flat_names)
 
 
 class _LossFn(torch.autograd.Function):
