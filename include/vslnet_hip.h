@@ -197,6 +197,62 @@ typedef struct {                       /* zero-initialise; new fields are append
 int vsl_localize_workspace_floats(vsl_handle h, int B, int T, int Lq, int Lc, int64_t* out);
 int vsl_localize(vsl_handle h, const vsl_localize_io* io, void* hip_stream);
 
+/* ONE ENCODING PER QUERY, TO BE ASKED ABOUT MANY VIDEOS (evaluation only: no dropout, nothing saved, no backward; no reference counterpart).  The word +
+ * char embedding, the Embedding linear and the query pass of the shared feature encoder do not depend on the video: vsl_encode_query runs that half of
+ * the inference forward for Q queries and writes the encoder's output -- bit for bit what vsl_forward's query branch leaves as the saved activation
+ * "qenc" for the same Q queries with training = 0 -- into the caller's (Q, Lq, 128) buffer.  It packs only the operands it reads (the char-conv image,
+ * the shared encoder's and the Embedding linear's; not VisualProjection's, the largest) and runs on the caller's stream alone.
+ * AN ENCODING BELONGS TO ITS PADDED Lq, to the Lc it was embedded at and to the parameter values it was computed with: the conv block's zero padding
+ * at the sequence end turns into pad-row values when Lq grows.  Where the query path is not sample-local (Lq > 32, or num_heads other than 8) a row is
+ * also rounded by its query's position in the batch when Lq is no multiple of 32, as vsl_encode_video records for T.  A caller re-encodes after the
+ * parameters change.
+ * The call marks its workspace like an inference forward: vsl_backward in it, and vsl_workspace_offset, are errors until a training forward has run.
+ * The trainable word table (word_table = 1: pad_vec / glove_vec ignored) works as in vsl_forward.  Limits: Q >= 1, 1 <= Lq <= min(max_pos_len, 128),
+ * Lc as in vsl_forward, Q Lq 128 floats below 2 GiB.  Detect the feature by the presence of the symbols: VSL_ABI_VERSION does not change for an added
+ * entry point. */
+typedef struct {                       /* zero-initialise; new fields are appended */
+    int32_t Q, Lq, Lc;                 /* queries (>= 1); padded query words / chars per word                                              */
+    const float* params;               /* flat parameter bucket                                                                            */
+    const float* pad_vec;              /* as in vsl_io                                                                                     */
+    const float* glove_vec;
+    const int64_t* word_ids;           /* (Q, Lq)                                                                                          */
+    const int64_t* char_ids;           /* (Q, Lq, Lc)                                                                                      */
+    const float* q_mask;               /* (Q, Lq)                                                                                          */
+    float* query_encoding;             /* out (Q, Lq, 128): the shared feature encoder's output on the embedded queries                    */
+    float* workspace;                  /* vsl_encode_query_workspace_floats() floats: the operand packs and the query branch's scratch      */
+} vsl_encode_query_io;
+int vsl_encode_query_workspace_floats(vsl_handle h, int Q, int Lq, int Lc, int64_t* out);
+int vsl_encode_query(vsl_handle h, const vsl_encode_query_io* io, void* hip_stream);
+
+/* PAIRS OF RESIDENT ENCODINGS: vsl_localize with no query branch at all (evaluation only; no reference counterpart).  Pair b reads video
+ * video_index[b] of an (N, T, 128) encoding from vsl_encode_video and query query_index[b] of a (Q, Lq, 128) encoding from vsl_encode_query with its
+ * (Q, Lq) mask; the call runs CQAttention, CQConcatenate, the highlight layer, the predictor and the span heads for the B pairs and writes what
+ * vsl_localize writes for the replicated queries word_ids[query_index], char_ids[query_index], q_mask[query_index] -- bit for bit where the query
+ * encoding does not depend on the query's position in its batch (num_heads 8 with Lq <= 32, or Lq a multiple of 32), within a few 1e-6 otherwise (see
+ * vsl_encode_query).  The reads of both encodings and of the word mask go through the indices (one scalar load per workgroup); everything written
+ * stays at pair b, and nothing here ever holds a (B, T, 128) or (B, Lq, 128) copy of an encoding.  It packs only the operands behind the two branches.
+ * Both encodings must come from the SAME parameter values as `params`, at this T and this Lq.  The indices are device arrays; 0 <= video_index[b] < N
+ * and 0 <= query_index[b] < Q are the CALLER'S precondition: the library does not read them on the host, and an index outside its range reads outside
+ * the encoding.  Refused by name: B, N, Q < 1; NULL encodings, masks or indices; Lq > 128; T > 4096 (and the limits of vsl_forward on T, Lq, B T).
+ * The call marks its workspace like an inference forward.  Detect the feature by the presence of the symbols: VSL_ABI_VERSION does not change for an
+ * added entry point. */
+typedef struct {                       /* zero-initialise; new fields are appended */
+    int32_t B, T, Lq, N, Q;            /* pairs; T of the video encoding; Lq of the query encoding; videos / queries in the encodings      */
+    const float* params;               /* the SAME parameter values both encodings were computed with                                      */
+    const float* video_encoding;       /* (N, T, 128) from vsl_encode_video with the SAME T                                                */
+    const float* v_mask;               /* (N, T): per VIDEO                                                                                */
+    const float* query_encoding;       /* (Q, Lq, 128) from vsl_encode_query with the SAME Lq                                              */
+    const float* q_mask;               /* (Q, Lq): per QUERY                                                                               */
+    const int32_t* video_index;        /* (B), device: video of pair b                                                                     */
+    const int32_t* query_index;        /* (B), device: query of pair b                                                                     */
+    float* h_score;                    /* out (B, T), as vsl_forward writes them                                                           */
+    float* start_logits;
+    float* end_logits;
+    float* workspace;                  /* vsl_pairs_workspace_floats() floats: the vsl_localize plan without the query branch's scratch    */
+} vsl_pairs_io;
+int vsl_pairs_workspace_floats(vsl_handle h, int B, int T, int Lq, int64_t* out);
+int vsl_localize_pairs(vsl_handle h, const vsl_pairs_io* io, void* hip_stream);
+
 /* TRAINING THROUGH A SHARED VIDEO ENCODING: one step over N videos and B queries, query b paired with video video_index[b] (no reference counterpart:
  * it runs the video half once per sample).  VisualProjection and encoder application 0 run forward AND backward on N T rows; the query branch,
  * CQAttention, CQConcatenate, the highlight layer, the predictor, the span heads and the losses run on B samples as in vsl_forward / vsl_backward.
@@ -307,6 +363,40 @@ typedef struct vsl_topk_io {               /* zero-initialise; new fields are ap
 } vsl_topk_io;
 int vsl_extract_topk(vsl_handle h, const vsl_topk_io* io, void* hip_stream);
 
+/* THE K_out BEST MOMENTS OF EVERY GROUP OF TOP-K LISTS: the device-side merge behind a search over several videos (no reference counterpart).  A list is
+ * what vsl_extract_topk leaves for one (query, video) pair -- K slots of (start, end, score) with a ranking `key` (normally its `prob`), `count` of them
+ * filled -- and a group is every list of one query.  Per group g the call writes K_out slots:
+ *   - candidates: slot k < min(count[b], K) of every list b with group_index[b] == g.  A group_index outside [0, G) puts the list in no group;
+ *   - every candidate carries a tag: tag[b] (the list's video, say), b itself when `tag` is NULL, or tag[b][k] with tag_per_slot != 0 (a (B, K) array:
+ *     the out_tag of an earlier merge, see below);
+ *   - order: key descending, then tag ascending, then list b ascending, then slot ascending.  That is a strict total order, so the K_out first
+ *     candidates are a pure function of the inputs: the same bits on every run, no atomic anywhere.  The lists need not be sorted;
+ *   - outputs (G, K_out): out_tag, out_list (the b a slot came from), out_start, out_end, out_score, out_key copied from the chosen candidate, and
+ *     out_count (G) = candidates written.  Slots from out_count[g] on hold -1, -1, -1, -1, -inf, 0.
+ * TWO LEVELS: a corpus too large for one call is merged in chunks and the chunks' results are merged again -- the first level's outputs are the second
+ * level's lists (K = the first level's K_out, count = its out_count, tag = its out_tag with tag_per_slot = 1, group_index = the group a row belongs
+ * to).  When every tag occurs in exactly one first-level call and every chunk's K_out is at least the final K_out, out_tag / out_start /
+ * out_end / out_score / out_key / out_count of the second level are exactly those of ONE call over all the lists: candidates that tie in key and tag sit
+ * in one chunk, whose output keeps their order (out_list then numbers the second level's rows).
+ * Limits: 1 <= K <= 32, 1 <= K_out <= 32, B >= 1, G >= 1; every pointer but `tag` is required.  NaN keys give an unspecified choice (every loop is
+ * bounded by B, K and K_out).  A free-standing call like vsl_extract_topk: it reads no plan and no workspace and is legal after any kind of forward; one
+ * workgroup per group, ONE launch on the caller's stream.  Detect the feature by the presence of the symbol: VSL_ABI_VERSION does not change for an
+ * added entry point. */
+typedef struct vsl_merge_io {              /* zero-initialise; new fields are appended */
+    int B, K, G, K_out;
+    const int64_t* start; const int64_t* end;             /* (B, K) */
+    const float* score; const float* key;                 /* (B, K) */
+    const int32_t* count;                                 /* (B,) */
+    const int32_t* group_index;                           /* (B,), device */
+    const int32_t* tag;                                   /* (B,), (B, K) with tag_per_slot, or NULL = b */
+    int32_t tag_per_slot;
+    int32_t* out_tag; int32_t* out_list;                  /* (G, K_out) */
+    int64_t* out_start; int64_t* out_end;                 /* (G, K_out) */
+    float* out_score; float* out_key;                     /* (G, K_out) */
+    int32_t* out_count;                                   /* (G,) */
+} vsl_merge_io;
+int vsl_merge_topk(vsl_handle h, const vsl_merge_io* io, void* hip_stream);
+
 /* Optimizer step on the flat buckets: clip_grad_norm_(grads, clip_norm) (main_t7.py:111) followed by AdamW with decoupled
  * weight decay (build_optimizer_and_scheduler, VSLNet_t7.py:8-17: no decay for names containing "bias", "layer_norm" or
  * "LayerNorm" -- the library derives that mask from its own parameter names).  Two kernels (one with norm_from_backward), no host synchronisation: the
@@ -346,7 +436,7 @@ typedef struct vsl_fused_step {
 } vsl_fused_step;
 
 /* workspace introspection for the parity tests: float offset of a named saved activation, -1 if unknown, -2 (and vsl_last_error()) when the
- * handle's last forward was an inference forward (or vsl_encode_video / vsl_localize), which saves nothing.
+ * handle's last forward was an inference forward (or vsl_encode_video / vsl_localize / vsl_encode_query / vsl_localize_pairs), which saves nothing.
  * names: "video_affine", "embedding_net", "venc", "qenc", "cq_attention", "cq_concat", "gated", "pred_s", "pred_e" */
 int64_t vsl_workspace_offset(vsl_handle h, int B, int T, int Lq, int Lc, const char* name);
 

@@ -27,6 +27,10 @@ What differs from the reference, by design:
     also asks the library for the K best moments per query (greedy temporal NMS, vsl_extract_topk) and reports Rank@K at IoU 0.3 / 0.5 / 0.7 and the
     best-of-K mean IoU beside the Rank@1 numbers, which stay those of extract_index.  0 (default): off, the output is what it was.  Like the other
     flags they go into configs.json and come back as defaults in --mode test (trained with --topk 5: Rank@5 there unless --topk 0 is given);
+  * `--corpus` (`--mode test`, `--data resident`, `--topk K` >= 1): after the usual numbers, every query of the test split is also run against EVERY
+    video of the split (runner.eval_corpus: videos and queries encoded once, VSLNet.retrieve ranks the moments of all videos on the device) and
+    corpus Rank@K at IoU 0.5 / 0.7 -- a returned moment in the ground-truth video at that IoU -- and video Recall@K are reported.  Off by default:
+    nothing printed or written changes.  `--mode train` only stores the flag in configs.json, where --mode test finds it as its default;
   * `--task synthetic` builds a small learnable dataset in the reference's record format (no dataset files needed).
 """
 import argparse
@@ -95,6 +99,8 @@ def build_parser():
     p.add_argument('--nms_iou', type=float, default=0.5, help='--topk: a candidate whose temporal IoU with an already chosen moment exceeds this is suppressed '
                    '(1.0: plain top-K, 0.0: disjoint moments only)')
     p.add_argument('--max_span', type=int, default=0, help='--topk: longest candidate moment in clips (0: unlimited)')
+    p.add_argument('--corpus', action='store_true', help='--mode test with --data resident and --topk K >= 1: also run every query against EVERY video of '
+                   'the test split (runner.eval_corpus) and report corpus Rank@K at IoU 0.5 / 0.7 and video Recall@K')
     p.add_argument('--synthetic_train', type=int, default=512)
     p.add_argument('--synthetic_test', type=int, default=128)
     return p
@@ -134,6 +140,17 @@ def check_accum(configs, world):
             raise ValueError('--accum_steps > 1 with --share_videos is refused: the shared step accumulates at the library and Engine level only '
                              '(Engine.backward(accumulate=True))')
     return accum
+
+
+def check_corpus(configs):
+    """--corpus in --mode test and what it needs (a configs.json from before the flag has none; --mode train only stores the flag)"""
+    if not getattr(configs, 'corpus', False) or configs.mode.lower() != 'test':
+        return False
+    if configs.data != 'resident':
+        raise ValueError('--corpus needs --data resident (every video of the split is encoded in device memory)')
+    if topk_of(configs) is None:
+        raise ValueError('--corpus needs --topk K >= 1: the moments returned per query')
+    return True
 
 
 def topk_of(configs):
@@ -354,6 +371,7 @@ def test(configs, parser, argv, dataset, features, device, log=print):
     model.load_state_dict(torch.load(runner.get_last_checkpoint(model_dir, suffix='t7'), map_location=device))
     model.eval()
     topk = topk_of(configs)
+    check_corpus(configs)
     if configs.data == 'resident':
         loader = data.ResidentSplit(dataset['test_set'], features, configs, device, train=False)
     else:
@@ -369,9 +387,16 @@ def test(configs, parser, argv, dataset, features, device, log=print):
         k = rank_k[0]['k']
         rows += [('Rank@%d, IoU=0.3' % k, rank_k[0]['r_k_i3']), ('Rank@%d, IoU=0.5' % k, rank_k[0]['r_k_i5']), ('Rank@%d, IoU=0.7' % k, rank_k[0]['r_k_i7']),
                  ('best-of-%d mean IoU' % k, rank_k[0]['mIoU_k'])]
+    corpus = {}
+    if getattr(configs, 'corpus', False):
+        stats, _ = runner.eval_corpus(model, loader, device, topk)
+        k = stats['k']
+        rows += [('Corpus Rank@%d, IoU=0.5' % k, stats['corpus_r_k_i5']), ('Corpus Rank@%d, IoU=0.7' % k, stats['corpus_r_k_i7']),
+                 ('video Recall@%d' % k, stats['video_recall_k'])]
+        corpus = {key: v for key, v in stats.items() if key != 'k'}
     for name, v in rows:
         log('\x1b[1;31m{}:\t{:.2f}\x1b[0m'.format(name, v))
-    return dict({'r1i3': r1i3, 'r1i5': r1i5, 'r1i7': r1i7, 'mIoU': mi}, **(rank_k[0] if rank_k else {}))
+    return dict({'r1i3': r1i3, 'r1i5': r1i5, 'r1i7': r1i7, 'mIoU': mi}, **(rank_k[0] if rank_k else {}), **corpus)
 
 
 def run(argv=None, log=print):
@@ -380,6 +405,7 @@ def run(argv=None, log=print):
     world, rank, local = _dist_env()
     check_accum(configs, world)                     # (before the dataset is built: a refused combination costs nothing)
     topk_of(configs)
+    check_corpus(configs)
     runner.set_th_config(configs.seed)
     dataset, features = data.load_dataset(configs)
     configs.char_size, configs.word_size = dataset['n_chars'], dataset['n_words']      # main_t7.py:52-53

@@ -1,5 +1,5 @@
 // C ABI of libvslnet_hip.so (declared in include/vslnet_hip.h).  Every entry point checks its arguments and states its own refusals; the ones
-// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, the backward's three entry points, vsl_input_grads) then go
+// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, vsl_encode_query, vsl_localize_pairs, the backward's three entry points, vsl_input_grads) then go
 // through ONE path, enqueue(): plan of the shape, the call's context, the CallScope, the sequence of forward.hip / backward.hip, the launch-error
 // check and, for a forward, record_forward(): what it left for the calls behind it.  (layout.hip, plan.hip do the rest; the vsl_profile_* entry
 // points live with the profiler in streams.hip.)  Host code only -- no device code lives here.
@@ -333,6 +333,55 @@ int vsl_localize(vsl_handle h, const vsl_localize_io* l, void* hip_stream) {
     });
 }
 
+// ---- one encoding per query, to be asked about many videos (evaluation only, like vsl_encode_video)
+int vsl_encode_query_workspace_floats(vsl_handle h, int Q, int Lq, int Lc, int64_t* out) { return workspace_floats(h, PlanKind::EncodeQuery, Q, 0, Lq, Lc, out); }
+
+int vsl_encode_query(vsl_handle h, const vsl_encode_query_io* e, void* hip_stream) {
+    if (!h || !e) return fail("null handle / io");
+    if (e->Q < 1) return fail("vsl_encode_query: Q=%d queries (at least one)", e->Q);
+    if (!e->params || (!h->cfg.word_table && (!e->pad_vec || !e->glove_vec)) || !e->word_ids || !e->char_ids || !e->q_mask || !e->query_encoding || !e->workspace)
+        return fail("vsl_encode_query_io has a null device pointer");
+    vsl_io io;
+    memset(&io, 0, sizeof io);
+    io.B = e->Q; io.Lq = e->Lq; io.Lc = e->Lc;
+    io.params = e->params; io.pad_vec = e->pad_vec; io.glove_vec = e->glove_vec;
+    io.word_ids = e->word_ids; io.char_ids = e->char_ids; io.q_mask = e->q_mask;
+    io.workspace = e->workspace; io.inference = 1;
+    // (FwdInfer: nothing saved -- vsl_backward in this workspace and vsl_workspace_offset are refused as after an inference forward)
+    return enqueue(h, &io, PlanKind::EncodeQuery, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) { forward_encode_query(c, e->query_encoding); });
+}
+
+// ---- pairs of resident encodings: vsl_localize with no query branch at all
+constexpr int PAIRS_PLAN_LC = 4;      // the pairs plan has no embedding: its key carries the smallest legal Lc
+
+int vsl_pairs_workspace_floats(vsl_handle h, int B, int T, int Lq, int64_t* out) { return workspace_floats(h, PlanKind::LocalizePairs, B, T, Lq, PAIRS_PLAN_LC, out); }
+
+int vsl_localize_pairs(vsl_handle h, const vsl_pairs_io* l, void* hip_stream) {
+    if (!h || !l) return fail("null handle / io");
+    if (l->B < 1) return fail("vsl_localize_pairs: B=%d pairs (at least one)", l->B);
+    if (l->N < 1) return fail("vsl_localize_pairs: N=%d videos in the encoding (at least one)", l->N);
+    if (l->Q < 1) return fail("vsl_localize_pairs: Q=%d queries in the encoding (at least one)", l->Q);
+    if (l->Lq > MAX_LQ) return fail("vsl_localize_pairs: Lq=%d > %d query words", l->Lq, MAX_LQ);
+    if (l->T > MAX_L) return fail("vsl_localize_pairs: T=%d > %d clips", l->T, MAX_L);
+    if (!l->video_encoding) return fail("vsl_localize_pairs: video_encoding is NULL (the output of vsl_encode_video for the same T and params)");
+    if (!l->query_encoding) return fail("vsl_localize_pairs: query_encoding is NULL (the output of vsl_encode_query for the same Lq and params)");
+    if (!l->v_mask) return fail("vsl_localize_pairs: v_mask is NULL (the (N, T) clip mask of the video encoding)");
+    if (!l->q_mask) return fail("vsl_localize_pairs: q_mask is NULL (the (Q, Lq) word mask of the query encoding)");
+    if (!l->video_index) return fail("vsl_localize_pairs: video_index is NULL (the video of each pair)");
+    if (!l->query_index) return fail("vsl_localize_pairs: query_index is NULL (the query of each pair)");
+    if (!l->params || !l->h_score || !l->start_logits || !l->end_logits || !l->workspace) return fail("vsl_pairs_io has a null device pointer");
+    vsl_io io;
+    memset(&io, 0, sizeof io);
+    io.B = l->B; io.T = l->T; io.Lq = l->Lq; io.Lc = PAIRS_PLAN_LC;
+    io.params = l->params;
+    io.h_score = l->h_score; io.start_logits = l->start_logits; io.end_logits = l->end_logits;
+    io.workspace = l->workspace; io.inference = 1;
+    return enqueue(h, &io, PlanKind::LocalizePairs, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) {
+        io.v_mask = c.W(c.p->vmask);          // every kernel behind the join reads the gathered (B, T) mask
+        forward_pairs(c, CqContext{l->video_encoding, l->video_index, l->query_encoding, l->q_mask, l->query_index}, l->v_mask);
+    });
+}
+
 int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_stream) {
     if (!h || !io || !l) return fail("null argument");
     if (!l->start_labels || !l->end_labels || !l->h_labels || !l->losses) return fail("vsl_loss_io has a null pointer");
@@ -411,6 +460,25 @@ int vsl_extract_topk(vsl_handle h, const vsl_topk_io* io, void* hip_stream) {
     if (!io->start_index || !io->end_index || !io->score) return fail("vsl_extract_topk: start_index, end_index and score are required outputs");
     launch_extract_topk(TopkArgs{io->start_logits, io->end_logits, io->valid_len, io->B, io->T, io->K, io->nms_iou, io->max_span, io->start_index,
                                  io->end_index, io->score, io->prob, io->count}, (hipStream_t)hip_stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int vsl_merge_topk(vsl_handle h, const vsl_merge_io* io, void* hip_stream) {
+    if (!h || !io) return fail("vsl_merge_topk: null argument");
+    if (io->B < 1) return fail("vsl_merge_topk: B=%d must be at least 1", io->B);
+    if (io->G < 1) return fail("vsl_merge_topk: G=%d must be at least 1", io->G);
+    if (io->K < 1 || io->K > TOPK_MAX_K) return fail("vsl_merge_topk: K=%d must be in [1, %d]", io->K, TOPK_MAX_K);
+    if (io->K_out < 1 || io->K_out > TOPK_MAX_K) return fail("vsl_merge_topk: K_out=%d must be in [1, %d]", io->K_out, TOPK_MAX_K);
+    if (!io->start || !io->end || !io->score || !io->key || !io->count) return fail("vsl_merge_topk: start, end, score, key and count are required inputs");
+    if (!io->group_index) return fail("vsl_merge_topk: null group_index");
+    if (io->tag_per_slot && !io->tag) return fail("vsl_merge_topk: tag_per_slot needs a (B, K) tag");
+    if (!io->out_tag || !io->out_list || !io->out_start || !io->out_end || !io->out_score || !io->out_key || !io->out_count)
+        return fail("vsl_merge_topk: out_tag, out_list, out_start, out_end, out_score, out_key and out_count are required outputs");
+    static const bool rescan_all = getenv("VSL_MERGE_RESCAN_ALL") != nullptr;      // (measuring switch of tools/merge_rate.py: the kernel without its cached heads)
+    launch_merge_topk(MergeArgs{io->start, io->end, io->score, io->key, io->count, io->group_index, io->tag, io->B, io->K, io->G, io->K_out,
+                                io->tag_per_slot != 0, rescan_all, io->out_tag, io->out_list, io->out_start, io->out_end, io->out_score, io->out_key,
+                                io->out_count}, (hipStream_t)hip_stream);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -1,5 +1,5 @@
 // The forward launch sequences: one encoder application, the rnn head's helpers, the stages (video branch, query branch, fusion + predictor)
-// and the three forwards composed from them.
+// and the forwards composed from them.
 #include "host.hpp"
 
 namespace vsl {
@@ -112,8 +112,9 @@ static void video_branch(Ctx& c, float* out) {
 // a pack launch another stream's kernel has to wait for: its stop event and its record in the profiler's ledger (nullptr / -1: nothing to wait for)
 struct PackWait { hipEvent_t ev = nullptr; int rec = -1; };
 
-// word + char embedding, then the Embedding linear + encoder application 1; `emb_pack`: the Embedding linear's operand when another stream packs it
-static void query_branch(Ctx& c, PackWait emb_pack) {
+// word + char embedding, then the Embedding linear + encoder application 1; `emb_pack`: the Embedding linear's operand when another stream packs it;
+// `out`: the caller's encoding (vsl_encode_query), nullptr = the plan's own buffer
+static void query_branch(Ctx& c, PackWait emb_pack, float* out = nullptr) {
     const vsl_config& cf = c.h->cfg; const ModelP& P = c.h->P; const ModelPk& K = c.h->K;
     const Plan& p = *c.p; const vsl_io& io = *c.io;
     const int B = p.B, Lq = p.Lq, Rq = B * Lq;
@@ -142,7 +143,7 @@ static void query_branch(Ctx& c, PackWait emb_pack) {
         qa.ln1_g = c.P(E.ln1g); qa.ln1_b = c.P(E.ln1b); qa.bq = c.P(E.qb); qa.bk = c.P(E.kb); qa.bv = c.P(E.vb);
         qa.h1 = c.SV(w.h1); qa.q = c.SV(w.q); qa.k = c.SV(w.k); qa.v = c.SV(w.v); qa.d1 = c.drop(16 + 4);
         qa.mask = io.q_mask; qa.ln2_g = c.P(E.ln2g); qa.ln2_b = c.P(E.ln2b); qa.bo = c.P(E.ob);
-        qa.att = c.SV(w.att); qa.lse = c.SV(w.lse); qa.r = c.SV(w.r); qa.h2 = c.SV(w.h2); qa.out = c.W(w.out);
+        qa.att = c.SV(w.att); qa.lse = c.SV(w.lse); qa.r = c.SV(w.r); qa.h2 = c.SV(w.h2); qa.out = out ? out : c.W(w.out);
         qa.d2 = c.drop(16 + 5); qa.d3 = c.drop(16 + 6); qa.d4 = c.drop(16 + 7); qa.d5 = c.drop(16 + 8);
         qa.EW = cf.word_dim + 100; qa.L = Lq; qa.b_off = 0;
         LAUNCH("query_fwd", launch_query_fwd(qa, B, c.s));
@@ -152,7 +153,7 @@ static void query_branch(Ctx& c, PackWait emb_pack) {
         LAUNCH("linear_fwd", launch_linear_fwd3(c.W(p.E), reinterpret_cast<const uint16_t*>(c.PK(K.emb_f3)), c.P(P.emb_b), c.W(p.qf), Rq, cf.word_dim + 100, c.s));
     else          // a width the 16-wide K steps of the split kernel do not tile: the fp32-input MFMA kernel (K streamed in chunks)
         LAUNCH("linear_fwd", launch_linear_fwd(c.W(p.E), c.PK(K.emb_f), c.P(P.emb_b), c.W(p.qf), Rq, cf.word_dim + 100, c.s));
-    enc_fwd(c, P.fe, K.fe, p.qe, c.W(p.qf), io.q_mask, B, 1);
+    enc_fwd(c, P.fe, K.fe, p.qe, c.W(p.qf), io.q_mask, B, 1, nullptr, out);
 }
 
 // CQAttention over the context and the encoded query, CQConcatenate, the highlight score, the predictor and the span heads -- the dependent chain
@@ -167,7 +168,8 @@ static void fuse_and_predict(Ctx& c, CqContext ctx) {
     static const bool fold_on = switch_on("VSL_CQ_FOLD", true);
     const bool cq_fold = fold_on && cq_col_folds(T, Lq);
     CqFwdArgs cq;
-    cq.C = ctx.C; cq.vidx = ctx.vidx; cq.Qf = c.W(p.qe.out); cq.vmask = io.v_mask; cq.qmask = io.q_mask;
+    cq.C = ctx.C; cq.vidx = ctx.vidx; cq.vmask = io.v_mask;
+    cq.Qf = ctx.Qf ? ctx.Qf : c.W(p.qe.out); cq.qmask = ctx.Qf ? ctx.qmask : io.q_mask; cq.qidx = ctx.Qf ? ctx.qidx : nullptr;
     cq.w4C = c.P(P.w4C); cq.w4Q = c.P(P.w4Q); cq.w4mlu = c.P(P.w4mlu);
     cq.S = c.W(p.S); cq.Srow = c.W(p.Srow); cq.Scol = c.SV(p.Scol);
     cq.Mpart = c.W(p.cqP1); cq.M = c.SV(p.M);       // the per-tile partials of M go where the backward's cqP1 arena is free until then
@@ -255,7 +257,7 @@ static void fuse_and_predict(Ctx& c, CqContext ctx) {
     if (!heads_hosted) LAUNCH("head_fwd", launch_head_fwd(hs, he, c.W(p.gated), io.v_mask, R, c.s));
 }
 
-// ---- the three forwards: which packs go where, what forks and what joins
+// ---- the forwards: which packs go where, what forks and what joins
 
 // The third stream's pack launches: the Embedding linear's operand first (the query branch waits for it behind embed_fwd: the returned PackWait),
 // then everything the two branches do not read.  The caller has made `sp` wait for whatever has to come first.
@@ -322,6 +324,17 @@ void forward_encode(Ctx& c, float* video_encoding) {
     video_branch(c, video_encoding);
 }
 
+// vsl_encode_query: the query half alone into the caller's buffer -- the char-conv image and the shared encoder's operands (the head of the first
+// class: VisualProjection's, its last jobs_va jobs, stay unpacked), the Embedding linear's operand, then the query branch.  One stream: there is
+// nothing to run beside it.
+void forward_encode_query(Ctx& c, float* query_encoding) {
+    const vsl_handle_s* h = c.h;
+    const int head = h->jobs_char + h->jobs_first;
+    LAUNCH("pack", launch_pack(c.io->params, c.W(c.p->pack), h->jobs_dev, head - h->jobs_va, c.s));
+    LAUNCH("pack", launch_pack(c.io->params, c.W(c.p->pack), h->jobs_dev + head, h->jobs_query, c.s));
+    query_branch(c, PackWait{}, query_encoding);
+}
+
 // vsl_localize: the query branch is the ONLY chain in front of the CQ kernels, so it owns the main stream and there is no fork and no join on the
 // dependent chain (each costs a ~6 - 20 us bubble, see Ctx::order_n); the packs it does not read and the mask gather run beside it on the third stream.
 // VisualProjection's operands -- the last jobs_va jobs of the first class, the largest pack job -- stay unpacked.
@@ -345,6 +358,23 @@ void forward_localize(Ctx& c, CqContext ctx, const float* vmask_nt) {
     c.s = c.main;
     query_branch(c, emb_pack);
     if (split3) c.order(sp, c.main);       // the remaining packs (long done) and the gathered mask
+    fuse_and_predict(c, ctx);
+}
+
+// vsl_localize_pairs: no query branch at all -- both sides of CQAttention are resident encodings read through their indices.  Only the "rest" class of
+// packs is needed (no char image, no shared-encoder, Embedding or VisualProjection operands); the mask gather runs beside it on the third stream.
+void forward_pairs(Ctx& c, CqContext ctx, const float* vmask_nt) {
+    const vsl_handle_s* h = c.h;
+    const Plan& p = *c.p;
+    const int nj = (int)h->jobs.size(), rest = h->jobs_char + h->jobs_first + h->jobs_query;
+    hipStream_t sp = c.side(1);
+    const bool split = sp != c.main;
+    if (split) { c.order(c.main, sp); c.s = sp; }      // (behind whatever the caller's stream holds: the workspace may still be read by an earlier call)
+    // the per-pair clip mask, beside the pack; first read by the CQ kernels, behind the join with its stream
+    LAUNCH("vmask_gather", launch_vmask_gather(vmask_nt, ctx.vidx, c.W(p.vmask), p.B, p.T, c.s));
+    c.s = c.main;
+    LAUNCH("pack", launch_pack(c.io->params, c.W(p.pack), h->jobs_dev + rest, nj - rest, c.s));
+    if (split) c.order(sp, c.main);
     fuse_and_predict(c, ctx);
 }
 

@@ -66,6 +66,8 @@ enum class PlanKind {
     Infer,      // what a forward keeps live, reused by liveness (build_infer_plan)
     Encode,     // vsl_encode_video: B = videos, Lq = Lc = 0 (build_encode_plan)
     Localize,   // vsl_localize: the inference plan without the video pass
+    LocalizePairs, // vsl_localize_pairs: the Localize plan without the query branch (no E, qf, qe, no embedding scratch)
+    EncodeQuery,// vsl_encode_query: B = queries, T = 0: the packs and the query branch's own scratch (build_query_plan)
     TrainShared // vsl_forward_shared / vsl_backward_shared: the training plan with the video half sized by N videos, everything else by B queries
 };
 
@@ -127,7 +129,7 @@ struct vsl_handle_s {
     const void* infer_ws = nullptr;      // workspace the last INFERENCE forward ran in (it holds no saves: vsl_backward on it is refused) ; a training forward in it clears this
     enum LastFwd { FwdNone, FwdFull, FwdInfer, FwdShared };
     LastFwd last_fwd = FwdNone;          // its kind: vsl_backward / vsl_backward_shared refuse the other kind's saves, vsl_loss finds its scratch in that plan, and after
-                                         // FwdInfer (inference forward, vsl_encode_video, vsl_localize) vsl_workspace_offset has nothing to point at
+                                         // FwdInfer (inference forward, vsl_encode_video, vsl_localize, vsl_encode_query, vsl_localize_pairs) vsl_workspace_offset has nothing to point at
     int shared_N = 0;                    // N of the last vsl_forward_shared
     // what the backward entry points left since that forward (api.hip backward; cleared by record_forward): vsl_input_grads reads d_video_affine out
     // of the workspace and VisualProjection's weight out of vsl_io.params, so it needs a backward behind the forward, in that workspace, that has not
@@ -305,10 +307,14 @@ void free_plan(Plan* p);
 bool prof_selected(const vsl_handle_s* h, const char* name);
 bool query_chain_is_longer(const Plan& p);      // after the backward's video / query fork
 // forward.hip
-struct CqContext { const float* C; const int* vidx; };     // the context of CQAttention: C (B, T, 128), or a resident (N, T, 128) encoding read through vidx (B)
+// the operands of CQAttention: the context C (B, T, 128), or a resident (N, T, 128) encoding read through vidx (B); the encoded query Qf (B, Lq, 128) with its
+// (B, Lq) mask -- nullptr: the plan's own query pass and vsl_io.q_mask -- or a resident (Q, Lq, 128) encoding and its (Q, Lq) mask read through qidx (B)
+struct CqContext { const float* C; const int* vidx; const float* Qf = nullptr; const float* qmask = nullptr; const int* qidx = nullptr; };
 void forward_full(Ctx& c);                      // vsl_forward, or (c.sh set, plan TrainShared) vsl_forward_shared
 void forward_encode(Ctx& c, float* video_encoding);
 void forward_localize(Ctx& c, CqContext ctx, const float* vmask_nt);
+void forward_encode_query(Ctx& c, float* query_encoding);
+void forward_pairs(Ctx& c, CqContext ctx, const float* vmask_nt);
 bool query_fused(const Ctx& c);
 std::vector<int> lstm_chunks(int T);
 extern std::atomic<unsigned long long> g_rnn_launches;

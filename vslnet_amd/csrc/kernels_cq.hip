@@ -18,16 +18,17 @@ namespace vsl {
 // =========================================================================================================
 // a11's WeightedPool (:253-259) and the pooled half of CQConcatenate's Conv1D (:268-274) for one sample: alpha, pooled, pb = W2 pooled + b.  Query-side only;
 // one 256-thread workgroup.  al: [128], pl: [128] floats of LDS.
-__device__ __forceinline__ void cq_pool_body(const float* __restrict__ Qf, const float* __restrict__ qmask, const CqPoolArgs& cp, int b, int Lq, float* al, float* pl) {
+// qsrc: first row of the sample's query in Qf / qmask (b Lq, or qidx[b] Lq when the queries are a resident encoding: vsl_localize_pairs); what is written stays at b.
+__device__ __forceinline__ void cq_pool_body(const float* __restrict__ Qf, const float* __restrict__ qmask, const CqPoolArgs& cp, int b, size_t qsrc, int Lq, float* al, float* pl) {
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const size_t qrow = (size_t)b * Lq;
     const float* pool_w = cp.pool_w; const float* Wcat = cp.Wcat; const float* bcat = cp.bcat;
     float* alpha = cp.alpha; float* pooled = cp.pooled; float* pb = cp.pb;
     // ---- WeightedPool: alpha = softmax_j(Q[j].w + mask) ; pooled = sum_j alpha_j Q[j]
     for (int jj = w; jj < Lq; jj += 4) {
-        const float* row = Qf + (qrow + jj) * D;
+        const float* row = Qf + (qsrc + jj) * D;
         const float d = wave_sum(row[lane] * pool_w[lane] + row[lane + 64] * pool_w[lane + 64]);
-        if (lane == 0) al[jj] = d + (1.f - qmask[qrow + jj]) * MASK_VALUE;
+        if (lane == 0) al[jj] = d + (1.f - qmask[qsrc + jj]) * MASK_VALUE;
     }
     __syncthreads();
     if (w == 0) {                              // a lane owns words lane and lane + 64
@@ -45,7 +46,7 @@ __device__ __forceinline__ void cq_pool_body(const float* __restrict__ Qf, const
         for (int j0 = 0; j0 < Lq; j0 += 8) {        // eight rows in flight; same summation order as one row at a time
             float qv[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) qv[u] = Qf[(qrow + min(j0 + u, Lq - 1)) * D + tid];
+            for (int u = 0; u < 8; ++u) qv[u] = Qf[(qsrc + min(j0 + u, Lq - 1)) * D + tid];
 #pragma unroll
             for (int u = 0; u < 8; ++u) if (j0 + u < Lq) acc += al[j0 + u] * qv[u];
         }
@@ -71,17 +72,20 @@ __device__ __forceinline__ void cq_pool_body(const float* __restrict__ Qf, const
 
 // VIDX (the three CQAttention kernels): the context of sample b is video vidx[b] of a resident (N, T, 128) encoding (vsl_localize) -- the READS of C
 // go through the index, one scalar load per workgroup; everything written stays at sample b.  VIDX = false: C is (B, T, 128), `vidx` is not read.
-template <int NU, bool VIDX>   // NU: words per lane of the row softmax: 8 (Lq <= 64), 12 (<= 96) or 16 (<= MAX_LQ = 128)
+// QIDX (the pairs instantiations, vsl_localize_pairs: always together with VIDX): the query of sample b is query qidx[b] of a resident (Q, Lq, 128)
+// encoding with its (Q, Lq) mask -- the READS of Qf and qmask go through the index the same way.  QIDX = false: `qidx` is not read.
+template <int NU, bool VIDX, bool QIDX>   // NU: words per lane of the row softmax: 8 (Lq <= 64), 12 (<= 96) or 16 (<= MAX_LQ = 128)
 __global__ __launch_bounds__(256) void k_cq_score(const float* __restrict__ C, const float* __restrict__ Qf,
                                                   const float* __restrict__ qmask, const float* __restrict__ w4C,
                                                   const float* __restrict__ w4Q, const float* __restrict__ w4mlu,
                                                   float* __restrict__ S, float* __restrict__ Srow, int T, int Lq, int b_off,
-                                                  Drop dc, Drop dq, CqPoolArgs cp, const int* __restrict__ vidx) {
+                                                  Drop dc, Drop dq, CqPoolArgs cp, const int* __restrict__ vidx, const int* __restrict__ qidx) {
     // cp.pool_w != nullptr: ONE extra workgroup per sample (blockIdx.x = number of tiles) runs the WeightedPool / pooled-bias path (the column kernel
     // is folded into k_cq_out then: launch_cq_out)
     if (cp.pool_w && blockIdx.x == gridDim.x - 1) {          // (block-uniform)
         extern __shared__ __attribute__((aligned(16))) float psm[];
-        cq_pool_body(Qf, qmask, cp, blockIdx.y, Lq, psm, psm + 128);
+        const int pb = blockIdx.y;
+        cq_pool_body(Qf, qmask, cp, pb, QIDX ? (size_t)qidx[pb] * Lq : (size_t)pb * Lq, Lq, psm, psm + 128);
         return;
     }
     // S[i][j] = Cd[i].w4C + Qd[j].w4Q + (Cd[i] * w4mlu).Qd[j]   (:233-243) on a 32-clip tile; Cd / Qd = dropped-out C / Q.
@@ -98,6 +102,7 @@ __global__ __launch_bounds__(256) void k_cq_score(const float* __restrict__ C, c
     const int b = blockIdx.y, t0 = blockIdx.x * TILE_M;
     const size_t crow = (size_t)b * T, qrow = (size_t)b * Lq;
     const size_t vrow = VIDX ? (size_t)vidx[b] * T : crow;      // first row of this sample's context in C
+    const size_t qsrc = QIDX ? (size_t)qidx[b] * Lq : qrow;     // ... of its query in Qf / qmask
     {   // one batch of 16-byte loads for both tiles, dropout applied on the way into LDS
         float4 cv[4], qv[8];
 #pragma unroll
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(256) void k_cq_score(const float* __restrict__ C, c
             for (int q = 0; q < 8; ++q) {
                 const int e = tid + (q0 + q) * 256, j = e >> 5, c = (e & 31) * 4;
                 qv[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (q0 + q < 4 * NTJ) qv[q] = *reinterpret_cast<const float4*>(Qf + (qrow + min(j, Lq - 1)) * D + c);
+                if (q0 + q < 4 * NTJ) qv[q] = *reinterpret_cast<const float4*>(Qf + (qsrc + min(j, Lq - 1)) * D + c);
             }
         };
         auto store_q = [&](int q0) {
@@ -223,7 +228,7 @@ __global__ __launch_bounds__(256) void k_cq_score(const float* __restrict__ C, c
             if (j < Lq) {
                 raw[u] = Pp[rr * PJ + j] + Pp[(TILE_M + rr) * PJ + j] + Pp[(2 * TILE_M + rr) * PJ + j] + Pp[(3 * TILE_M + rr) * PJ + j] +
                          s0[rr] + s1[j];
-                v[u] = raw[u] + (1.f - qmask[qrow + j]) * MASK_VALUE;
+                v[u] = raw[u] + (1.f - qmask[qsrc + j]) * MASK_VALUE;
                 mx = fmaxf(mx, v[u]);
             }
         }
@@ -241,28 +246,34 @@ __global__ __launch_bounds__(256) void k_cq_score(const float* __restrict__ C, c
         }
     }
 }
-template <int NU, bool VIDX> static void cq_score_go(const CqFwdArgs& a, const char* name, hipStream_t s) {
+template <int NU, bool VIDX, bool QIDX = false> static void cq_score_go(const CqFwdArgs& a, const char* name, hipStream_t s) {
     const int NTJ = (a.Lq + 31) / 32;
     const size_t shm = (size_t)((TILE_M + 32 * NTJ) * LDP + TILE_M + 32 * NTJ + 4 * TILE_M * (32 * NTJ + 1)) * sizeof(float);
     const dim3 grid((a.T + TILE_M - 1) / TILE_M + (a.fold ? 1 : 0), a.B);
-    dynamic_lds_optin<k_cq_score<NU, VIDX>>(shm, name);
-    VSL_LAUNCH((k_cq_score<NU, VIDX>), grid, dim3(256), shm, s, a.C, a.Qf, a.qmask, a.w4C, a.w4Q, a.w4mlu, a.S, a.Srow, a.T, a.Lq, a.b_off, a.dc, a.dq,
-               a.fold ? a.pool : CqPoolArgs{}, a.vidx);
+    dynamic_lds_optin<k_cq_score<NU, VIDX, QIDX>>(shm, name);
+    VSL_LAUNCH((k_cq_score<NU, VIDX, QIDX>), grid, dim3(256), shm, s, a.C, a.Qf, a.qmask, a.w4C, a.w4Q, a.w4mlu, a.S, a.Srow, a.T, a.Lq, a.b_off, a.dc, a.dq,
+               a.fold ? a.pool : CqPoolArgs{}, a.vidx, a.qidx);
 }
 void launch_cq_score(const CqFwdArgs& a, hipStream_t s) {
+    if (a.qidx) {        // (vsl_localize_pairs: both indices)
+        if (a.Lq <= 64) cq_score_go<8, true, true>(a, "k_cq_score<8, true, true>", s);
+        else if (a.Lq <= 96) cq_score_go<12, true, true>(a, "k_cq_score<12, true, true>", s);
+        else cq_score_go<16, true, true>(a, "k_cq_score<16, true, true>", s);
+        return;
+    }
     if (a.Lq <= 64) { if (a.vidx) cq_score_go<8, true>(a, "k_cq_score<8, true>", s); else cq_score_go<8, false>(a, "k_cq_score<8>", s); }
     else if (a.Lq <= 96) { if (a.vidx) cq_score_go<12, true>(a, "k_cq_score<12, true>", s); else cq_score_go<12, false>(a, "k_cq_score<12>", s); }
     else { if (a.vidx) cq_score_go<16, true>(a, "k_cq_score<16, true>", s); else cq_score_go<16, false>(a, "k_cq_score<16>", s); }
 }
 
-template <bool VIDX>
+template <bool VIDX, bool QIDX>
 __global__ __launch_bounds__(256) void k_cq_col(const float* __restrict__ C, const float* __restrict__ Qf,
                                                 const float* __restrict__ S, const float* __restrict__ cmask,
                                                 const float* __restrict__ qmask, const float* __restrict__ pool_w,
                                                 const float* __restrict__ Wcat, const float* __restrict__ bcat,
                                                 float* __restrict__ Scol, float* __restrict__ Mpart, float* __restrict__ alpha,
                                                 float* __restrict__ pooled, float* __restrict__ pb, int T, int Lq,
-                                                const int* __restrict__ vidx) {
+                                                const int* __restrict__ vidx, const int* __restrict__ qidx) {
     // Tile-parallel: workgroup = (32-clip tile, sample).  The column-softmax statistics need every clip of the sample, so
     // each workgroup recomputes them from the sample's whole score matrix (T x Lq floats, L2-resident, all 256 threads);
     // it then writes its S_col tile and the per-tile partial of M = S_col^T C (MFMA, gemm_tn); k_cq_out adds the partials.
@@ -353,7 +364,7 @@ __global__ __launch_bounds__(256) void k_cq_col(const float* __restrict__ C, con
     }
     return;
     }
-    cq_pool_body(Qf, qmask, CqPoolArgs{pool_w, Wcat, bcat, alpha, pooled, pb}, b, Lq, al, pl);
+    cq_pool_body(Qf, qmask, CqPoolArgs{pool_w, Wcat, bcat, alpha, pooled, pb}, b, QIDX ? (size_t)qidx[b] * Lq : qrow, Lq, al, pl);
 }
 bool cq_col_folds(int T, int Lq) { return T <= 4 * TILE_M && Lq <= 32; }      // (k_cq_out's fold: at most four tiles per sample, one 32-word tile of M)
 void launch_cq_col(const CqFwdArgs& a, hipStream_t s) {
@@ -362,9 +373,10 @@ void launch_cq_col(const CqFwdArgs& a, hipStream_t s) {
     const CqPoolArgs& p = a.pool;
     auto go = [&](auto kern) {
         VSL_LAUNCH(kern, grid, dim3(256), shm, s, a.C, a.Qf, a.S, a.vmask, a.qmask, p.pool_w, p.Wcat, p.bcat, a.Scol, a.Mpart, p.alpha, p.pooled, p.pb, a.T, a.Lq,
-                   a.vidx);
+                   a.vidx, a.qidx);
     };
-    if (a.vidx) go(k_cq_col<true>); else go(k_cq_col<false>);
+    if (a.qidx) go(k_cq_col<true, true>);        // (vsl_localize_pairs: both indices)
+    else if (a.vidx) go(k_cq_col<true, false>); else go(k_cq_col<false, false>);
 }
 
 // CQConcatenate + HighLightLayer + gating (a11 / a12, VSLNet_t7.py:60) ride on the same kernel (row-local on the tile just produced)
@@ -377,13 +389,13 @@ struct CqCatFuse {
     const float *S, *cmask;
     float* Scol;
 };
-template <bool VIDX>
+template <bool VIDX, bool QIDX>
 __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, const float* __restrict__ Qf,
                                                 const float* __restrict__ Srow, const float* __restrict__ Mpart,
                                                 float* __restrict__ M, const float* __restrict__ Wpack,
                                                 const float* __restrict__ bias, float* __restrict__ cat_out,
                                                 float* __restrict__ out, int T, int Lq, CqCatFuse cf,
-                                                const int* __restrict__ vidx) {
+                                                const int* __restrict__ vidx, const int* __restrict__ qidx) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int LQ1 = Lq + 1;
     // Lq > CQ_BIG_LQ: M lives where the concat tile will be written (it is dead by then, behind one extra barrier): 101 instead of 167 KB
@@ -397,6 +409,7 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
     const int b = blockIdx.y, t0 = blockIdx.x * TILE_M, ntile = gridDim.x;
     const size_t crow = (size_t)b * T, qrow = (size_t)b * Lq;
     const size_t vrow = VIDX ? (size_t)vidx[b] * T : crow;      // first row of this sample's context in C
+    const size_t qsrc = QIDX ? (size_t)qidx[b] * Lq : qrow;     // ... of its query in Qf
     BFrag<1, 16> bf;
     load_tile128(Cs, C + vrow * D, t0, TILE_M, T);
     if (cf.S) {                                // (block-uniform) k_cq_col's work for the whole sample, in the concat tile's LDS (dead until the concat)
@@ -507,7 +520,7 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
                 const int j = jc + 2 * u + hh;
                 const bool ok = j < Lq;
                 sv[u] = ok ? sa[jc + 2 * u] : 0.f;
-                qv[u] = ok ? Qf[(qrow + j) * D + col] : 0.f;
+                qv[u] = ok ? Qf[(qsrc + j) * D + col] : 0.f;
                 mv[u] = ok ? Ms[j * LDP + col] : 0.f;
             }
 #pragma unroll
@@ -598,17 +611,18 @@ __global__ __launch_bounds__(256) void k_cq_out(const float* __restrict__ C, con
         }
     }
 }
-template <bool VIDX> static void cq_out_go(const CqFwdArgs& a, const char* name, hipStream_t s) {
+template <bool VIDX, bool QIDX = false> static void cq_out_go(const CqFwdArgs& a, const char* name, hipStream_t s) {
     const int T = a.T, Lq = a.Lq;
     const size_t shm = (Lq > CQ_BIG_LQ ? (size_t)(std::max(TILE_M * CATP, Lq * LDP) + TILE_M * LDP + TILE_M * (Lq + 1) + 32)
                                        : (size_t)(TILE_M * CATP + TILE_M * LDP + Lq * LDP + TILE_M * (Lq + 1) + 32)) * sizeof(float);
     const dim3 grid((T + TILE_M - 1) / TILE_M, a.B);
     const CqCatFuse cf{a.W1pack, a.pool.pb, a.wh, a.bh, a.vmask, a.f2, a.hscore, a.gated, a.fold ? a.S : nullptr, a.fold ? a.vmask : nullptr, a.fold ? a.Scol : nullptr};
-    dynamic_lds_optin<k_cq_out<VIDX>>(shm, name);
-    VSL_LAUNCH(k_cq_out<VIDX>, grid, dim3(256), shm, s, a.C, a.Qf, a.Srow, a.Mpart, a.M, a.Wcqa, a.bcqa, a.cat, a.f1, T, Lq, cf, a.vidx);
+    dynamic_lds_optin<k_cq_out<VIDX, QIDX>>(shm, name);
+    VSL_LAUNCH((k_cq_out<VIDX, QIDX>), grid, dim3(256), shm, s, a.C, a.Qf, a.Srow, a.Mpart, a.M, a.Wcqa, a.bcqa, a.cat, a.f1, T, Lq, cf, a.vidx, a.qidx);
 }
 void launch_cq_out(const CqFwdArgs& a, hipStream_t s) {
-    if (a.vidx) cq_out_go<true>(a, "k_cq_out<true>", s); else cq_out_go<false>(a, "k_cq_out", s);
+    if (a.qidx) cq_out_go<true, true>(a, "k_cq_out<true, true>", s);        // (vsl_localize_pairs: both indices)
+    else if (a.vidx) cq_out_go<true>(a, "k_cq_out<true>", s); else cq_out_go<false>(a, "k_cq_out", s);
 }
 
 // the (N, T) clip mask of a resident encoding expanded to one row per query: out[b][t] = vmask[vidx[b]][t] (vsl_localize; the predictor, head and

@@ -331,6 +331,8 @@ struct CqFwdArgs {
     Drop dc, dq;                          // on C and on Qf in the trilinear score
     int fold;                             // the column kernel folded away (cq_col_folds): k_cq_score gets one extra workgroup per sample for the WeightedPool /
                                           // pooled-bias path, k_cq_out computes the sample's column softmax and M itself from S and launch_cq_col is not called
+    const int* qidx = nullptr;            // nullable, device, B ints (vsl_localize_pairs; only together with vidx): Qf is a resident (Q, Lq, 128) encoding and qmask its
+                                          // (Q, Lq) mask, sample b reads query qidx[b] (0 <= qidx[b] < Q is the caller's precondition); every output stays per sample
 };
 void launch_cq_score(const CqFwdArgs& a, hipStream_t s);
 void launch_cq_col(const CqFwdArgs& a, hipStream_t s);
@@ -366,6 +368,22 @@ struct TopkArgs {
 };
 constexpr int TOPK_MAX_K = 32;
 void launch_extract_topk(const TopkArgs& a, hipStream_t s);
+// the K_out best candidates of every group of top-K lists (kernels_merge.hip; the semantics: include/vslnet_hip.h, vsl_merge_topk)
+struct MergeArgs {
+    const int64_t *start, *end;           // (B, K) candidate lists
+    const float *score, *key;             // (B, K); the order is by key
+    const int32_t* count;                 // (B): filled slots of list b
+    const int32_t* group_index;           // (B): group of list b; outside [0, G): none
+    const int32_t* tag;                   // (B), or (B, K) with tag_per_slot; nullable = b
+    int B, K, G, K_out;                   // 1 <= K, K_out <= 32
+    int tag_per_slot;
+    int rescan_all;                       // measuring switch: no cached per-thread head
+    int32_t *out_tag, *out_list;          // (G, K_out)
+    int64_t *out_start, *out_end;
+    float *out_score, *out_key;
+    int32_t* out_count;                   // (G)
+};
+void launch_merge_topk(const MergeArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- backward
 // fuse != nullptr: the end head's workgroups continue with that attention-output backward on their own tile of dfeat (which is then NOT stored)

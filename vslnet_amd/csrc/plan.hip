@@ -65,10 +65,12 @@ void place_encoder(EncWs& w, int64_t region, int64_t RD) {
 // PlanKind::Localize (vsl_localize): the same plan without a video pass -- the context is the caller's resident encoding, so `a` serves the second predictor
 // pass / the end LSTM alone and nothing here ever holds a (B, T, 128) copy of the encoding; the (B, T) gathered clip mask is added and vsl_loss's
 // scratch (there is no vsl_io to call it with) left out, so the plan never exceeds the inference plan of the shape by more than B T floats.
+// PlanKind::LocalizePairs (vsl_localize_pairs): the Localize plan without the query branch's scratch -- the encoded queries are resident too.
 int build_infer_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind kind) {
     if (int rc = check_shape(h, B, T, Lq, Lc)) return rc;
     const vsl_config& cf = h->cfg;
-    const bool video = kind != PlanKind::Localize;
+    const bool video = kind != PlanKind::Localize && kind != PlanKind::LocalizePairs;
+    const bool query = kind != PlanKind::LocalizePairs;          // (vsl_localize_pairs: the encoded queries are the caller's, there is no query branch)
     Plan* p = new Plan();
     p->kind = kind;
     p->B = B; p->T = T; p->Lq = Lq; p->Lc = Lc;
@@ -80,8 +82,10 @@ int build_infer_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, 
     p->pack = al(h->pack_floats);
     if (video) p->loss_scratch = al(5 * (int64_t)B + 8);          // (vsl_loss on the outputs of an inference forward)
     // the query branch's own scratch (beside the video pass on another stream)
-    p->E = al(Rq * EW); p->qf = al(Rq * D);
-    p->qe.y[3] = al(Rq * D); p->qe.q = al(Rq * D); p->qe.k = al(Rq * D); p->qe.v = al(Rq * D); p->qe.att = al(Rq * D); p->qe.out = al(Rq * D);
+    if (query) {
+        p->E = al(Rq * EW); p->qf = al(Rq * D);
+        p->qe.y[3] = al(Rq * D); p->qe.q = al(Rq * D); p->qe.k = al(Rq * D); p->qe.v = al(Rq * D); p->qe.att = al(Rq * D); p->qe.out = al(Rq * D);
+    }
     p->pb = al((int64_t)B * D);
     // the region
     const int64_t nt = (T + TILE_M - 1) / TILE_M;
@@ -133,6 +137,35 @@ int build_encode_plan(vsl_handle_s* h, int N, int T, Plan** out) {
     p->partial = al(0);
     p->total = al.cur;
     if (p->total >= (int64_t(1) << 31)) { delete p; return fail("encode workspace of %lld floats exceeds the 2^31 offset range", (long long)p->total); }
+    *out = p;
+    return 0;
+}
+
+// vsl_encode_query: the operand packs and the query branch's own scratch of the inference plan -- the embedding concat E, the Embedding linear's
+// output and ONE encoder application's y3, q, k, v, att on B Lq rows.  The output goes to the caller's buffer.  B = queries; the plan has no video
+// side (T = 0 in its key).
+int build_query_plan(vsl_handle_s* h, int Q, int Lq, int Lc, Plan** out) {
+    const vsl_config& cf = h->cfg;
+    if (Q < 1 || Lq < 1) return fail("vsl_encode_query: empty call (Q=%d queries, Lq=%d words)", Q, Lq);
+    if (Lq > cf.max_pos_len)
+        return fail("sequence length (Lq=%d) exceeds max_pos_len=%d: the positional table has no such row (layers_t7.py:196 -- IndexError in the reference)", Lq, cf.max_pos_len);
+    if (Lq > MAX_LQ) return fail("Lq=%d > %d query words: the CQAttention kernels keep the whole query of a sample in LDS "
+                                 "(the reference truncates at max_pos_len words, data_gen.py:188)", Lq, MAX_LQ);
+    if ((int64_t)Q * Lq * D * 4 >= (int64_t(1) << 31))
+        return fail("Q*Lq = %lld rows: an (R, 128) fp32 activation must stay below 2 GiB for the 32-bit buffer offsets of the conv-block kernels (encode the queries in chunks)", (long long)Q * Lq);
+    if (Lc < 4 || Lc > MAX_LC) return fail("Lc=%d must be in [4, %d] (the widest char conv has kernel 4, layers_t7.py:52)", Lc, MAX_LC);
+    Plan* p = new Plan();
+    p->kind = PlanKind::EncodeQuery;
+    p->B = Q; p->T = 0; p->Lq = Lq; p->Lc = Lc;
+    const int64_t Rq = (int64_t)Q * Lq;
+    p->qe.R = (int)Rq; p->qe.L = Lq;
+    Bump al;
+    p->pack = al(h->pack_floats);
+    p->E = al(Rq * (cf.word_dim + 100)); p->qf = al(Rq * D);
+    p->qe.y[3] = al(Rq * D); p->qe.q = al(Rq * D); p->qe.k = al(Rq * D); p->qe.v = al(Rq * D); p->qe.att = al(Rq * D);
+    p->partial = al(0);
+    p->total = al.cur;
+    if (p->total >= (int64_t(1) << 31)) { delete p; return fail("encode-query workspace of %lld floats exceeds the 2^31 offset range", (long long)p->total); }
     *out = p;
     return 0;
 }
@@ -312,8 +345,10 @@ int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind
         case PlanKind::Train: rc = build_train_plan(h, B, T, Lq, Lc, &p); break;
         case PlanKind::TrainShared: rc = build_train_plan(h, B, T, Lq, Lc, &p, N); break;
         case PlanKind::Infer:
-        case PlanKind::Localize: rc = build_infer_plan(h, B, T, Lq, Lc, &p, kind); break;
+        case PlanKind::Localize:
+        case PlanKind::LocalizePairs: rc = build_infer_plan(h, B, T, Lq, Lc, &p, kind); break;
         case PlanKind::Encode: rc = build_encode_plan(h, B, T, &p); break;
+        case PlanKind::EncodeQuery: rc = build_query_plan(h, B, Lq, Lc, &p); break;
     }
     if (rc) return rc;
     if (h->plans.size() >= MAX_PLANS) {

@@ -67,6 +67,30 @@ class VideoEncoding:
         self.owner, self.epoch = owner, epoch
 
 
+class vsl_encode_query_io(C.Structure):
+    _fields_ = [('Q', C.c_int32), ('Lq', C.c_int32), ('Lc', C.c_int32), ('params', C.c_void_p), ('pad_vec', C.c_void_p), ('glove_vec', C.c_void_p),
+                ('word_ids', C.c_void_p), ('char_ids', C.c_void_p), ('q_mask', C.c_void_p), ('query_encoding', C.c_void_p), ('workspace', C.c_void_p)]
+
+
+class vsl_pairs_io(C.Structure):
+    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('Lq', C.c_int32), ('N', C.c_int32), ('Q', C.c_int32),
+                ('params', C.c_void_p), ('video_encoding', C.c_void_p), ('v_mask', C.c_void_p), ('query_encoding', C.c_void_p), ('q_mask', C.c_void_p),
+                ('video_index', C.c_void_p), ('query_index', C.c_void_p),
+                ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('workspace', C.c_void_p)]
+
+
+class QueryEncoding:
+    """What Engine.encode_query returns: the shared feature encoder's output for Q queries padded to Lq words (embedded at Lc chars per word), and
+    their word masks.  It belongs to its Lq and Lc and to the parameter values it was computed with (include/vslnet_hip.h).  `owner` / `epoch` are
+    set by VSLNet.encode_query, like VideoEncoding's."""
+    __slots__ = ('encoding', 'q_mask', 'Q', 'Lq', 'Lc', 'owner', 'epoch')
+
+    def __init__(self, encoding, q_mask, Lc, owner=None, epoch=None):
+        self.encoding, self.q_mask = encoding, q_mask
+        self.Q, self.Lq, self.Lc = int(encoding.shape[0]), int(encoding.shape[1]), int(Lc)
+        self.owner, self.epoch = owner, epoch
+
+
 class vsl_loss_io(C.Structure):
     _fields_ = [('start_labels', C.c_void_p), ('end_labels', C.c_void_p), ('h_labels', C.c_void_p),
                 ('w_loc', C.c_float), ('w_highlight', C.c_float), ('inv_batch', C.c_float), ('mask_sum', C.c_float),
@@ -94,6 +118,19 @@ class vsl_topk_io(C.Structure):
 TopkSpans = namedtuple('TopkSpans', 'start end score prob count')
 
 
+class vsl_merge_io(C.Structure):
+    _fields_ = [('B', C.c_int), ('K', C.c_int), ('G', C.c_int), ('K_out', C.c_int),
+                ('start', C.c_void_p), ('end', C.c_void_p), ('score', C.c_void_p), ('key', C.c_void_p), ('count', C.c_void_p),
+                ('group_index', C.c_void_p), ('tag', C.c_void_p), ('tag_per_slot', C.c_int32),
+                ('out_tag', C.c_void_p), ('out_list', C.c_void_p), ('out_start', C.c_void_p), ('out_end', C.c_void_p),
+                ('out_score', C.c_void_p), ('out_key', C.c_void_p), ('out_count', C.c_void_p)]
+
+
+# what Engine.merge_topk returns, per group: (G, k_out) int32 tag and list (the input list a slot came from), int64 start / end, fp32 score and prob
+# (the ranking key), (G,) int32 count; slots from count[g] on hold -1, -1, -1, -1, -inf, 0
+CorpusMoments = namedtuple('CorpusMoments', 'tag list start end score prob count')
+
+
 class VslError(RuntimeError):
     pass
 
@@ -104,7 +141,8 @@ ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count',
                'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats',
                'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize',
                'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset',
-               'vsl_backward_accumulate', 'vsl_extract_topk', 'vsl_input_grads']
+               'vsl_backward_accumulate', 'vsl_extract_topk', 'vsl_input_grads', 'vsl_merge_topk',
+               'vsl_encode_query_workspace_floats', 'vsl_encode_query', 'vsl_pairs_workspace_floats', 'vsl_localize_pairs']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -164,6 +202,14 @@ def load_library():
         lib.vsl_backward_accumulate.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
     if hasattr(lib, 'vsl_extract_topk'):                     # (likewise: top-K spans with temporal NMS)
         lib.vsl_extract_topk.argtypes = [C.c_void_p, C.POINTER(vsl_topk_io), C.c_void_p]
+    if hasattr(lib, 'vsl_encode_query'):                     # (likewise: one encoding per query)
+        lib.vsl_encode_query_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        lib.vsl_encode_query.argtypes = [C.c_void_p, C.POINTER(vsl_encode_query_io), C.c_void_p]
+    if hasattr(lib, 'vsl_localize_pairs'):                   # (likewise: pairs of resident encodings)
+        lib.vsl_pairs_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        lib.vsl_localize_pairs.argtypes = [C.c_void_p, C.POINTER(vsl_pairs_io), C.c_void_p]
+    if hasattr(lib, 'vsl_merge_topk'):                       # (likewise: the merge of top-K lists per group)
+        lib.vsl_merge_topk.argtypes = [C.c_void_p, C.POINTER(vsl_merge_io), C.c_void_p]
     if hasattr(lib, 'vsl_input_grads'):                      # (likewise: the gradient with respect to the video features)
         lib.vsl_input_grads.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p, C.c_void_p]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -253,6 +299,12 @@ class Engine:
         self.has_topk = hasattr(self.lib, 'vsl_extract_topk')
         # vsl_input_grads: the gradient with respect to the video features, one launch behind a backward.  An older build lacks it; input_grads then raises
         self.has_input_grads = hasattr(self.lib, 'vsl_input_grads')
+        # vsl_merge_topk: the k_out best moments of every group of top-K lists (a search over several videos).  An older build lacks it; merge_topk then raises
+        self.has_merge_topk = hasattr(self.lib, 'vsl_merge_topk')
+        # vsl_encode_query: the query half of the inference forward, once per query.  An older build lacks it; encode_query then raises
+        # ... and vsl_localize_pairs, which reads it: both or neither
+        self.has_query_encoding = all(hasattr(self.lib, s) for s in ('vsl_encode_query', 'vsl_encode_query_workspace_floats', 'vsl_localize_pairs',
+                                                                     'vsl_pairs_workspace_floats'))
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -529,6 +581,104 @@ class Engine:
         self._call(self.lib.vsl_encode_video(self.h, C.byref(io), stream))
         self._no_saves((flat, vfeats, v_mask, enc, ws))
         return VideoEncoding(enc, v_mask)
+
+    def _need_query_encoding(self):
+        if not self.has_query_encoding:
+            raise VslError('the loaded library has no query encodings (vsl_encode_query / vsl_localize_pairs are missing)')
+
+    def encode_query_workspace_floats(self, Q, Lq, Lc):
+        """Floats an encode_query call of Q queries padded to Lq words of Lc chars needs (operand packs + the query branch's scratch)."""
+        self._need_query_encoding()
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._call(self.lib.vsl_encode_query_workspace_floats(self.h, Q, Lq, Lc, C.byref(n)))
+        return int(n.value)
+
+    def encode_query(self, flat, pad_vec, glove_vec, word_ids, char_ids, q_mask):
+        """The word + char embedding, the Embedding linear and the query pass of the shared feature encoder for Q queries, once: -> QueryEncoding
+        (encoding (Q, Lq, 128), q_mask (Q, Lq)).  No dropout, nothing saved.  The encoding is the `qenc` of forward() on these queries, bit for bit,
+        and belongs to this Lq / Lc and to these parameter values."""
+        self._need_query_encoding()
+        if char_ids.dim() != 3 or char_ids.shape[0] < 1:
+            raise ValueError('encode_query: char_ids must be (Q, Lq, Lc) with Q >= 1 queries, got %s' % (tuple(char_ids.shape),))
+        Q, Lq, Lc = char_ids.shape
+        _chk(flat, torch.float32, (self.param_floats,), 'params')
+        _chk(word_ids, torch.int64, (Q, Lq), 'word_ids')
+        _chk(char_ids, torch.int64, (Q, Lq, Lc), 'char_ids')
+        _chk(q_mask, torch.float32, (Q, Lq), 'q_mask')
+        if self.cfg.word_table:
+            pad_vec = glove_vec = None
+        else:
+            _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
+            _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
+        self._flush_loss()
+        ws = self._grow_ws(self.encode_query_workspace_floats(Q, Lq, Lc))
+        enc = torch.empty(Q, Lq, 128, dtype=torch.float32, device=self.device)
+        io = vsl_encode_query_io()
+        io.Q, io.Lq, io.Lc = Q, Lq, Lc
+        io.params, io.pad_vec, io.glove_vec = _ptr(flat), _ptr(pad_vec), _ptr(glove_vec)
+        io.word_ids, io.char_ids, io.q_mask = _ptr(word_ids), _ptr(char_ids), _ptr(q_mask)
+        io.query_encoding, io.workspace = _ptr(enc), _ptr(ws)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_encode_query(self.h, C.byref(io), stream))
+        self._no_saves((flat, pad_vec, glove_vec, word_ids, char_ids, q_mask, enc, ws))
+        return QueryEncoding(enc, q_mask, Lc)
+
+    def pairs_workspace_floats(self, B, T, Lq):
+        """Floats a localize_pairs call of this shape needs (the localize plan without the query branch's scratch)."""
+        self._need_query_encoding()
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._call(self.lib.vsl_pairs_workspace_floats(self.h, B, T, Lq, C.byref(n)))
+        return int(n.value)
+
+    def _pair_index(self, index, n, name, what):
+        """an index of localize_pairs: a device tensor is trusted (no synchronising read), anything else range-checked and uploaded as int32"""
+        if isinstance(index, torch.Tensor) and index.is_cuda:
+            return index.to(torch.int32).contiguous()
+        host = torch.as_tensor(index).to(torch.int64).reshape(-1)
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n):
+            raise ValueError('localize_pairs: %s out of range: values in [%d, %d], the encoding holds %d %s' % (name, int(host.min()), int(host.max()), n, what))
+        return host.to(torch.int32).to(self.device)
+
+    def localize_pairs(self, flat, venc, qenc, video_index, query_index):
+        """localize() with no query branch: pair b is query query_index[b] of the resident QueryEncoding `qenc` in video video_index[b] of the resident
+        VideoEncoding `venc`.  -> (h_score, start_logits, end_logits), each (B, venc.T): what localize() returns for word_ids[query_index],
+        char_ids[query_index], q_mask[query_index] -- bit for bit where the query encoding does not depend on the query's position in its batch
+        (include/vslnet_hip.h).  Indices as in localize(): host values are range-checked, device tensors trusted.
+        `flat` must hold the parameter values both encodings were computed with (VSLNet.localize_pairs checks that through the handles' epochs)."""
+        self._need_query_encoding()
+        if not isinstance(venc, VideoEncoding):
+            raise TypeError('localize_pairs: venc must be the VideoEncoding that encode_video returned')
+        if not isinstance(qenc, QueryEncoding):
+            raise TypeError('localize_pairs: qenc must be the QueryEncoding that encode_query returned')
+        N, T, Q, Lq = venc.N, venc.T, qenc.Q, qenc.Lq
+        vidx = self._pair_index(video_index, N, 'video_index', 'videos')
+        qidx = self._pair_index(query_index, Q, 'query_index', 'queries')
+        B = int(vidx.numel())
+        if B < 1:
+            raise ValueError('localize_pairs: no pairs')
+        _chk(vidx, torch.int32, (B,), 'video_index')
+        _chk(qidx, torch.int32, (B,), 'query_index')
+        _chk(flat, torch.float32, (self.param_floats,), 'params')
+        _chk(venc.encoding, torch.float32, (N, T, 128), 'video encoding')
+        _chk(venc.v_mask, torch.float32, (N, T), 'v_mask')
+        _chk(qenc.encoding, torch.float32, (Q, Lq, 128), 'query encoding')
+        _chk(qenc.q_mask, torch.float32, (Q, Lq), 'q_mask')
+        self._flush_loss()
+        ws = self._grow_ws(self.pairs_workspace_floats(B, T, Lq))
+        out = torch.empty(3, B, T, dtype=torch.float32, device=self.device)
+        io = vsl_pairs_io()
+        io.B, io.T, io.Lq, io.N, io.Q = B, T, Lq, N, Q
+        io.params = _ptr(flat)
+        io.video_encoding, io.v_mask, io.query_encoding, io.q_mask = _ptr(venc.encoding), _ptr(venc.v_mask), _ptr(qenc.encoding), _ptr(qenc.q_mask)
+        io.video_index, io.query_index = _ptr(vidx), _ptr(qidx)
+        io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
+        io.workspace = _ptr(ws)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_localize_pairs(self.h, C.byref(io), stream))
+        self._no_saves((flat, venc, qenc, vidx, qidx, out, ws))
+        return out[0], out[1], out[2]
 
     def localize(self, flat, pad_vec, glove_vec, enc, video_index, word_ids, char_ids, q_mask):
         """Everything of forward() behind the video pass, for B queries against the resident encoding `enc`: query b is localised in video
@@ -812,6 +962,42 @@ class Engine:
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._call(self.lib.vsl_extract_topk(self.h, C.byref(io), stream))
         return TopkSpans(idx[0], idx[1], val[0], val[1] if want_prob else None, count)
+
+    def merge_topk(self, spans, group_index, G, k_out, tag=None):
+        """The k_out best moments of every group of top-k lists (include/vslnet_hip.h, vsl_merge_topk; the written specification:
+        vslnet_amd.spans.merge_topk_reference) -> CorpusMoments.  `spans`: a TopkSpans of B lists (extract_topk(want_prob=True); the ranking key is its
+        `prob`); `group_index` (B,) int32 on the device: the group (query) of list b, a value outside [0, G) drops the list; `tag`: None (list b is tagged
+        b), (B,) int32 (one tag per list: its video), or (B, k) int32 (one per slot: the `tag` of an earlier merge_topk whose result is merged again --
+        pass TopkSpans(m.start, m.end, m.score, m.prob, m.count) of that CorpusMoments m).  Order: prob descending, then tag, list, slot ascending."""
+        if not self.has_merge_topk:
+            raise VslError('the loaded library has no cross-list merge (vsl_merge_topk is missing)')
+        if spans.prob is None:
+            raise ValueError('merge_topk: the spans carry no prob to rank by (extract_topk(want_prob=True))')
+        B, K = spans.start.shape
+        for name, v in (('G', G), ('k_out', k_out)):         # (ctypes would wrap them; the library checks the ranges)
+            if not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError('merge_topk: %s=%d is not a C int' % (name, v))
+        _chk(spans.start, torch.int64, (B, K), 'spans.start')
+        _chk(spans.end, torch.int64, (B, K), 'spans.end')
+        _chk(spans.score, torch.float32, (B, K), 'spans.score')
+        _chk(spans.prob, torch.float32, (B, K), 'spans.prob')
+        _chk(spans.count, torch.int32, (B,), 'spans.count')
+        _chk(group_index, torch.int32, (B,), 'group_index')
+        per_slot = tag is not None and tag.dim() == 2
+        if tag is not None:
+            _chk(tag, torch.int32, (B, K) if per_slot else (B,), 'tag')
+        n = max(G, 0), max(k_out, 0)
+        i32 = torch.empty((2,) + n, dtype=torch.int32, device=self.device)
+        i64 = torch.empty((2,) + n, dtype=torch.int64, device=self.device)
+        f32 = torch.empty((2,) + n, dtype=torch.float32, device=self.device)
+        count = torch.empty(n[0], dtype=torch.int32, device=self.device)
+        io = vsl_merge_io(B, K, G, k_out, spans.start.data_ptr(), spans.end.data_ptr(), spans.score.data_ptr(), spans.prob.data_ptr(),
+                          spans.count.data_ptr(), group_index.data_ptr(), tag.data_ptr() if tag is not None else None, int(per_slot),
+                          i32[0].data_ptr(), i32[1].data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(), f32[0].data_ptr(), f32[1].data_ptr(),
+                          count.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_merge_topk(self.h, C.byref(io), stream))
+        return CorpusMoments(i32[0], i32[1], i64[0], i64[1], f32[0], f32[1], count)
 
 
 def flat_from_state_dict(engine, sd):

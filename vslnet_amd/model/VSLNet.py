@@ -282,6 +282,71 @@ class VSLNet(nn.Module):
         return eng.localize(self._flat, we.pad_vec.data if we.is_pretrained else None, we.glove_vec.data if we.is_pretrained else None, enc,
                             video_index, word_ids.contiguous(), char_ids.contiguous(), q_mask.contiguous().float())
 
+    # ---- one encoding per query, pairs of resident encodings, a search over the videos of an encoding (no reference counterpart) ----
+    def encode_query(self, word_ids, char_ids, q_mask):
+        """The embedding and the query pass of the shared feature encoder over Q queries, once: -> QueryEncoding for `localize_pairs` / `retrieve`.
+        The handle belongs to this module, this Lq / Lc and the parameters as they are now: `train()`, `load_state_dict` or moving the module make it
+        stale."""
+        self._shared_video_mode('encode_query')
+        eng = self._engine_for(char_ids.device)
+        we = self.embedding_net.word_emb
+        enc = eng.encode_query(self._flat, we.pad_vec.data if we.is_pretrained else None, we.glove_vec.data if we.is_pretrained else None,
+                               word_ids.contiguous(), char_ids.contiguous(), q_mask.contiguous().float())
+        enc.owner, enc.epoch = self, self._param_epoch
+        return enc
+
+    def _check_handle(self, enc, what, kind):
+        if getattr(enc, 'owner', None) is not self:
+            raise ValueError('VSLNet.%s: this %s was made by another module (or not by this module\'s encode call)' % (what, kind))
+        if enc.epoch != self._param_epoch:
+            raise ValueError('VSLNet.%s: stale %s -- the parameters may have changed since it was computed (train(), load_state_dict or a move ran '
+                             'in between): encode again' % (what, kind))
+
+    def localize_pairs(self, venc, qenc, video_index, query_index):
+        """localize() for pairs of resident encodings: pair b is query query_index[b] of `qenc` (encode_query) in video video_index[b] of `venc`
+        (encode_video).  -> (h_score, start_logits, end_logits), each (B, venc.T).  No query is embedded or encoded here.  Indices: list / numpy / CPU
+        tensor (range-checked) or a device tensor (trusted)."""
+        self._shared_video_mode('localize_pairs')
+        self._check_handle(venc, 'localize_pairs', 'VideoEncoding')
+        self._check_handle(qenc, 'localize_pairs', 'QueryEncoding')
+        eng = self._engine_for(venc.encoding.device)
+        self._step += 1                                     # (a graph built on an earlier forward is stale: its saves are overwritten)
+        return eng.localize_pairs(self._flat, venc, qenc, video_index, query_index)
+
+    def merge_topk(self, spans, group_index, G, k_out, tag=None):
+        """The k_out best moments of every group of top-k lists (Engine.merge_topk) -> CorpusMoments(tag, list, start, end, score, prob, count)."""
+        self._engine_for(spans.start.device)
+        return self._engine.merge_topk(spans, group_index, G, k_out, tag=tag)
+
+    def retrieve(self, venc, qenc, k, nms_iou=0.5, max_span=0, lengths=None, pairs_per_call=4096):
+        """The k best moments of every query of `qenc` over ALL videos of `venc` -> CorpusMoments shaped (Q, k): `tag` = the video (its number in
+        `venc`), start / end = the clips in that video, `prob` = the ranking key, descending; ties by video, then by the per-video rank.
+        Every query runs against every video in chunks of at most `pairs_per_call` pairs -- all queries x a block of videos: localize_pairs,
+        extract_topk(k, nms_iou, max_span, want_prob=True) per pair, merge_topk per query -- and one second merge_topk joins the chunks.  NMS acts
+        inside a video.  `lengths` (N,): valid clips per video (default: the row sums of venc.v_mask).  Nothing goes through the host."""
+        from ..engine import TopkSpans
+        self._shared_video_mode('retrieve')
+        self._check_handle(venc, 'retrieve', 'VideoEncoding')
+        self._check_handle(qenc, 'retrieve', 'QueryEncoding')
+        Q, N, dev = qenc.Q, venc.N, venc.encoding.device
+        if pairs_per_call < Q:
+            raise ValueError('retrieve: pairs_per_call=%d is less than one video for each of the %d queries' % (pairs_per_call, Q))
+        lengths = (venc.v_mask.sum(dim=1) if lengths is None else torch.as_tensor(lengths, device=dev)).to(torch.int32)
+        per = max(1, pairs_per_call // Q)                    # videos per chunk
+        queries = torch.arange(Q, dtype=torch.int32, device=dev)
+        first = []
+        for v0 in range(0, N, per):
+            nv = min(per, N - v0)
+            qidx = queries.repeat_interleave(nv)            # pair (q, v) at q * nv + (v - v0)
+            vidx = torch.arange(v0, v0 + nv, dtype=torch.int32, device=dev).repeat(Q)
+            _, sl, el = self.localize_pairs(venc, qenc, vidx, qidx)
+            spans = self.extract_topk(sl, el, k, nms_iou=nms_iou, max_span=max_span, lengths=lengths[vidx.long()], want_prob=True)
+            first.append(self.merge_topk(spans, qidx, Q, k, tag=vidx))
+        if len(first) == 1:
+            return first[0]
+        cat = lambda name: torch.cat([getattr(m, name) for m in first]).contiguous()      # noqa: E731
+        return self.merge_topk(TopkSpans(cat('start'), cat('end'), cat('score'), cat('prob'), cat('count')), queries.repeat(len(first)), Q, k, tag=cat('tag'))
+
     def extract_index(self, start_logits, end_logits):
         self._engine_for(start_logits.device)
         return self._engine.extract_index(start_logits.detach().contiguous(), end_logits.detach().contiguous())

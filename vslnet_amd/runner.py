@@ -268,3 +268,51 @@ def eval_test_shared(model, split, device, mode='test', epoch=None, global_step=
                 if sp is not None:
                     best.append(best_iou_of_spans(sp[0][m], sp[1][m], sp[2][m], r))
     return _finish(ious, best, topk, epoch, global_step)
+
+
+def corpus_hits(tag, start, end, count, record, video):
+    """One query's corpus result against its record: the best IoU over the returned moments that lie in the ground-truth video `video` (0 when none
+    does) and whether any does.  A moment in another video is a miss whatever its span."""
+    gt = [record['s_time'], record['e_time']]
+    inside = [r for r in range(int(count)) if int(tag[r]) == int(video)]
+    best = max([calculate_iou(list(index_to_time(int(start[r]), int(end[r]), record['v_len'], record['duration'])), gt) for r in inside], default=0.0)
+    return best, bool(inside)
+
+
+def summarise_corpus(best_ious, found, k):
+    """Corpus Rank@K: the share of queries with a returned moment IN THE GROUND-TRUTH VIDEO at IoU >= 0.5 / 0.7, and video Recall@K: the share with any
+    returned moment in that video -> ({'k', 'corpus_r_k_i5', 'corpus_r_k_i7', 'video_recall_k'}, text line)."""
+    r5, r7 = (calculate_iou_accuracy(best_ious, t) for t in (0.5, 0.7))
+    rec = float(np.mean(np.asarray(found, dtype=np.float64)) * 100.0)
+    text = 'Corpus Rank@{k}, IoU=0.5: {:.2f}\tIoU=0.7: {:.2f}\tvideo Recall@{k}: {:.2f}\n'.format(r5, r7, rec, k=k)
+    return {'k': k, 'corpus_r_k_i5': r5, 'corpus_r_k_i7': r7, 'video_recall_k': rec}, text
+
+
+def eval_corpus(model, split, device, topk, videos_per_call=64, pairs_per_call=4096):
+    """Moment retrieval over the whole split (no reference counterpart): every record's query is run against EVERY video of a `data.ResidentSplit`,
+    not only its own.  The videos are encoded once at the split's Tmax (split.encode, as eval_test_shared does), the queries batch by batch
+    (VSLNet.encode_query), and VSLNet.retrieve returns each query's topk.k best moments over all videos, ranked on the device; one device-to-host
+    copy per batch brings (video, start, end, count) back.  -> (stats dict, text line) of summarise_corpus.  `topk`: a TopK(k, nms_iou, max_span)."""
+    del device
+    if topk is None:
+        raise ValueError('eval_corpus needs topk = TopK(k >= 1, nms_iou, max_span): the moments returned per query')
+    best, found = [], []
+    bs, n = split.batch_size, len(split.records)
+    with torch.no_grad():
+        venc = split.encode(model, videos_per_call=videos_per_call)
+        d_order = torch.arange(n, device=split.device)
+        for a in range(0, n, bs):
+            idx = np.arange(a, min(n, a + bs))
+            idx_dev = d_order[a:a + bs]
+            Lq, Lc = int(split.nwords[idx].max()), int(split.nchars[idx].max())
+            word_ids = torch.index_select(split.d_words[:, :Lq], 0, idx_dev)
+            char_ids = torch.index_select(split.d_chars[:, :Lq, :Lc], 0, idx_dev)
+            qenc = model.encode_query(word_ids, char_ids, (word_ids != 0).float())
+            m = model.retrieve(venc, qenc, topk.k, nms_iou=topk.nms_iou, max_span=topk.max_span, pairs_per_call=max(pairs_per_call, len(idx)))
+            out = torch.cat([m.tag.long(), m.start, m.end, m.count[:, None].long()], dim=1).cpu().numpy()
+            K = topk.k
+            for q, i in enumerate(idx):
+                b, f = corpus_hits(out[q, :K], out[q, K:2 * K], out[q, 2 * K:3 * K], out[q, 3 * K], split.records[i], split.vid_of[i])
+                best.append(b)
+                found.append(f)
+    return summarise_corpus(best, found, topk.k)

@@ -1,5 +1,6 @@
-"""Top-K moments per query: the written specification of `vsl_extract_topk` (include/vslnet_hip.h) as brute-force numpy, and the conversion of
-its spans to seconds.  `topk_spans_reference` is what the tests compare the kernel with; the library never calls it."""
+"""Top-K moments per query: the written specifications of `vsl_extract_topk` and `vsl_merge_topk` (include/vslnet_hip.h) as brute-force numpy, and the
+conversion of spans to seconds.  `topk_spans_reference` and `merge_topk_reference` are what the tests compare the kernels with; the library never
+calls them."""
 from collections import namedtuple
 
 import numpy as np
@@ -54,6 +55,35 @@ def topk_spans_reference(sl, el, k, nms_iou=1.0, max_span=0, lengths=None):
             uni = ln + np.float32(ce - cs + 1) - inter.astype(np.float32)
             live &= ~((inter > 0) & (inter.astype(np.float32) > np.float32(nms_iou) * uni))
     return start, end, score, prob, count
+
+
+def merge_topk_reference(start, end, score, key, count, group_index, G, k_out, tag=None):
+    """B lists of K slots -> per group g: tag, list (G, k_out) int32, start, end (G, k_out) int64, score, key (G, k_out) float32, count (G,) int32.
+    Candidates of group g: slot k < min(count[b], K) of every list b with group_index[b] == g (a group_index outside [0, G): no group).  A candidate's
+    tag is tag[b], tag[b][k] for a (B, K) tag, b without one.  They are sorted by key descending, then tag, list and slot ascending -- a strict total
+    order -- and the first k_out are written.  Slots from count[g] on hold -1, -1, -1, -1, -inf, 0."""
+    start, end = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+    score, key = np.asarray(score, dtype=np.float32), np.asarray(key, dtype=np.float32)
+    B, K = start.shape
+    tag = None if tag is None else np.asarray(tag)
+    out_tag, out_list = np.full((G, k_out), -1, dtype=np.int32), np.full((G, k_out), -1, dtype=np.int32)
+    out_start, out_end = np.full((G, k_out), -1, dtype=np.int64), np.full((G, k_out), -1, dtype=np.int64)
+    out_score, out_key = np.full((G, k_out), -np.inf, dtype=np.float32), np.zeros((G, k_out), dtype=np.float32)
+    out_count = np.zeros(G, dtype=np.int32)
+    cands = [[] for _ in range(G)]
+    for b in range(B):
+        g = int(group_index[b])
+        if not 0 <= g < G:
+            continue
+        for k in range(min(int(count[b]), K)):
+            t = b if tag is None else int(tag[b, k]) if tag.ndim == 2 else int(tag[b])
+            cands[g].append((-float(key[b, k]), t, b, k))
+    for g in range(G):
+        for r, (_, t, b, k) in enumerate(sorted(cands[g])[:k_out]):
+            out_tag[g, r], out_list[g, r], out_start[g, r], out_end[g, r] = t, b, start[b, k], end[b, k]
+            out_score[g, r], out_key[g, r] = score[b, k], key[b, k]
+            out_count[g] = r + 1
+    return out_tag, out_list, out_start, out_end, out_score, out_key, out_count
 
 
 def spans_to_times(start, end, count, v_len, duration):
