@@ -397,6 +397,65 @@ typedef struct vsl_merge_io {              /* zero-initialise; new fields are ap
 } vsl_merge_io;
 int vsl_merge_topk(vsl_handle h, const vsl_merge_io* io, void* hip_stream);
 
+/* SLIDING WINDOWS OVER A VIDEO OF ANY LENGTH (no reference counterpart: it resamples every video down to max_pos_len clips).  A trained model runs over
+ * overlapping windows of T clips; two calls make that a device-side path.
+ *
+ * vsl_encode_windows: VisualProjection ONCE over the `rows` feature rows of the call, then encoder application 0 over N windows of T clips.  Window n
+ * is feature rows window_row[n] .. window_row[n] + window_len[n] - 1.  The result is what vsl_encode_video writes for the materialised batch
+ *     X[n][t] = features[window_row[n] + t]  for t < window_len[n],  a zero feature row otherwise,       v_mask[n][t] = t < window_len[n]
+ * and the library never builds X: a clip that lies in several windows is projected once, and one launch (ledger label "window_gather") copies each
+ * window's projected rows -- and, into the pad rows, the projection of a zero row, which is the bias -- into the slot the encoder reads.  The
+ * encoding is bit for bit vsl_encode_video's on X at the same N and T.
+ *   - window_row, window_len: (N) int32 on the DEVICE.  A source row outside [0, rows), or t >= window_len[n], is a pad row: a bad table cannot read
+ *     outside the features.  window_len[n] in 1..T is the caller's precondition (0 gives an all-pad window, whose softmax over no key is the caller's
+ *     problem as with an all-zero v_mask in vsl_encode_video);
+ *   - outputs: video_encoding (N, T, 128) and v_mask (N, T), both written; together they are a resident encoding for vsl_localize / vsl_localize_pairs;
+ *   - workspace: vsl_encode_windows_workspace_floats = the plan of vsl_encode_video at (N, T) plus rows * 128 floats;
+ *   - the call marks its workspace like an inference forward (nothing saved; vsl_backward there and vsl_workspace_offset are refused).
+ * Refused by name: N < 1; T outside 1 .. min(4096, max_pos_len); rows < 1; rows * video_feature_dim, rows * 128 or N * T * 128 at or above 2^31; a NULL
+ * pointer.  Detect the feature by the presence of the symbols: VSL_ABI_VERSION does not change for an added entry point. */
+typedef struct vsl_encode_windows_io {     /* zero-initialise; new fields are appended */
+    int32_t rows, N, T;                    /* feature rows of the call ; windows ; clips per window                                            */
+    const float* params;
+    const float* video_features;           /* (rows, video_feature_dim) fp32, or NULL with video_features_bf16                                 */
+    const uint16_t* video_features_bf16;   /* bf16 throughput mode, as vsl_io.video_features_bf16                                              */
+    const int32_t* window_row;             /* (N), device: first feature row of window n                                                       */
+    const int32_t* window_len;             /* (N), device: valid clips of window n                                                             */
+    float* video_encoding;                 /* (N, T, 128) out                                                                                  */
+    float* v_mask;                         /* (N, T) out                                                                                       */
+    float* workspace;                      /* vsl_encode_windows_workspace_floats() floats                                                     */
+} vsl_encode_windows_io;
+int vsl_encode_windows_workspace_floats(vsl_handle h, int N, int T, int rows, int64_t* out);
+int vsl_encode_windows(vsl_handle h, const vsl_encode_windows_io* io, void* hip_stream);
+
+/* vsl_merge_windows: the K_out best moments of every GROUP of window lists in the video's own clip coordinates, with temporal NMS across the lists.  A
+ * list is what vsl_extract_topk leaves for one (window, query) pair at window-local indices; a group is every window of one (query, video) pair;
+ * offset[b] is the clip index of list b's window start (NULL: 0 everywhere).  Per group g:
+ *   - candidates: slot k < min(count[b], K) of every list b with group_index[b] == g (a group_index outside [0, G): no group); the global span of a
+ *     candidate is (start + offset[b], end + offset[b]), which must fit an int32;
+ *   - order: key descending, then global start, global end, list and slot ascending -- a strict total order;
+ *   - K_out rounds; each takes the first candidate in that order that is not suppressed by an earlier choice of the group;
+ *   - a candidate is suppressed by a chosen span iff the two global spans are IDENTICAL (at every nms_iou: a moment two windows report is written
+ *     once) or vsl_extract_topk's rule holds on the global spans (the same integers, one fp32 multiply).  nms_iou = 1 removes duplicates only;
+ *   - outputs (G, K_out): out_list (the b a slot came from), out_start, out_end (global), out_score, out_key, and out_count (G) = rounds that found a
+ *     candidate.  Slots from out_count[g] on hold -1, -1, -1, -inf, 0.
+ * Limits, each refused by name: 1 <= K <= 32, 1 <= K_out <= 32, B >= 1, G >= 1, 0 <= nms_iou <= 1; every pointer but `offset` is required.  NaN keys
+ * give an unspecified choice (every loop is bounded by B, K and K_out).  A free-standing call like vsl_merge_topk: no plan, no workspace, no atomic --
+ * the same bits on every run; one workgroup per group, ONE launch on the caller's stream.  Detect the feature by the presence of the symbol. */
+typedef struct vsl_merge_windows_io {      /* zero-initialise; new fields are appended */
+    int B, K, G, K_out; float nms_iou;
+    const int64_t* start; const int64_t* end;             /* (B, K), window-local */
+    const float* score; const float* key;                 /* (B, K) */
+    const int32_t* count;                                 /* (B,) */
+    const int32_t* group_index;                           /* (B,), device */
+    const int32_t* offset;                                /* (B,), device, or NULL = 0 */
+    int32_t* out_list;                                    /* (G, K_out) */
+    int64_t* out_start; int64_t* out_end;                 /* (G, K_out), global */
+    float* out_score; float* out_key;                     /* (G, K_out) */
+    int32_t* out_count;                                   /* (G,) */
+} vsl_merge_windows_io;
+int vsl_merge_windows(vsl_handle h, const vsl_merge_windows_io* io, void* hip_stream);
+
 /* Optimizer step on the flat buckets: clip_grad_norm_(grads, clip_norm) (main_t7.py:111) followed by AdamW with decoupled
  * weight decay (build_optimizer_and_scheduler, VSLNet_t7.py:8-17: no decay for names containing "bias", "layer_norm" or
  * "LayerNorm" -- the library derives that mask from its own parameter names).  Two kernels (one with norm_from_backward), no host synchronisation: the

@@ -31,6 +31,11 @@ What differs from the reference, by design:
     video of the split (runner.eval_corpus: videos and queries encoded once, VSLNet.retrieve ranks the moments of all videos on the device) and
     corpus Rank@K at IoU 0.5 / 0.7 -- a returned moment in the ground-truth video at that IoU -- and video Recall@K are reported.  Off by default:
     nothing printed or written changes.  `--mode train` only stores the flag in configs.json, where --mode test finds it as its default;
+  * `--window T --window_stride S` (`--mode test`, `--data resident`): after the usual numbers, every record of the test split is also evaluated by
+    sliding windows of T clips at stride S over the clip sequence the split holds (runner.eval_windows: VSLNet.encode_windows + localize_long, the
+    windows' moments merged on the device into the video's own clips) and Rank@1 / mean IoU of the first merged moment -- with `--topk K` also Rank@K
+    over the K merged moments -- are reported.  0 (default): off, nothing printed or written changes.  `--mode train` only stores the flags in
+    configs.json, where --mode test finds them as its defaults;
   * `--task synthetic` builds a small learnable dataset in the reference's record format (no dataset files needed).
 """
 import argparse
@@ -101,6 +106,9 @@ def build_parser():
     p.add_argument('--max_span', type=int, default=0, help='--topk: longest candidate moment in clips (0: unlimited)')
     p.add_argument('--corpus', action='store_true', help='--mode test with --data resident and --topk K >= 1: also run every query against EVERY video of '
                    'the test split (runner.eval_corpus) and report corpus Rank@K at IoU 0.5 / 0.7 and video Recall@K')
+    p.add_argument('--window', type=int, default=0, help='--mode test with --data resident: also evaluate every record by sliding windows of this many clips '
+                   '(runner.eval_windows; at most --max_pos_len; 0: off)')
+    p.add_argument('--window_stride', type=int, default=0, help='--window: clips between two window starts (1 .. --window; 0: half the window)')
     p.add_argument('--synthetic_train', type=int, default=512)
     p.add_argument('--synthetic_test', type=int, default=128)
     return p
@@ -151,6 +159,21 @@ def check_corpus(configs):
     if topk_of(configs) is None:
         raise ValueError('--corpus needs --topk K >= 1: the moments returned per query')
     return True
+
+
+def window_of(configs):
+    """--window / --window_stride in --mode test -> (window, stride), or None (off; a configs.json from before the flags has none; --mode train only stores them)"""
+    window = int(getattr(configs, 'window', 0) or 0)
+    if window == 0 or configs.mode.lower() != 'test':
+        return None
+    stride = int(getattr(configs, 'window_stride', 0) or 0) or max(1, window // 2)
+    if configs.data != 'resident':
+        raise ValueError('--window needs --data resident (the windows run over the split held in device memory)')
+    if not 1 <= window <= int(configs.max_pos_len):
+        raise ValueError('--window %d: between 1 and --max_pos_len %d (the model has a positional row per clip of a window)' % (window, configs.max_pos_len))
+    if not 1 <= stride <= window:
+        raise ValueError('--window_stride %d: between 1 and --window %d (a larger stride would skip clips)' % (stride, window))
+    return window, stride
 
 
 def topk_of(configs):
@@ -372,6 +395,7 @@ def test(configs, parser, argv, dataset, features, device, log=print):
     model.eval()
     topk = topk_of(configs)
     check_corpus(configs)
+    windows = window_of(configs)
     if configs.data == 'resident':
         loader = data.ResidentSplit(dataset['test_set'], features, configs, device, train=False)
     else:
@@ -394,6 +418,15 @@ def test(configs, parser, argv, dataset, features, device, log=print):
         rows += [('Corpus Rank@%d, IoU=0.5' % k, stats['corpus_r_k_i5']), ('Corpus Rank@%d, IoU=0.7' % k, stats['corpus_r_k_i7']),
                  ('video Recall@%d' % k, stats['video_recall_k'])]
         corpus = {key: v for key, v in stats.items() if key != 'k'}
+    if windows is not None:
+        stats, _ = runner.eval_windows(model, loader, device, windows[0], windows[1], topk=topk)
+        tag = 'Windows %d/%d ' % windows
+        rows += [(tag + 'Rank@1, IoU=0.3', stats['win_r1i3']), (tag + 'Rank@1, IoU=0.5', stats['win_r1i5']), (tag + 'Rank@1, IoU=0.7', stats['win_r1i7']),
+                 (tag + 'mean IoU', stats['win_mIoU'])]
+        if topk is not None:
+            rows += [(tag + 'Rank@%d, IoU=0.3' % topk.k, stats['win_r_k_i3']), (tag + 'Rank@%d, IoU=0.5' % topk.k, stats['win_r_k_i5']),
+                     (tag + 'Rank@%d, IoU=0.7' % topk.k, stats['win_r_k_i7']), (tag + 'best-of-%d mean IoU' % topk.k, stats['win_mIoU_k'])]
+        corpus = dict(corpus, **stats)
     for name, v in rows:
         log('\x1b[1;31m{}:\t{:.2f}\x1b[0m'.format(name, v))
     return dict({'r1i3': r1i3, 'r1i5': r1i5, 'r1i7': r1i7, 'mIoU': mi}, **(rank_k[0] if rank_k else {}), **corpus)
@@ -406,6 +439,7 @@ def run(argv=None, log=print):
     check_accum(configs, world)                     # (before the dataset is built: a refused combination costs nothing)
     topk_of(configs)
     check_corpus(configs)
+    window_of(configs)
     runner.set_th_config(configs.seed)
     dataset, features = data.load_dataset(configs)
     configs.char_size, configs.word_size = dataset['n_chars'], dataset['n_words']      # main_t7.py:52-53

@@ -1,5 +1,5 @@
 // C ABI of libvslnet_hip.so (declared in include/vslnet_hip.h).  Every entry point checks its arguments and states its own refusals; the ones
-// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, vsl_encode_query, vsl_localize_pairs, the backward's three entry points, vsl_input_grads) then go
+// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, vsl_encode_query, vsl_localize_pairs, vsl_encode_windows, the backward's three entry points, vsl_input_grads) then go
 // through ONE path, enqueue(): plan of the shape, the call's context, the CallScope, the sequence of forward.hip / backward.hip, the launch-error
 // check and, for a forward, record_forward(): what it left for the calls behind it.  (layout.hip, plan.hip do the rest; the vsl_profile_* entry
 // points live with the profiler in streams.hip.)  Host code only -- no device code lives here.
@@ -36,11 +36,11 @@ static void record_forward(vsl_handle_s* h, vsl_handle_s::LastFwd kind, const fl
 }
 
 // One enqueuing call: the plan of the io's shape, the call's context, the call's bookkeeping, `seq` (which enqueues), the launch-error check, and
-// -- `fwd` other than FwdNone: the call is a forward of that kind -- the record of it.
+// -- `fwd` other than FwdNone: the call is a forward of that kind -- the record of it.  `rows`: the feature rows in the key of an EncodeWindows plan.
 template <class Seq>
-static int enqueue(vsl_handle_s* h, const vsl_io* io, PlanKind kind, const vsl_shared_io* sh, void* hip_stream, vsl_handle_s::LastFwd fwd, Seq&& seq) {
+static int enqueue(vsl_handle_s* h, const vsl_io* io, PlanKind kind, const vsl_shared_io* sh, void* hip_stream, vsl_handle_s::LastFwd fwd, Seq&& seq, int rows = 0) {
     Plan* p = nullptr;
-    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, kind, sh ? sh->N : 0)) return rc;
+    if (int rc = get_plan(h, io->B, io->T, io->Lq, io->Lc, &p, kind, sh ? sh->N : rows)) return rc;
     Ctx c{h, p, io, (hipStream_t)hip_stream, false, io->workspace};
     c.main = c.s;
     c.sh = sh;
@@ -333,6 +333,28 @@ int vsl_localize(vsl_handle h, const vsl_localize_io* l, void* hip_stream) {
     });
 }
 
+// ---- windows over a long video: each clip projected once, each window encoded (evaluation only, like vsl_encode_video)
+int vsl_encode_windows_workspace_floats(vsl_handle h, int N, int T, int rows, int64_t* out) { return workspace_floats(h, PlanKind::EncodeWindows, N, T, 0, 0, out, rows); }
+
+int vsl_encode_windows(vsl_handle h, const vsl_encode_windows_io* e, void* hip_stream) {
+    if (!h || !e) return fail("null handle / io");
+    if (!e->params || (!e->video_features && !e->video_features_bf16) || !e->video_encoding || !e->v_mask || !e->workspace)
+        return fail("vsl_encode_windows_io has a null device pointer");
+    if (!e->window_row) return fail("vsl_encode_windows: window_row is NULL (the first feature row of each window)");
+    if (!e->window_len) return fail("vsl_encode_windows: window_len is NULL (the valid clips of each window)");
+    if (e->video_features_bf16 && (h->cfg.video_feature_dim % 8 != 0))
+        return fail("bf16 features need video_feature_dim %% 8 == 0 (got %d)", h->cfg.video_feature_dim);
+    vsl_io io;
+    memset(&io, 0, sizeof io);
+    io.B = e->N; io.T = e->T;
+    io.params = e->params; io.video_features = e->video_features; io.video_features_bf16 = e->video_features_bf16; io.v_mask = e->v_mask;
+    io.workspace = e->workspace; io.inference = 1;
+    // (the shape's refusals, by name: build_windows_plan.  FwdInfer: nothing saved -- vsl_backward in this workspace and vsl_workspace_offset are
+    // refused as after an inference forward)
+    return enqueue(h, &io, PlanKind::EncodeWindows, nullptr, hip_stream, vsl_handle_s::FwdInfer,
+                   [&](Ctx& c) { forward_encode_windows(c, e->window_row, e->window_len, e->v_mask, e->video_encoding); }, e->rows);
+}
+
 // ---- one encoding per query, to be asked about many videos (evaluation only, like vsl_encode_video)
 int vsl_encode_query_workspace_floats(vsl_handle h, int Q, int Lq, int Lc, int64_t* out) { return workspace_floats(h, PlanKind::EncodeQuery, Q, 0, Lq, Lc, out); }
 
@@ -479,6 +501,25 @@ int vsl_merge_topk(vsl_handle h, const vsl_merge_io* io, void* hip_stream) {
     launch_merge_topk(MergeArgs{io->start, io->end, io->score, io->key, io->count, io->group_index, io->tag, io->B, io->K, io->G, io->K_out,
                                 io->tag_per_slot != 0, rescan_all, io->out_tag, io->out_list, io->out_start, io->out_end, io->out_score, io->out_key,
                                 io->out_count}, (hipStream_t)hip_stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int vsl_merge_windows(vsl_handle h, const vsl_merge_windows_io* io, void* hip_stream) {
+    if (!h || !io) return fail("vsl_merge_windows: null argument");
+    if (io->B < 1) return fail("vsl_merge_windows: B=%d must be at least 1", io->B);
+    if (io->G < 1) return fail("vsl_merge_windows: G=%d must be at least 1", io->G);
+    if (io->K < 1 || io->K > TOPK_MAX_K) return fail("vsl_merge_windows: K=%d must be in [1, %d]", io->K, TOPK_MAX_K);
+    if (io->K_out < 1 || io->K_out > TOPK_MAX_K) return fail("vsl_merge_windows: K_out=%d must be in [1, %d]", io->K_out, TOPK_MAX_K);
+    if (!(io->nms_iou >= 0.f && io->nms_iou <= 1.f)) return fail("vsl_merge_windows: nms_iou=%g must be in [0, 1]", (double)io->nms_iou);
+    if (!io->start || !io->end || !io->score || !io->key || !io->count) return fail("vsl_merge_windows: start, end, score, key and count are required inputs");
+    if (!io->group_index) return fail("vsl_merge_windows: null group_index");
+    if (!io->out_list || !io->out_start || !io->out_end || !io->out_score || !io->out_key || !io->out_count)
+        return fail("vsl_merge_windows: out_list, out_start, out_end, out_score, out_key and out_count are required outputs");
+    static const bool rescan_all = getenv("VSL_MERGE_RESCAN_ALL") != nullptr;      // (measuring switch: the kernel without its cached heads)
+    launch_merge_windows(MergeWindowsArgs{io->start, io->end, io->score, io->key, io->count, io->group_index, io->offset, io->B, io->K, io->G, io->K_out,
+                                          io->nms_iou, rescan_all, io->out_list, io->out_start, io->out_end, io->out_score, io->out_key, io->out_count},
+                         (hipStream_t)hip_stream);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -324,6 +324,24 @@ void forward_encode(Ctx& c, float* video_encoding) {
     video_branch(c, video_encoding);
 }
 
+// vsl_encode_windows: the pack of forward_encode, VisualProjection ONCE over the call's feature rows into the plan's (rows, 128) buffer, the gather of
+// every window's rows (and of the projection of a zero row behind its length) into the slot the encoder reads, the (N, T) mask into the caller's
+// buffer, then encoder application 0 over the windows into the caller's encoding.  One stream, as forward_encode.
+void forward_encode_windows(Ctx& c, const int32_t* window_row, const int32_t* window_len, float* v_mask, float* video_encoding) {
+    const vsl_handle_s* h = c.h;
+    const vsl_config& cf = h->cfg; const ModelP& P = h->P; const ModelPk& K = h->K;
+    const Plan& p = *c.p; const vsl_io& io = *c.io;
+    LAUNCH("pack", launch_pack(io.params, c.W(p.pack), h->jobs_dev + h->jobs_char, h->jobs_first, c.s));
+    if (io.video_features_bf16)
+        LAUNCH("vproj_fwd", launch_vproj_fwd_bf16(io.video_features_bf16, reinterpret_cast<const uint16_t*>(c.PK(K.va_f16)), c.P(P.va_b), c.W(p.wproj), p.rows,
+                                                  cf.video_feature_dim, c.drop(SITE_VIS), c.s));
+    else
+        LAUNCH("vproj_fwd", launch_vproj_fwd3(io.video_features, reinterpret_cast<const uint16_t*>(c.PK(K.va_f3)), c.P(P.va_b), c.W(p.wproj), p.rows, cf.video_feature_dim,
+                                              c.drop(SITE_VIS), c.s));
+    LAUNCH("window_gather", launch_window_gather(WindowGatherArgs{c.W(p.wproj), c.P(P.va_b), window_row, window_len, c.W(p.vf), v_mask, p.B, p.T, p.rows}, c.s));
+    enc_fwd(c, P.fe, K.fe, p.ve, c.W(p.vf), v_mask, p.B, 0, nullptr, video_encoding);
+}
+
 // vsl_encode_query: the query half alone into the caller's buffer -- the char-conv image and the shared encoder's operands (the head of the first
 // class: VisualProjection's, its last jobs_va jobs, stay unpacked), the Embedding linear's operand, then the query branch.  One stream: there is
 // nothing to run beside it.

@@ -68,7 +68,8 @@ enum class PlanKind {
     Localize,   // vsl_localize: the inference plan without the video pass
     LocalizePairs, // vsl_localize_pairs: the Localize plan without the query branch (no E, qf, qe, no embedding scratch)
     EncodeQuery,// vsl_encode_query: B = queries, T = 0: the packs and the query branch's own scratch (build_query_plan)
-    TrainShared // vsl_forward_shared / vsl_backward_shared: the training plan with the video half sized by N videos, everything else by B queries
+    TrainShared,// vsl_forward_shared / vsl_backward_shared: the training plan with the video half sized by N videos, everything else by B queries
+    EncodeWindows // vsl_encode_windows: the Encode plan of (B = windows, T) + the (rows, 128) projection of the feature rows; rows sits in the key's N slot (build_windows_plan)
 };
 
 struct Plan {
@@ -77,6 +78,8 @@ struct Plan {
     int NV() const { return N > 0 ? N : B; }       // samples of the video half
     PlanKind kind = PlanKind::Train;
     int64_t vmask = -1;                 // Localize: the (N, T) clip mask gathered to (B, T)
+    int rows = 0;                       // EncodeWindows: feature rows VisualProjection runs over
+    int64_t wproj = -1;                 // EncodeWindows: its (rows, 128) output, which k_window_gather reads
     int64_t pack = -1, vf = -1, E = -1, argpos = -1, qf = -1;
     EncWs ve, qe, p1, p2;
     LstmWs lstm[2];
@@ -124,7 +127,7 @@ struct vsl_handle_s {
     const float* sq_src = nullptr;       // the last vsl_backward's per-block sums of squares (Plan::sq_dev), their count, the bucket they describe
     int sq_n = 0;
     const float* sq_grads = nullptr;
-    std::map<std::tuple<int, int, int, int, int, vsl::PlanKind>, vsl::Plan*> plans;      // key: B, T, Lq, Lc, N (TrainShared; 0 otherwise), kind
+    std::map<std::tuple<int, int, int, int, int, vsl::PlanKind>, vsl::Plan*> plans;      // key: B, T, Lq, Lc, N (TrainShared; EncodeWindows: rows; 0 otherwise), kind
     // what the last forward left (api.hip record_forward):
     const void* infer_ws = nullptr;      // workspace the last INFERENCE forward ran in (it holds no saves: vsl_backward on it is refused) ; a training forward in it clears this
     enum LastFwd { FwdNone, FwdFull, FwdInfer, FwdShared };
@@ -301,7 +304,7 @@ void build_packs(vsl_handle_s* h);
 void finish_pack_jobs(vsl_handle_s* h);
 int ensure_opt_state(vsl_handle_s* h);
 // plan.hip
-int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind kind = PlanKind::Train, int N = 0);     // N: TrainShared only
+int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind kind = PlanKind::Train, int N = 0);     // N: TrainShared (videos) and EncodeWindows (feature rows) only
 void free_plan(Plan* p);
 // streams.hip
 bool prof_selected(const vsl_handle_s* h, const char* name);
@@ -312,6 +315,7 @@ bool query_chain_is_longer(const Plan& p);      // after the backward's video / 
 struct CqContext { const float* C; const int* vidx; const float* Qf = nullptr; const float* qmask = nullptr; const int* qidx = nullptr; };
 void forward_full(Ctx& c);                      // vsl_forward, or (c.sh set, plan TrainShared) vsl_forward_shared
 void forward_encode(Ctx& c, float* video_encoding);
+void forward_encode_windows(Ctx& c, const int32_t* window_row, const int32_t* window_len, float* v_mask, float* video_encoding);
 void forward_localize(Ctx& c, CqContext ctx, const float* vmask_nt);
 void forward_encode_query(Ctx& c, float* query_encoding);
 void forward_pairs(Ctx& c, CqContext ctx, const float* vmask_nt);

@@ -384,6 +384,34 @@ struct MergeArgs {
     int32_t* out_count;                   // (G)
 };
 void launch_merge_topk(const MergeArgs& a, hipStream_t s);
+// the K_out best moments of every group of WINDOW lists in the video's own coordinates, with NMS across the lists (kernels_merge_windows.hip; the
+// semantics: include/vslnet_hip.h, vsl_merge_windows)
+struct MergeWindowsArgs {
+    const int64_t *start, *end;           // (B, K) candidate lists, window-local
+    const float *score, *key;             // (B, K); the order is by key
+    const int32_t* count;                 // (B): filled slots of list b
+    const int32_t* group_index;           // (B): group of list b; outside [0, G): none
+    const int32_t* offset;                // (B), nullable = 0: clip index of the list's window start
+    int B, K, G, K_out;                   // 1 <= K, K_out <= 32
+    float nms_iou;                        // in [0, 1]; identical global spans are suppressed at every value
+    int rescan_all;                       // measuring switch: no cached per-thread head
+    int32_t* out_list;                    // (G, K_out)
+    int64_t *out_start, *out_end;         // global
+    float *out_score, *out_key;
+    int32_t* out_count;                   // (G)
+};
+void launch_merge_windows(const MergeWindowsArgs& a, hipStream_t s);
+// windows over projected feature rows (kernels_window.hip; vsl_encode_windows): out (N, T, 128) = proj rows window_row[n] + t for t < window_len[n]
+// inside [0, rows), the projection of a zero feature row (0 + bias) elsewhere ; mask (N, T) = t < window_len[n]
+struct WindowGatherArgs {
+    const float* proj;                    // (rows, 128) VisualProjection's output over the feature rows
+    const float* bias;                    // (128) VisualProjection's bias
+    const int32_t *window_row, *window_len;   // (N), device
+    float* out;                           // (N, T, 128)
+    float* mask;                          // (N, T)
+    int N, T, rows;
+};
+void launch_window_gather(const WindowGatherArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- backward
 // fuse != nullptr: the end head's workgroups continue with that attention-output backward on their own tile of dfeat (which is then NOT stored)

@@ -141,6 +141,35 @@ int build_encode_plan(vsl_handle_s* h, int N, int T, Plan** out) {
     return 0;
 }
 
+// vsl_encode_windows: the encode plan of (N windows, T) -- so the encoder application runs in the slots vsl_encode_video gives it -- plus the
+// (rows, 128) projection of the feature rows behind it.  B = windows; rows sits in the key's N slot, Plan::N stays 0 (NV() = the windows).
+int build_windows_plan(vsl_handle_s* h, int N, int T, int rows, Plan** out) {
+    if (N < 1) return fail("vsl_encode_windows: N=%d windows (at least one)", N);
+    if (T < 1 || T > std::min(MAX_L, h->cfg.max_pos_len))
+        return fail("vsl_encode_windows: T=%d clips per window must be in [1, %d] (min of %d and max_pos_len=%d)", T, std::min(MAX_L, h->cfg.max_pos_len), MAX_L, h->cfg.max_pos_len);
+    if (rows < 1) return fail("vsl_encode_windows: rows=%d feature rows (at least one)", rows);
+    if ((int64_t)rows * h->cfg.video_feature_dim >= (int64_t(1) << 31))
+        return fail("vsl_encode_windows: rows * video_feature_dim = %lld must stay below 2^31 (hand the call fewer feature rows)", (long long)rows * h->cfg.video_feature_dim);
+    if ((int64_t)rows * D >= (int64_t(1) << 31)) return fail("vsl_encode_windows: rows * 128 = %lld must stay below 2^31 (hand the call fewer feature rows)", (long long)rows * D);
+    if ((int64_t)N * T * D >= (int64_t(1) << 31)) return fail("vsl_encode_windows: N * T * 128 = %lld must stay below 2^31 (encode the windows in chunks)", (long long)N * T * D);
+    if (int rc = check_video_shape(h, N, T, " (encode the windows in chunks)")) return rc;
+    Plan* p = new Plan();
+    p->kind = PlanKind::EncodeWindows;
+    p->B = N; p->T = T; p->Lq = 0; p->Lc = 0; p->rows = rows;
+    const int64_t R = (int64_t)N * T, RD = ((R * D) + 3) & ~int64_t(3);
+    p->ve.R = (int)R; p->ve.L = T;
+    Bump al;
+    p->pack = al(h->pack_floats);
+    place_encoder(p->ve, al(5 * RD), RD);
+    p->vf = p->ve.att;
+    p->wproj = al((int64_t)rows * D);
+    p->partial = al(0);
+    p->total = al.cur;
+    if (p->total >= (int64_t(1) << 31)) { delete p; return fail("vsl_encode_windows: workspace of %lld floats exceeds the 2^31 offset range", (long long)p->total); }
+    *out = p;
+    return 0;
+}
+
 // vsl_encode_query: the operand packs and the query branch's own scratch of the inference plan -- the embedding concat E, the Embedding linear's
 // output and ONE encoder application's y3, q, k, v, att on B Lq rows.  The output goes to the caller's buffer.  B = queries; the plan has no video
 // side (T = 0 in its key).
@@ -334,7 +363,8 @@ void free_plan(Plan* p) {
 // beyond that.  (A forward and its backward use the same shape back to back, so a live plan is never evicted.)
 constexpr size_t MAX_PLANS = 2048;
 int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind kind, int N) {
-    if (kind != PlanKind::TrainShared) N = 0;
+    if (kind == PlanKind::EncodeWindows) { }      // (N = the feature rows: part of the key, checked by the builder)
+    else if (kind != PlanKind::TrainShared) N = 0;
     else if (N < 1) return fail("shared training step: N=%d videos (at least one)", N);
     auto key = std::make_tuple(B, T, Lq, Lc, N, kind);
     auto it = h->plans.find(key);
@@ -349,6 +379,7 @@ int get_plan(vsl_handle_s* h, int B, int T, int Lq, int Lc, Plan** out, PlanKind
         case PlanKind::LocalizePairs: rc = build_infer_plan(h, B, T, Lq, Lc, &p, kind); break;
         case PlanKind::Encode: rc = build_encode_plan(h, B, T, &p); break;
         case PlanKind::EncodeQuery: rc = build_query_plan(h, B, Lq, Lc, &p); break;
+        case PlanKind::EncodeWindows: rc = build_windows_plan(h, B, T, N, &p); break;
     }
     if (rc) return rc;
     if (h->plans.size() >= MAX_PLANS) {

@@ -131,6 +131,40 @@ class vsl_merge_io(C.Structure):
 CorpusMoments = namedtuple('CorpusMoments', 'tag list start end score prob count')
 
 
+class vsl_encode_windows_io(C.Structure):
+    _fields_ = [('rows', C.c_int32), ('N', C.c_int32), ('T', C.c_int32), ('params', C.c_void_p), ('video_features', C.c_void_p),
+                ('video_features_bf16', C.c_void_p), ('window_row', C.c_void_p), ('window_len', C.c_void_p), ('video_encoding', C.c_void_p),
+                ('v_mask', C.c_void_p), ('workspace', C.c_void_p)]
+
+
+class vsl_merge_windows_io(C.Structure):
+    _fields_ = [('B', C.c_int), ('K', C.c_int), ('G', C.c_int), ('K_out', C.c_int), ('nms_iou', C.c_float),
+                ('start', C.c_void_p), ('end', C.c_void_p), ('score', C.c_void_p), ('key', C.c_void_p), ('count', C.c_void_p),
+                ('group_index', C.c_void_p), ('offset', C.c_void_p),
+                ('out_list', C.c_void_p), ('out_start', C.c_void_p), ('out_end', C.c_void_p), ('out_score', C.c_void_p), ('out_key', C.c_void_p),
+                ('out_count', C.c_void_p)]
+
+
+class WindowEncoding(VideoEncoding):
+    """What VSLNet.encode_windows returns: a VideoEncoding over ALL sliding windows of a list of videos (row n = window n; `localize` and
+    `localize_pairs` take it as it is, owner / epoch / staleness as for any VideoEncoding), and where the windows lie: `video_of_window`,
+    `offset_of_window` (the window's first clip in its video) and `window_len` as (N,) int32 device tensors, `lengths` (clips per video) and
+    `first_window` (V + 1 prefix sums: video v owns windows first_window[v] .. first_window[v + 1] - 1) as numpy arrays, `window` and `stride`."""
+    __slots__ = ('video_of_window', 'offset_of_window', 'window_len', 'lengths', 'first_window', 'window', 'stride')
+
+    def __init__(self, encoding, v_mask, video_of_window, offset_of_window, window_len, lengths, first_window, window, stride, owner=None, epoch=None):
+        super().__init__(encoding, v_mask, owner=owner, epoch=epoch)
+        self.video_of_window, self.offset_of_window, self.window_len = video_of_window, offset_of_window, window_len
+        self.lengths, self.first_window, self.window, self.stride = lengths, first_window, int(window), int(stride)
+
+
+# what Engine.merge_windows returns, per group: (G, k_out) int32 list (the input list a slot came from), int64 start / end in the video's own clips,
+# fp32 score and prob (the ranking key), (G,) int32 count; slots from count[g] on hold -1, -1, -1, -inf, 0
+WindowMoments = namedtuple('WindowMoments', 'list start end score prob count')
+# what VSLNet.localize_long returns, per (video, query) pair: the same with `window` (the row of the WindowEncoding a moment came from) in place of `list`
+LongMoments = namedtuple('LongMoments', 'window start end score prob count')
+
+
 class VslError(RuntimeError):
     pass
 
@@ -142,7 +176,8 @@ ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count',
                'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize',
                'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset',
                'vsl_backward_accumulate', 'vsl_extract_topk', 'vsl_input_grads', 'vsl_merge_topk',
-               'vsl_encode_query_workspace_floats', 'vsl_encode_query', 'vsl_pairs_workspace_floats', 'vsl_localize_pairs']
+               'vsl_encode_query_workspace_floats', 'vsl_encode_query', 'vsl_pairs_workspace_floats', 'vsl_localize_pairs',
+               'vsl_encode_windows_workspace_floats', 'vsl_encode_windows', 'vsl_merge_windows']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -210,6 +245,11 @@ def load_library():
         lib.vsl_localize_pairs.argtypes = [C.c_void_p, C.POINTER(vsl_pairs_io), C.c_void_p]
     if hasattr(lib, 'vsl_merge_topk'):                       # (likewise: the merge of top-K lists per group)
         lib.vsl_merge_topk.argtypes = [C.c_void_p, C.POINTER(vsl_merge_io), C.c_void_p]
+    if hasattr(lib, 'vsl_encode_windows'):                   # (likewise: sliding windows over a long video)
+        lib.vsl_encode_windows_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        lib.vsl_encode_windows.argtypes = [C.c_void_p, C.POINTER(vsl_encode_windows_io), C.c_void_p]
+    if hasattr(lib, 'vsl_merge_windows'):                    # (likewise: the cross-window merge)
+        lib.vsl_merge_windows.argtypes = [C.c_void_p, C.POINTER(vsl_merge_windows_io), C.c_void_p]
     if hasattr(lib, 'vsl_input_grads'):                      # (likewise: the gradient with respect to the video features)
         lib.vsl_input_grads.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p, C.c_void_p]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -305,6 +345,9 @@ class Engine:
         # ... and vsl_localize_pairs, which reads it: both or neither
         self.has_query_encoding = all(hasattr(self.lib, s) for s in ('vsl_encode_query', 'vsl_encode_query_workspace_floats', 'vsl_localize_pairs',
                                                                      'vsl_pairs_workspace_floats'))
+        # vsl_encode_windows / vsl_merge_windows: sliding windows over a video of any length.  An older build has neither; encode_windows and
+        # merge_windows then raise
+        self.has_windows = all(hasattr(self.lib, s) for s in ('vsl_encode_windows', 'vsl_encode_windows_workspace_floats', 'vsl_merge_windows'))
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -581,6 +624,86 @@ class Engine:
         self._call(self.lib.vsl_encode_video(self.h, C.byref(io), stream))
         self._no_saves((flat, vfeats, v_mask, enc, ws))
         return VideoEncoding(enc, v_mask)
+
+    # ---- sliding windows over a video of any length (evaluation only) ---------------------------------------
+    def _need_windows(self):
+        if not self.has_windows:
+            raise VslError('the loaded library has no sliding windows (vsl_encode_windows / vsl_merge_windows are missing)')
+
+    def encode_windows_workspace_floats(self, N, T, rows):
+        """Floats an encode_windows call of N windows of T clips over `rows` feature rows needs (the encode plan of (N, T) + rows * 128)."""
+        self._need_windows()
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            self._call(self.lib.vsl_encode_windows_workspace_floats(self.h, int(N), int(T), int(rows), C.byref(n)))
+        return int(n.value)
+
+    def encode_windows(self, flat, feats, window_row, window_len, T, out=None, out_mask=None):
+        """VisualProjection ONCE over the (rows, video_feature_dim) feature rows `feats`, then the video pass of the shared feature encoder over N
+        windows of T clips: window n is rows window_row[n] .. window_row[n] + window_len[n] - 1, zero feature rows behind its length
+        (include/vslnet_hip.h, vsl_encode_windows).  -> VideoEncoding (encoding (N, T, 128), v_mask (N, T) = t < window_len[n]): the bits of
+        encode_video on the materialised zero-padded windows, which are never built.  `window_row` / `window_len`: (N,) int32 DEVICE tensors; a row
+        outside the features is treated as padding.  `feats` in torch.bfloat16 selects the bf16 throughput mode.  `out` / `out_mask`: contiguous
+        fp32 cuda tensors of those shapes to write into (slices of a larger encoding)."""
+        self._need_windows()
+        if feats.dim() != 2:
+            raise ValueError('encode_windows: the features must be (rows, video_feature_dim), got %s' % (tuple(feats.shape),))
+        rows, N, T = int(feats.shape[0]), int(window_row.numel()), int(T)
+        bf16 = feats.dtype == torch.bfloat16
+        _chk(flat, torch.float32, (self.param_floats,), 'params')
+        _chk(feats, torch.bfloat16 if bf16 else torch.float32, (rows, self.cfg.video_feature_dim), 'video_features')
+        _chk(window_row, torch.int32, (N,), 'window_row')
+        _chk(window_len, torch.int32, (N,), 'window_len')
+        self._flush_loss()
+        ws = self._grow_ws(self.encode_windows_workspace_floats(N, T, rows))
+        enc = torch.empty(N, T, 128, dtype=torch.float32, device=self.device) if out is None else out
+        mask = torch.empty(N, T, dtype=torch.float32, device=self.device) if out_mask is None else out_mask
+        _chk(enc, torch.float32, (N, T, 128), 'out')
+        _chk(mask, torch.float32, (N, T), 'out_mask')
+        io = vsl_encode_windows_io()
+        io.rows, io.N, io.T = rows, N, T
+        io.params = _ptr(flat)
+        io.video_features, io.video_features_bf16 = (None, _ptr(feats)) if bf16 else (_ptr(feats), None)
+        io.window_row, io.window_len = _ptr(window_row), _ptr(window_len)
+        io.video_encoding, io.v_mask, io.workspace = _ptr(enc), _ptr(mask), _ptr(ws)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_encode_windows(self.h, C.byref(io), stream))
+        self._no_saves((flat, feats, window_row, window_len, enc, mask, ws))
+        return VideoEncoding(enc, mask)
+
+    def merge_windows(self, spans, group_index, G, k_out, offset=None, nms_iou=0.5):
+        """The k_out best moments of every group of WINDOW lists, in the video's own clips, with temporal NMS across the lists (include/vslnet_hip.h,
+        vsl_merge_windows; the written specification: vslnet_amd.spans.merge_windows_reference) -> WindowMoments.  `spans`: a TopkSpans of B lists at
+        window-local indices (extract_topk(want_prob=True); the ranking key is its `prob`); `group_index` (B,) int32 on the device: the (query, video)
+        pair of list b, a value outside [0, G) drops the list; `offset` (B,) int32 on the device: the first clip of list b's window (None: 0).  Two
+        candidates at the same global span are reported once at every nms_iou."""
+        self._need_windows()
+        if spans.prob is None:
+            raise ValueError('merge_windows: the spans carry no prob to rank by (extract_topk(want_prob=True))')
+        B, K = spans.start.shape
+        G, k_out = int(G), int(k_out)
+        for name, v in (('G', G), ('k_out', k_out)):         # (ctypes would wrap them; the library checks the ranges)
+            if not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError('merge_windows: %s=%d is not a C int' % (name, v))
+        _chk(spans.start, torch.int64, (B, K), 'spans.start')
+        _chk(spans.end, torch.int64, (B, K), 'spans.end')
+        _chk(spans.score, torch.float32, (B, K), 'spans.score')
+        _chk(spans.prob, torch.float32, (B, K), 'spans.prob')
+        _chk(spans.count, torch.int32, (B,), 'spans.count')
+        _chk(group_index, torch.int32, (B,), 'group_index')
+        if offset is not None:
+            _chk(offset, torch.int32, (B,), 'offset')
+        n = max(G, 0), max(k_out, 0)
+        lst = torch.empty(n, dtype=torch.int32, device=self.device)
+        i64 = torch.empty((2,) + n, dtype=torch.int64, device=self.device)
+        f32 = torch.empty((2,) + n, dtype=torch.float32, device=self.device)
+        count = torch.empty(n[0], dtype=torch.int32, device=self.device)
+        io = vsl_merge_windows_io(B, K, G, k_out, float(nms_iou), spans.start.data_ptr(), spans.end.data_ptr(), spans.score.data_ptr(),
+                                  spans.prob.data_ptr(), spans.count.data_ptr(), group_index.data_ptr(), offset.data_ptr() if offset is not None else None,
+                                  lst.data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(), f32[0].data_ptr(), f32[1].data_ptr(), count.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_merge_windows(self.h, C.byref(io), stream))
+        return WindowMoments(lst, i64[0], i64[1], f32[0], f32[1], count)
 
     def _need_query_encoding(self):
         if not self.has_query_encoding:

@@ -347,6 +347,110 @@ class VSLNet(nn.Module):
         cat = lambda name: torch.cat([getattr(m, name) for m in first]).contiguous()      # noqa: E731
         return self.merge_topk(TopkSpans(cat('start'), cat('end'), cat('score'), cat('prob'), cat('count')), queries.repeat(len(first)), Q, k, tag=cat('tag'))
 
+    # ---- videos of any length: sliding windows, one ranked list of moments per (video, query) in the video's own clips (no reference counterpart) ----
+    def encode_windows(self, videos, window, stride, windows_per_call=256):
+        """The sliding windows of one or several videos of ANY length through VisualProjection and the shared feature encoder -> WindowEncoding, a
+        VideoEncoding over all windows (T = `window`) for `localize_long` (and `localize` / `localize_pairs`).  `videos`: one (L, video_feature_dim)
+        tensor or a list of them, fp32 or bfloat16 (the bf16 throughput mode), each of its own length.  Window w of a video starts at clip w * stride;
+        a video has one window when L <= window, else ceil((L - window) / stride) + 1, the last one possibly short (spans.window_table).  Each clip
+        is projected once however many windows hold it and the (windows, window, video_feature_dim) block is never built.  The library runs in
+        chunks of at most `windows_per_call` windows, each handed only the feature rows its windows span (one video: a view; several: their
+        concatenation), so the row limits apply per chunk; the result does not depend on the chunking where the encoder's output does not depend on
+        a sample's position in its batch (window % 32 == 0 or window <= 32: exactly; elsewhere within a few 1e-6)."""
+        import numpy as np
+        from ..engine import WindowEncoding
+        from ..spans import window_table
+        self._shared_video_mode('encode_windows')
+        videos = [videos] if torch.is_tensor(videos) else list(videos)
+        window, stride, per = int(window), int(stride), int(windows_per_call)
+        if not videos:
+            raise ValueError('encode_windows: no video')
+        if stride < 1:
+            raise ValueError('encode_windows: stride=%d must be at least 1' % stride)
+        if stride > window:
+            raise ValueError('encode_windows: stride=%d > window=%d: clips between two windows would be skipped' % (stride, window))
+        if window > self.configs.max_pos_len:
+            raise ValueError('encode_windows: window=%d > max_pos_len=%d: the model has no positional row for such a window' % (window, self.configs.max_pos_len))
+        if per < 1:
+            raise ValueError('encode_windows: windows_per_call=%d must be at least 1' % per)
+        bf16 = videos[0].dtype == torch.bfloat16
+        for v in videos:
+            if v.dim() != 2 or v.shape[0] < 1 or (v.dtype == torch.bfloat16) != bf16:
+                raise ValueError('encode_windows: every video must be a (L >= 1, video_feature_dim) tensor and all of one precision, got %s %s' % (tuple(v.shape), v.dtype))
+        eng = self._engine_for(videos[0].device)
+        if not eng.has_windows:
+            raise VslError('the loaded library has no sliding windows (vsl_encode_windows / vsl_merge_windows are missing)')
+        videos = [v.contiguous() if bf16 else v.contiguous().float() for v in videos]
+        lengths = np.array([int(v.shape[0]) for v in videos], dtype=np.int64)
+        tabs = [window_table(L, window, stride) for L in lengths]
+        first = np.concatenate([[0], np.cumsum([len(t[0]) for t in tabs])]).astype(np.int64)
+        video_of = np.concatenate([np.full(len(t[0]), i, dtype=np.int64) for i, t in enumerate(tabs)])
+        offset, wlen = np.concatenate([t[0] for t in tabs]), np.concatenate([t[1] for t in tabs])
+        N, dev = int(first[-1]), eng.device
+        enc = torch.empty(N, window, 128, dtype=torch.float32, device=dev)
+        mask = torch.empty(N, window, dtype=torch.float32, device=dev)
+        wrow = np.zeros(N, dtype=np.int64)
+        calls = []
+        for a in range(0, N, per):                          # the feature rows of a chunk: for each of its videos, the clips its windows span
+            b, parts, base = min(N, a + per), [], 0
+            for v in range(int(video_of[a]), int(video_of[b - 1]) + 1):
+                w = np.arange(max(a, first[v]), min(b, first[v + 1]))
+                lo, hi = int(offset[w[0]]), int(offset[w[-1]] + wlen[w[-1]])
+                wrow[w] = base + offset[w] - lo
+                parts.append(videos[v][lo:hi])
+                base += hi - lo
+            calls.append((a, b, parts))
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev)      # noqa: E731
+        d_row, d_len = up(wrow), up(wlen)
+        for a, b, parts in calls:
+            eng.encode_windows(self._flat, parts[0] if len(parts) == 1 else torch.cat(parts), d_row[a:b], d_len[a:b], window, out=enc[a:b], out_mask=mask[a:b])
+        return WindowEncoding(enc, mask, up(video_of), up(offset), d_len, lengths, first, window, stride, owner=self, epoch=self._param_epoch)
+
+    def localize_long(self, wenc, qenc, k, nms_iou=0.5, max_span=0, pairs=None, pairs_per_call=4096):
+        """The k best moments of (video, query) pairs over videos of any length, in each video's OWN clip indices -> LongMoments(window, start, end,
+        score, prob, count) shaped (P, k).  `wenc`: the WindowEncoding of encode_windows, `qenc`: a QueryEncoding.  By default every query of `qenc`
+        runs against every video of `wenc` (pair p = video * Q + query); `pairs`: (P, 2) integers as (video, query).  Every window of a pair's video
+        is localised against the query (localize_pairs in chunks of at most `pairs_per_call` (window, query) lists), extract_topk(k, nms_iou,
+        max_span) with the window's own length leaves k moments per window at window-local indices, and ONE merge_windows -- a group per pair, ranked
+        by `prob` -- shifts them to the video's clips and suppresses across the windows with the same nms_iou: a moment two overlapping windows
+        report is written once.  `window` is the row of `wenc` a moment came from.  Nothing goes through the host."""
+        import numpy as np
+        from ..engine import LongMoments, TopkSpans, WindowEncoding
+        self._shared_video_mode('localize_long')
+        if not isinstance(wenc, WindowEncoding):
+            raise TypeError('localize_long: wenc must be the WindowEncoding that encode_windows returned')
+        self._check_handle(wenc, 'localize_long', 'WindowEncoding')
+        self._check_handle(qenc, 'localize_long', 'QueryEncoding')
+        V, Q, dev, k = len(wenc.lengths), qenc.Q, wenc.encoding.device, int(k)
+        if pairs is None:
+            pv, pq = np.repeat(np.arange(V, dtype=np.int64), Q), np.tile(np.arange(Q, dtype=np.int64), V)
+        else:
+            pairs = np.asarray(pairs.cpu() if torch.is_tensor(pairs) else pairs, dtype=np.int64).reshape(-1, 2)
+            pv, pq = pairs[:, 0], pairs[:, 1]
+            if len(pv) == 0 or pv.min() < 0 or pv.max() >= V or pq.min() < 0 or pq.max() >= Q:
+                raise ValueError('localize_long: pairs must be (P >= 1, 2) rows of (video in [0, %d), query in [0, %d))' % (V, Q))
+        if int(pairs_per_call) < 1:
+            raise ValueError('localize_long: pairs_per_call=%d must be at least 1' % int(pairs_per_call))
+        nwin = (wenc.first_window[1:] - wenc.first_window[:-1])[pv]               # lists of each pair: one per window of its video
+        group = np.repeat(np.arange(len(pv), dtype=np.int64), nwin)
+        widx = np.concatenate([np.arange(wenc.first_window[v], wenc.first_window[v + 1]) for v in pv])
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev)      # noqa: E731
+        d_w, d_q, d_g = up(widx), up(pq[group]), up(group)
+        B = len(widx)
+        idx = torch.empty(2, B, max(k, 0), dtype=torch.int64, device=dev)
+        val = torch.empty(2, B, max(k, 0), dtype=torch.float32, device=dev)
+        count = torch.empty(B, dtype=torch.int32, device=dev)
+        d_len = wenc.window_len[d_w.long()]
+        for a in range(0, B, int(pairs_per_call)):
+            b = min(B, a + int(pairs_per_call))
+            _, sl, el = self.localize_pairs(wenc, qenc, d_w[a:b], d_q[a:b])
+            s = self.extract_topk(sl, el, k, nms_iou=nms_iou, max_span=max_span, lengths=d_len[a:b], want_prob=True)
+            idx[0, a:b], idx[1, a:b], val[0, a:b], val[1, a:b], count[a:b] = s.start, s.end, s.score, s.prob, s.count
+        m = self._engine.merge_windows(TopkSpans(idx[0], idx[1], val[0], val[1], count), d_g, len(pv), k, offset=wenc.offset_of_window[d_w.long()].contiguous(),
+                                       nms_iou=nms_iou)
+        window = torch.where(m.list >= 0, d_w[m.list.clamp(min=0).long()], m.list)
+        return LongMoments(window, m.start, m.end, m.score, m.prob, m.count)
+
     def extract_index(self, start_logits, end_logits):
         self._engine_for(start_logits.device)
         return self._engine.extract_index(start_logits.detach().contiguous(), end_logits.detach().contiguous())

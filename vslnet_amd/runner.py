@@ -270,6 +270,55 @@ def eval_test_shared(model, split, device, mode='test', epoch=None, global_step=
     return _finish(ious, best, topk, epoch, global_step)
 
 
+def summarise_windows(ious, best, window, stride, topk):
+    """The metric block of eval_windows -> (stats dict, text): Rank@1 at IoU 0.3 / 0.5 / 0.7 and mean IoU of the first merged moment, and with `topk`
+    Rank@K over the K merged moments."""
+    r3, r5, r7 = (calculate_iou_accuracy(ious, t) for t in (0.3, 0.5, 0.7))
+    mi = float(np.mean(ious) * 100.0)
+    stats = {'window': int(window), 'window_stride': int(stride), 'win_r1i3': r3, 'win_r1i5': r5, 'win_r1i7': r7, 'win_mIoU': mi}
+    text = 'Windows {}/{}: Rank@1, IoU=0.3: {:.2f}\tIoU=0.5: {:.2f}\tIoU=0.7: {:.2f}\tmean IoU: {:.2f}\n'.format(window, stride, r3, r5, r7, mi)
+    if topk is not None:
+        sk, line = summarise_topk(best, topk.k)
+        stats.update({'win_' + key: v for key, v in sk.items() if key != 'k'})
+        text += 'Windows {}/{}: '.format(window, stride) + line
+    return stats, text
+
+
+def eval_windows(model, split, device, window, stride, topk=None, windows_per_call=256, pairs_per_call=4096):
+    """Evaluation by sliding windows (no reference counterpart): every video of a `data.ResidentSplit` is encoded as overlapping windows of `window`
+    clips at `stride` over the clip sequence the split holds (VSLNet.encode_windows, once), each batch of records encodes its queries
+    (VSLNet.encode_query) and VSLNet.localize_long returns each record's merged moments in its video's own clips; one device-to-host copy per batch
+    brings (start, end, count) back.  Rank@1 / mean IoU are those of the FIRST merged moment, Rank@K (with `topk`, whose nms_iou / max_span also
+    act inside and across the windows) of the best of the K; times through index_to_time with the video's full clip count.
+    -> (stats dict, text) of summarise_windows."""
+    del device
+    k = 1 if topk is None else topk.k
+    nms_iou, max_span = (0.5, 0) if topk is None else (topk.nms_iou, topk.max_span)
+    ious, best = [], []
+    bs, n = split.batch_size, len(split.records)
+    with torch.no_grad():
+        vlen = np.zeros(int(split.feats.shape[0]), dtype=np.int64)
+        vlen[split.vid_of] = split.lens
+        wenc = model.encode_windows([split.feats[v, :int(vlen[v])] for v in range(len(vlen))], window, stride, windows_per_call=windows_per_call)
+        d_order = torch.arange(n, device=split.device)
+        for a in range(0, n, bs):
+            idx = np.arange(a, min(n, a + bs))
+            idx_dev = d_order[a:a + bs]
+            Lq, Lc = int(split.nwords[idx].max()), int(split.nchars[idx].max())
+            word_ids = torch.index_select(split.d_words[:, :Lq], 0, idx_dev)
+            char_ids = torch.index_select(split.d_chars[:, :Lq, :Lc], 0, idx_dev)
+            qenc = model.encode_query(word_ids, char_ids, (word_ids != 0).float())
+            m = model.localize_long(wenc, qenc, k, nms_iou=nms_iou, max_span=max_span, pairs=np.stack([split.vid_of[idx], np.arange(len(idx))], axis=1),
+                                    pairs_per_call=pairs_per_call)
+            out = torch.cat([m.start, m.end, m.count[:, None].long()], dim=1).cpu().numpy()
+            for q, i in enumerate(idx):
+                r = split.records[i]
+                b = best_iou_of_spans(out[q, :k], out[q, k:2 * k], out[q, 2 * k], r)
+                ious.append(best_iou_of_spans(out[q, :1], out[q, k:k + 1], min(int(out[q, 2 * k]), 1), r))
+                best.append(b)
+    return summarise_windows(ious, best, window, stride, topk)
+
+
 def corpus_hits(tag, start, end, count, record, video):
     """One query's corpus result against its record: the best IoU over the returned moments that lie in the ground-truth video `video` (0 when none
     does) and whether any does.  A moment in another video is a miss whatever its span."""

@@ -1,6 +1,6 @@
-"""Top-K moments per query: the written specifications of `vsl_extract_topk` and `vsl_merge_topk` (include/vslnet_hip.h) as brute-force numpy, and the
-conversion of spans to seconds.  `topk_spans_reference` and `merge_topk_reference` are what the tests compare the kernels with; the library never
-calls them."""
+"""Top-K moments per query: the written specifications of `vsl_extract_topk`, `vsl_merge_topk` and `vsl_merge_windows` (include/vslnet_hip.h) as
+brute-force numpy, the table of sliding windows over a video, and the conversion of spans to seconds.  `topk_spans_reference`, `merge_topk_reference`
+and `merge_windows_reference` are what the tests compare the kernels with; the library never calls them."""
 from collections import namedtuple
 
 import numpy as np
@@ -84,6 +84,56 @@ def merge_topk_reference(start, end, score, key, count, group_index, G, k_out, t
             out_score[g, r], out_key[g, r] = score[b, k], key[b, k]
             out_count[g] = r + 1
     return out_tag, out_list, out_start, out_end, out_score, out_key, out_count
+
+
+def window_table(L, window, stride):
+    """The sliding windows over a video of L clips -> (start, length) int64 arrays: window w starts at clip w * stride; there is one window when
+    L <= window, else ceil((L - window) / stride) + 1; the last one may be short: length = min(window, L - w * stride).  Every clip is covered when
+    stride <= window."""
+    L, window, stride = int(L), int(window), int(stride)
+    if L < 1 or window < 1 or stride < 1:
+        raise ValueError('window_table: L=%d, window=%d, stride=%d must all be at least 1' % (L, window, stride))
+    if stride > window:
+        raise ValueError('window_table: stride=%d > window=%d would skip clips' % (stride, window))
+    W = 1 if L <= window else -(-(L - window) // stride) + 1
+    start = np.arange(W, dtype=np.int64) * stride
+    return start, np.minimum(window, L - start)
+
+
+def merge_windows_reference(start, end, score, key, count, group_index, G, k_out, nms_iou, offset=None):
+    """B lists of K slots at window-local indices -> per group g: list (G, k_out) int32, start, end (G, k_out) int64 in GLOBAL clips, score, key
+    (G, k_out) float32, count (G,) int32.  Candidates of group g: slot k < min(count[b], K) of every list b with group_index[b] == g (outside [0, G): no
+    group), at the global span (start + offset[b], end + offset[b]) (offset None: 0).  They are sorted by key descending, then global start, global
+    end, list and slot ascending -- a strict total order; k_out rounds each take the first candidate in that order that no earlier choice of the group
+    suppresses: a chosen span suppresses a candidate iff the two global spans are identical (at every nms_iou) or `suppressed` holds on them.  Slots
+    from count[g] on hold -1, -1, -1, -inf, 0."""
+    start, end = np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+    score, key = np.asarray(score, dtype=np.float32), np.asarray(key, dtype=np.float32)
+    B, K = start.shape
+    offset = np.zeros(B, dtype=np.int64) if offset is None else np.asarray(offset, dtype=np.int64)
+    out_list = np.full((G, k_out), -1, dtype=np.int32)
+    out_start, out_end = np.full((G, k_out), -1, dtype=np.int64), np.full((G, k_out), -1, dtype=np.int64)
+    out_score, out_key = np.full((G, k_out), -np.inf, dtype=np.float32), np.zeros((G, k_out), dtype=np.float32)
+    out_count = np.zeros(G, dtype=np.int32)
+    cands = [[] for _ in range(G)]
+    for b in range(B):
+        g = int(group_index[b])
+        if not 0 <= g < G:
+            continue
+        for k in range(min(int(count[b]), K)):
+            cands[g].append((-float(key[b, k]), int(start[b, k] + offset[b]), int(end[b, k] + offset[b]), b, k))
+    for g in range(G):
+        chosen = []
+        for _, s, e, b, k in sorted(cands[g]):
+            if len(chosen) == k_out:
+                break
+            if any((s, e) == (cs, ce) or suppressed(s, e, cs, ce, nms_iou) for cs, ce in chosen):
+                continue
+            r = len(chosen)
+            chosen.append((s, e))
+            out_list[g, r], out_start[g, r], out_end[g, r], out_score[g, r], out_key[g, r] = b, s, e, score[b, k], key[b, k]
+            out_count[g] = r + 1
+    return out_list, out_start, out_end, out_score, out_key, out_count
 
 
 def spans_to_times(start, end, count, v_len, duration):
