@@ -253,6 +253,52 @@ typedef struct {                       /* zero-initialise; new fields are append
 int vsl_pairs_workspace_floats(vsl_handle h, int B, int T, int Lq, int64_t* out);
 int vsl_localize_pairs(vsl_handle h, const vsl_pairs_io* io, void* hip_stream);
 
+/* COARSE-TO-FINE CORPUS SEARCH, THE COARSE HALF: which videos are relevant to a query (evaluation only; no reference counterpart).
+ *
+ * vsl_highlight_pairs: vsl_localize_pairs that stops behind the highlight layer.  It enqueues what vsl_localize_pairs enqueues up to and including the
+ * launch that writes h_score -- the operand pack, the mask gather, the CQAttention / CQConcatenate / highlight kernels, the same kernels in the same
+ * order -- and neither the predictor nor the span heads.  `pairs` is read as vsl_localize_pairs reads it, except:
+ *   - pairs.start_logits / pairs.end_logits are ignored (may be NULL);
+ *   - pairs.h_score may be NULL: the (B, T) scores then stay in the workspace.  When given it receives, bit for bit, what vsl_localize_pairs writes
+ *     for the same pairs;
+ *   - pairs.workspace: vsl_pairs_workspace_floats() floats, the plan of vsl_localize_pairs (its predictor slots are simply not used).
+ * Behind it, on the same stream, ONE launch (ledger label "pair_relevance") reduces every pair's h_score row to one float over the pair's VALID clips
+ * (the gathered per-pair mask the CQ kernels read):
+ *   - relevance = 0: the maximum -- exact;
+ *   - relevance = 1: the mean, sum / count in fp32.  The order of the additions is a function of T alone (one wave per pair: lane l adds clips l,
+ *     l + 64, ... ascending, a butterfly joins the lanes): the same bits on every run and at every position b of the pair in the call;
+ *   - a pair without a valid clip: -INFINITY.
+ * Output addressing: ld > 0: out[query_index[b] * ld + video_index[b]] -- a (Q, ld) relevance matrix filled chunk by chunk, no strided copy; two pairs
+ * of one call with the same (query, video) write the same value.  ld == 0: out[b].
+ * Refused by name: every refusal of vsl_localize_pairs but the two logits pointers; relevance other than 0 or 1; a NULL out; 0 < ld < N.
+ * The call marks its workspace like an inference forward.  Detect the feature by the presence of the symbols: VSL_ABI_VERSION does not change for
+ * an added entry point. */
+typedef struct vsl_highlight_io {          /* zero-initialise; new fields are appended */
+    vsl_pairs_io pairs;
+    int32_t relevance;                     /* 0 = max, 1 = mean                                                                                */
+    int32_t ld;                            /* 0: out is (B) ; >= N: out is a (Q, ld) matrix                                                    */
+    float* out;
+} vsl_highlight_io;
+int vsl_highlight_pairs(vsl_handle h, const vsl_highlight_io* io, void* hip_stream);
+
+/* vsl_select_topm: the best M of N per group on the device.  `key` is (G, N) fp32 with row stride ld >= N (the relevance matrix above: group = query,
+ * index = video).  Per group g:
+ *   - order: key descending, ties by the SMALLER index; -0.0 counts as +0.0 (keys are compared as key + 0.0f).  A strict total order: the result is a
+ *     pure function of the input, the same bits on every run; no atomic on global memory, none on a float;
+ *   - out_count[g] = min(M, N); out_index[g][r], out_key[g][r] (the key as compared: key + 0.0f) for r < count are the first `count` indices IN THAT
+ *     ORDER, ranked; slots from count on hold -1 and 0.
+ * M >= N sorts the whole row (N <= 1024).  A NaN key gives an unspecified choice (every loop is bounded by N and M).
+ * Limits, each refused by name: 1 <= M <= 1024; G, N >= 1; ld >= N; G * ld < 2^31; NULL pointers.  A free-standing call like vsl_merge_topk: no plan, no
+ * workspace; one workgroup per group, ONE launch on the caller's stream.  Detect the feature by the presence of the symbol. */
+typedef struct vsl_select_io {             /* zero-initialise; new fields are appended */
+    int32_t G, N, ld, M;
+    const float* key;                      /* (G, N), row stride ld                                                                            */
+    int32_t* out_index;                    /* (G, M)                                                                                           */
+    float* out_key;                        /* (G, M)                                                                                           */
+    int32_t* out_count;                    /* (G)                                                                                              */
+} vsl_select_io;
+int vsl_select_topm(vsl_handle h, const vsl_select_io* io, void* hip_stream);
+
 /* TRAINING THROUGH A SHARED VIDEO ENCODING: one step over N videos and B queries, query b paired with video video_index[b] (no reference counterpart:
  * it runs the video half once per sample).  VisualProjection and encoder application 0 run forward AND backward on N T rows; the query branch,
  * CQAttention, CQConcatenate, the highlight layer, the predictor, the span heads and the losses run on B samples as in vsl_forward / vsl_backward.

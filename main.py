@@ -31,6 +31,10 @@ What differs from the reference, by design:
     video of the split (runner.eval_corpus: videos and queries encoded once, VSLNet.retrieve ranks the moments of all videos on the device) and
     corpus Rank@K at IoU 0.5 / 0.7 -- a returned moment in the ground-truth video at that IoU -- and video Recall@K are reported.  Off by default:
     nothing printed or written changes.  `--mode train` only stores the flag in configs.json, where --mode test finds it as its default;
+  * `--corpus_prefilter M` (with `--corpus_relevance max|mean`; only with `--corpus`): the corpus search runs coarse to fine -- every query's videos are
+    ranked by the highlight score first (VSLNet.rank_videos) and the query is localised in its M best videos only -- and prefilter video recall@M, the
+    share of queries whose ground-truth video is among the M selected, is reported in front of the corpus numbers.  0 (default): every video,
+    nothing printed changes.  Stored in configs.json like the other flags;
   * `--window T --window_stride S` (`--mode test`, `--data resident`): after the usual numbers, every record of the test split is also evaluated by
     sliding windows of T clips at stride S over the clip sequence the split holds (runner.eval_windows: VSLNet.encode_windows + localize_long, the
     windows' moments merged on the device into the video's own clips) and Rank@1 / mean IoU of the first merged moment -- with `--topk K` also Rank@K
@@ -106,6 +110,10 @@ def build_parser():
     p.add_argument('--max_span', type=int, default=0, help='--topk: longest candidate moment in clips (0: unlimited)')
     p.add_argument('--corpus', action='store_true', help='--mode test with --data resident and --topk K >= 1: also run every query against EVERY video of '
                    'the test split (runner.eval_corpus) and report corpus Rank@K at IoU 0.5 / 0.7 and video Recall@K')
+    p.add_argument('--corpus_prefilter', type=int, default=0, help='--corpus: coarse to fine -- rank the videos of the split by highlight score first and '
+                   'localise each query only in its M best videos (VSLNet.retrieve prefilter=M); also reports prefilter video recall@M.  0: every video')
+    p.add_argument('--corpus_relevance', choices=('max', 'mean'), default='max', help='--corpus_prefilter: a video\'s relevance to a query is the max or '
+                   'the mean of the highlight score over its clips')
     p.add_argument('--window', type=int, default=0, help='--mode test with --data resident: also evaluate every record by sliding windows of this many clips '
                    '(runner.eval_windows; at most --max_pos_len; 0: off)')
     p.add_argument('--window_stride', type=int, default=0, help='--window: clips between two window starts (1 .. --window; 0: half the window)')
@@ -159,6 +167,20 @@ def check_corpus(configs):
     if topk_of(configs) is None:
         raise ValueError('--corpus needs --topk K >= 1: the moments returned per query')
     return True
+
+
+def prefilter_of(configs):
+    """--corpus_prefilter / --corpus_relevance -> (M, relevance); both belong to --corpus and are refused without it (a configs.json from before the
+    flags has none: the defaults)"""
+    m = int(getattr(configs, 'corpus_prefilter', 0) or 0)
+    relevance = getattr(configs, 'corpus_relevance', None) or 'max'
+    if m < 0:
+        raise ValueError('--corpus_prefilter %d: at least 0 (0: every video)' % m)
+    if relevance not in ('max', 'mean'):
+        raise ValueError('--corpus_relevance %r: max or mean' % (relevance,))
+    if (m or relevance != 'max') and not getattr(configs, 'corpus', False):
+        raise ValueError('--corpus_prefilter / --corpus_relevance need --corpus: they choose how the corpus search runs')
+    return m, relevance
 
 
 def window_of(configs):
@@ -395,6 +417,7 @@ def test(configs, parser, argv, dataset, features, device, log=print):
     model.eval()
     topk = topk_of(configs)
     check_corpus(configs)
+    prefilter, relevance = prefilter_of(configs)
     windows = window_of(configs)
     if configs.data == 'resident':
         loader = data.ResidentSplit(dataset['test_set'], features, configs, device, train=False)
@@ -413,8 +436,10 @@ def test(configs, parser, argv, dataset, features, device, log=print):
                  ('best-of-%d mean IoU' % k, rank_k[0]['mIoU_k'])]
     corpus = {}
     if getattr(configs, 'corpus', False):
-        stats, _ = runner.eval_corpus(model, loader, device, topk)
+        stats, _ = runner.eval_corpus(model, loader, device, topk, prefilter=prefilter, relevance=relevance)
         k = stats['k']
+        if prefilter:
+            rows += [('Prefilter (%s) video recall@%d' % (relevance, prefilter), stats['prefilter_recall_m'])]
         rows += [('Corpus Rank@%d, IoU=0.5' % k, stats['corpus_r_k_i5']), ('Corpus Rank@%d, IoU=0.7' % k, stats['corpus_r_k_i7']),
                  ('video Recall@%d' % k, stats['video_recall_k'])]
         corpus = {key: v for key, v in stats.items() if key != 'k'}
@@ -439,6 +464,7 @@ def run(argv=None, log=print):
     check_accum(configs, world)                     # (before the dataset is built: a refused combination costs nothing)
     topk_of(configs)
     check_corpus(configs)
+    prefilter_of(configs)
     window_of(configs)
     runner.set_th_config(configs.seed)
     dataset, features = data.load_dataset(configs)

@@ -1,5 +1,5 @@
 // C ABI of libvslnet_hip.so (declared in include/vslnet_hip.h).  Every entry point checks its arguments and states its own refusals; the ones
-// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, vsl_encode_query, vsl_localize_pairs, vsl_encode_windows, the backward's three entry points, vsl_input_grads) then go
+// that enqueue a launch sequence (vsl_forward, vsl_forward_shared, vsl_encode_video, vsl_localize, vsl_encode_query, vsl_localize_pairs, vsl_highlight_pairs, vsl_encode_windows, the backward's three entry points, vsl_input_grads) then go
 // through ONE path, enqueue(): plan of the shape, the call's context, the CallScope, the sequence of forward.hip / backward.hip, the launch-error
 // check and, for a forward, record_forward(): what it left for the calls behind it.  (layout.hip, plan.hip do the rest; the vsl_profile_* entry
 // points live with the profiler in streams.hip.)  Host code only -- no device code lives here.
@@ -402,6 +402,52 @@ int vsl_localize_pairs(vsl_handle h, const vsl_pairs_io* l, void* hip_stream) {
         io.v_mask = c.W(c.p->vmask);          // every kernel behind the join reads the gathered (B, T) mask
         forward_pairs(c, CqContext{l->video_encoding, l->video_index, l->query_encoding, l->q_mask, l->query_index}, l->v_mask);
     });
+}
+
+// ---- the coarse half of a corpus search: vsl_localize_pairs up to the highlight score, one relevance per pair
+int vsl_highlight_pairs(vsl_handle h, const vsl_highlight_io* r, void* hip_stream) {
+    if (!h || !r) return fail("null handle / io");
+    const vsl_pairs_io* l = &r->pairs;
+    if (l->B < 1) return fail("vsl_highlight_pairs: B=%d pairs (at least one)", l->B);
+    if (l->N < 1) return fail("vsl_highlight_pairs: N=%d videos in the encoding (at least one)", l->N);
+    if (l->Q < 1) return fail("vsl_highlight_pairs: Q=%d queries in the encoding (at least one)", l->Q);
+    if (l->Lq > MAX_LQ) return fail("vsl_highlight_pairs: Lq=%d > %d query words", l->Lq, MAX_LQ);
+    if (l->T > MAX_L) return fail("vsl_highlight_pairs: T=%d > %d clips", l->T, MAX_L);
+    if (!l->video_encoding) return fail("vsl_highlight_pairs: video_encoding is NULL (the output of vsl_encode_video for the same T and params)");
+    if (!l->query_encoding) return fail("vsl_highlight_pairs: query_encoding is NULL (the output of vsl_encode_query for the same Lq and params)");
+    if (!l->v_mask) return fail("vsl_highlight_pairs: v_mask is NULL (the (N, T) clip mask of the video encoding)");
+    if (!l->q_mask) return fail("vsl_highlight_pairs: q_mask is NULL (the (Q, Lq) word mask of the query encoding)");
+    if (!l->video_index) return fail("vsl_highlight_pairs: video_index is NULL (the video of each pair)");
+    if (!l->query_index) return fail("vsl_highlight_pairs: query_index is NULL (the query of each pair)");
+    if (!l->params || !l->workspace) return fail("vsl_highlight_io has a null device pointer");
+    if (r->relevance != 0 && r->relevance != 1) return fail("vsl_highlight_pairs: relevance=%d must be 0 (max) or 1 (mean)", r->relevance);
+    if (!r->out) return fail("vsl_highlight_pairs: out is NULL (the relevance of each pair)");
+    if (r->ld < 0 || (r->ld > 0 && r->ld < l->N))
+        return fail("vsl_highlight_pairs: ld=%d must be 0 (out is (B)) or at least N=%d (out is a (Q, ld) matrix)", r->ld, l->N);
+    vsl_io io;
+    memset(&io, 0, sizeof io);
+    io.B = l->B; io.T = l->T; io.Lq = l->Lq; io.Lc = PAIRS_PLAN_LC;
+    io.params = l->params;
+    io.workspace = l->workspace; io.inference = 1;
+    return enqueue(h, &io, PlanKind::LocalizePairs, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) {
+        io.v_mask = c.W(c.p->vmask);          // every kernel behind the join reads the gathered (B, T) mask
+        io.h_score = l->h_score ? l->h_score : c.W(c.p->p1.out);      // (no predictor runs: the first pass' output slot, (B T, 128), is free)
+        forward_highlight(c, CqContext{l->video_encoding, l->video_index, l->query_encoding, l->q_mask, l->query_index}, l->v_mask, r->out, r->ld, r->relevance);
+    });
+}
+
+int vsl_select_topm(vsl_handle h, const vsl_select_io* io, void* hip_stream) {
+    if (!h || !io) return fail("vsl_select_topm: null argument");
+    if (io->G < 1) return fail("vsl_select_topm: G=%d must be at least 1", io->G);
+    if (io->N < 1) return fail("vsl_select_topm: N=%d must be at least 1", io->N);
+    if (io->M < 1 || io->M > TOPM_MAX_M) return fail("vsl_select_topm: M=%d must be in [1, %d]", io->M, TOPM_MAX_M);
+    if (io->ld < io->N) return fail("vsl_select_topm: ld=%d must be at least N=%d", io->ld, io->N);
+    if ((int64_t)io->G * io->ld >= (int64_t(1) << 31)) return fail("vsl_select_topm: G * ld = %lld must stay below 2^31", (long long)io->G * io->ld);
+    if (!io->key) return fail("vsl_select_topm: key is NULL (the (G, N) keys)");
+    if (!io->out_index || !io->out_key || !io->out_count) return fail("vsl_select_topm: out_index, out_key and out_count are required outputs");
+    launch_select_topm(SelectArgs{io->key, io->G, io->N, io->ld, io->M, io->out_index, io->out_key, io->out_count}, (hipStream_t)hip_stream);
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_stream) {

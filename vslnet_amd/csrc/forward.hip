@@ -156,13 +156,11 @@ static void query_branch(Ctx& c, PackWait emb_pack, float* out = nullptr) {
     enc_fwd(c, P.fe, K.fe, p.qe, c.W(p.qf), io.q_mask, B, 1, nullptr, out);
 }
 
-// CQAttention over the context and the encoded query, CQConcatenate, the highlight score, the predictor and the span heads -- the dependent chain
-// behind the join of the two branches
-static void fuse_and_predict(Ctx& c, CqContext ctx) {
-    const vsl_config& cf = c.h->cfg; const ModelP& P = c.h->P; const ModelPk& K = c.h->K;
+// CQAttention, CQConcatenate and the highlight layer: h_score is final behind cq_out, which also leaves `gated` for the predictor
+static void cq_and_highlight(Ctx& c, CqContext ctx) {
+    const ModelP& P = c.h->P; const ModelPk& K = c.h->K;
     const Plan& p = *c.p; const vsl_io& io = *c.io;
-    const int B = p.B, T = p.T, Lq = p.Lq, R = B * T;
-    hipStream_t sq = c.side(0);
+    const int B = p.B, T = p.T, Lq = p.Lq;
     // short videos, short queries: the column kernel (column softmax over the clips, M = S_col^T C, WeightedPool) is folded into its neighbours --
     // one launch and one boundary less on the dependent chain (VSL_CQ_FOLD=0: three launches)
     static const bool fold_on = switch_on("VSL_CQ_FOLD", true);
@@ -181,6 +179,16 @@ static void fuse_and_predict(Ctx& c, CqContext ctx) {
     if (!cq_fold) LAUNCH("cq_col", launch_cq_col(cq, c.s));
     // cq_out also carries CQConcatenate + HighLightLayer + gating (row-local on the tile it produces)
     LAUNCH("cq_out", launch_cq_out(cq, c.s));
+}
+
+// CQAttention over the context and the encoded query, CQConcatenate, the highlight score, the predictor and the span heads -- the dependent chain
+// behind the join of the two branches
+static void fuse_and_predict(Ctx& c, CqContext ctx) {
+    const vsl_config& cf = c.h->cfg; const ModelP& P = c.h->P; const ModelPk& K = c.h->K;
+    const Plan& p = *c.p; const vsl_io& io = *c.io;
+    const int B = p.B, T = p.T, R = B * T;
+    hipStream_t sq = c.side(0);
+    cq_and_highlight(c, ctx);
     if (cf.predictor == 0) {
         // rnn head (:341-343): start = LSTM_s(x) * mask ; end = LSTM_e(start) * mask ; no LayerNorm in front of the span blocks
         // The recurrence is latency bound (one sample per CU, 0.6 us per step).  Up to RNN_FUSED_MAX_B samples the whole head is ONE launch: start
@@ -381,7 +389,8 @@ void forward_localize(Ctx& c, CqContext ctx, const float* vmask_nt) {
 
 // vsl_localize_pairs: no query branch at all -- both sides of CQAttention are resident encodings read through their indices.  Only the "rest" class of
 // packs is needed (no char image, no shared-encoder, Embedding or VisualProjection operands); the mask gather runs beside it on the third stream.
-void forward_pairs(Ctx& c, CqContext ctx, const float* vmask_nt) {
+// (pairs_pack_and_mask: everything of it in front of the CQ kernels; vsl_highlight_pairs starts the same way)
+static void pairs_pack_and_mask(Ctx& c, CqContext ctx, const float* vmask_nt) {
     const vsl_handle_s* h = c.h;
     const Plan& p = *c.p;
     const int nj = (int)h->jobs.size(), rest = h->jobs_char + h->jobs_first + h->jobs_query;
@@ -393,7 +402,19 @@ void forward_pairs(Ctx& c, CqContext ctx, const float* vmask_nt) {
     c.s = c.main;
     LAUNCH("pack", launch_pack(c.io->params, c.W(p.pack), h->jobs_dev + rest, nj - rest, c.s));
     if (split) c.order(sp, c.main);
+}
+
+void forward_pairs(Ctx& c, CqContext ctx, const float* vmask_nt) {
+    pairs_pack_and_mask(c, ctx, vmask_nt);
     fuse_and_predict(c, ctx);
+}
+
+// vsl_highlight_pairs: what forward_pairs enqueues up to cq_out -- the same kernels in the same order, so h_score holds the bits vsl_localize_pairs
+// gives -- then one launch that reduces every pair's row to its relevance.  No predictor, no span heads.
+void forward_highlight(Ctx& c, CqContext ctx, const float* vmask_nt, float* out, int ld, int mean) {
+    pairs_pack_and_mask(c, ctx, vmask_nt);
+    cq_and_highlight(c, ctx);
+    LAUNCH("pair_relevance", launch_pair_relevance(RelevanceArgs{c.io->h_score, c.io->v_mask, ctx.vidx, ctx.qidx, out, c.p->B, c.p->T, ld, mean}, c.s));
 }
 
 }  // namespace vsl

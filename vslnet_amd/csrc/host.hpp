@@ -319,6 +319,7 @@ void forward_encode_windows(Ctx& c, const int32_t* window_row, const int32_t* wi
 void forward_localize(Ctx& c, CqContext ctx, const float* vmask_nt);
 void forward_encode_query(Ctx& c, float* query_encoding);
 void forward_pairs(Ctx& c, CqContext ctx, const float* vmask_nt);
+void forward_highlight(Ctx& c, CqContext ctx, const float* vmask_nt, float* out, int ld, int mean);      // vsl_highlight_pairs: forward_pairs up to cq_out + the relevance reduction
 bool query_fused(const Ctx& c);
 std::vector<int> lstm_chunks(int T);
 extern std::atomic<unsigned long long> g_rnn_launches;

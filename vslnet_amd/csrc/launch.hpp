@@ -401,6 +401,26 @@ struct MergeWindowsArgs {
     int32_t* out_count;                   // (G)
 };
 void launch_merge_windows(const MergeWindowsArgs& a, hipStream_t s);
+// one relevance score per pair from its highlight scores (kernels_rank.hip; the semantics: include/vslnet_hip.h, vsl_highlight_pairs)
+struct RelevanceArgs {
+    const float* hscore;                  // (B, T) highlight scores
+    const float* vmask;                   // (B, T) the gathered per-pair clip mask the CQ kernels read
+    const int *vidx, *qidx;               // (B), device: video / query of pair b (read only when ld > 0)
+    float* out;                           // ld > 0: out[qidx[b] * ld + vidx[b]] ; ld == 0: out[b]
+    int B, T, ld;
+    int mean;                             // 0: max over the valid clips ; 1: their mean.  No valid clip: -inf
+};
+void launch_pair_relevance(const RelevanceArgs& a, hipStream_t s);
+// the best M of N per group (kernels_rank.hip; the semantics: include/vslnet_hip.h, vsl_select_topm)
+constexpr int TOPM_MAX_M = 1024;
+struct SelectArgs {
+    const float* key;                     // (G, N), row stride ld >= N
+    int G, N, ld, M;                      // 1 <= M <= TOPM_MAX_M
+    int32_t* out_index;                   // (G, M)
+    float* out_key;                       // (G, M)
+    int32_t* out_count;                   // (G) = min(M, N)
+};
+void launch_select_topm(const SelectArgs& a, hipStream_t s);
 // windows over projected feature rows (kernels_window.hip; vsl_encode_windows): out (N, T, 128) = proj rows window_row[n] + t for t < window_len[n]
 // inside [0, rows), the projection of a zero feature row (0 + bias) elsewhere ; mask (N, T) = t < window_len[n]
 struct WindowGatherArgs {

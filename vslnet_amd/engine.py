@@ -79,6 +79,22 @@ class vsl_pairs_io(C.Structure):
                 ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('workspace', C.c_void_p)]
 
 
+class vsl_highlight_io(C.Structure):
+    _fields_ = [('pairs', vsl_pairs_io), ('relevance', C.c_int32), ('ld', C.c_int32), ('out', C.c_void_p)]
+
+
+class vsl_select_io(C.Structure):
+    _fields_ = [('G', C.c_int32), ('N', C.c_int32), ('ld', C.c_int32), ('M', C.c_int32), ('key', C.c_void_p), ('out_index', C.c_void_p),
+                ('out_key', C.c_void_p), ('out_count', C.c_void_p)]
+
+
+# what Engine.select_topm / VSLNet.rank_videos return, per group (query): (G, m) int32 video (the index), fp32 relevance (the key), (G,) int32 count =
+# min(m, N); ranked: relevance descending, ties by the smaller index; slots from count[g] on hold -1, 0
+VideoRanks = namedtuple('VideoRanks', 'video relevance count')
+RELEVANCE = {'max': 0, 'mean': 1}                   # vsl_highlight_io.relevance
+TOPM_MAX_M = 1024                                   # vsl_select_topm: the largest M
+
+
 class QueryEncoding:
     """What Engine.encode_query returns: the shared feature encoder's output for Q queries padded to Lq words (embedded at Lc chars per word), and
     their word masks.  It belongs to its Lq and Lc and to the parameter values it was computed with (include/vslnet_hip.h).  `owner` / `epoch` are
@@ -177,7 +193,8 @@ ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count',
                'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset',
                'vsl_backward_accumulate', 'vsl_extract_topk', 'vsl_input_grads', 'vsl_merge_topk',
                'vsl_encode_query_workspace_floats', 'vsl_encode_query', 'vsl_pairs_workspace_floats', 'vsl_localize_pairs',
-               'vsl_encode_windows_workspace_floats', 'vsl_encode_windows', 'vsl_merge_windows']
+               'vsl_encode_windows_workspace_floats', 'vsl_encode_windows', 'vsl_merge_windows',
+               'vsl_highlight_pairs', 'vsl_select_topm']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -250,6 +267,10 @@ def load_library():
         lib.vsl_encode_windows.argtypes = [C.c_void_p, C.POINTER(vsl_encode_windows_io), C.c_void_p]
     if hasattr(lib, 'vsl_merge_windows'):                    # (likewise: the cross-window merge)
         lib.vsl_merge_windows.argtypes = [C.c_void_p, C.POINTER(vsl_merge_windows_io), C.c_void_p]
+    if hasattr(lib, 'vsl_highlight_pairs'):                  # (likewise: the coarse half of a corpus search)
+        lib.vsl_highlight_pairs.argtypes = [C.c_void_p, C.POINTER(vsl_highlight_io), C.c_void_p]
+    if hasattr(lib, 'vsl_select_topm'):
+        lib.vsl_select_topm.argtypes = [C.c_void_p, C.POINTER(vsl_select_io), C.c_void_p]
     if hasattr(lib, 'vsl_input_grads'):                      # (likewise: the gradient with respect to the video features)
         lib.vsl_input_grads.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p, C.c_void_p]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -348,6 +369,9 @@ class Engine:
         # vsl_encode_windows / vsl_merge_windows: sliding windows over a video of any length.  An older build has neither; encode_windows and
         # merge_windows then raise
         self.has_windows = all(hasattr(self.lib, s) for s in ('vsl_encode_windows', 'vsl_encode_windows_workspace_floats', 'vsl_merge_windows'))
+        # vsl_highlight_pairs / vsl_select_topm: rank the videos of a corpus by highlight score.  An older build has neither; highlight_pairs and
+        # select_topm then raise (and VSLNet.retrieve serves prefilter=0 only)
+        self.has_video_ranking = all(hasattr(self.lib, s) for s in ('vsl_highlight_pairs', 'vsl_select_topm'))
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -802,6 +826,86 @@ class Engine:
         self._call(self.lib.vsl_localize_pairs(self.h, C.byref(io), stream))
         self._no_saves((flat, venc, qenc, vidx, qidx, out, ws))
         return out[0], out[1], out[2]
+
+    def _need_video_ranking(self):
+        if not self.has_video_ranking:
+            raise VslError('the loaded library cannot rank videos (vsl_highlight_pairs / vsl_select_topm are missing)')
+
+    def highlight_pairs(self, flat, venc, qenc, video_index, query_index, relevance='max', out=None, ld=0, h_score=None):
+        """localize_pairs() that stops behind the highlight layer, plus one relevance per pair (include/vslnet_hip.h, vsl_highlight_pairs; the written
+        specification: vslnet_amd.spans.pair_relevance_reference): 'max' / 'mean' of the pair's h_score over its valid clips, -inf without one.
+        -> `out`.  ld == 0: out is (B,) (allocated when None).  ld >= venc.N: out is a caller-owned (Q, ld) fp32 matrix and pair b goes to
+        out[query_index[b], video_index[b]] -- a relevance matrix filled chunk by chunk.  `h_score`: an optional (B, T) buffer that receives the
+        scores, bit for bit those of localize_pairs.  Indices as in localize_pairs: host values are range-checked, device tensors trusted."""
+        self._need_video_ranking()
+        self._need_query_encoding()
+        if relevance not in RELEVANCE:
+            raise ValueError("highlight_pairs: relevance must be 'max' or 'mean', got %r" % (relevance,))
+        if not isinstance(venc, VideoEncoding):
+            raise TypeError('highlight_pairs: venc must be the VideoEncoding that encode_video returned')
+        if not isinstance(qenc, QueryEncoding):
+            raise TypeError('highlight_pairs: qenc must be the QueryEncoding that encode_query returned')
+        N, T, Q, Lq = venc.N, venc.T, qenc.Q, qenc.Lq
+        vidx = self._pair_index(video_index, N, 'video_index', 'videos')
+        qidx = self._pair_index(query_index, Q, 'query_index', 'queries')
+        B, ld = int(vidx.numel()), int(ld)
+        if B < 1:
+            raise ValueError('highlight_pairs: no pairs')
+        if not 0 <= ld < 2 ** 31:
+            raise ValueError('highlight_pairs: ld=%d is not a non-negative C int' % ld)
+        _chk(vidx, torch.int32, (B,), 'video_index')
+        _chk(qidx, torch.int32, (B,), 'query_index')
+        _chk(flat, torch.float32, (self.param_floats,), 'params')
+        _chk(venc.encoding, torch.float32, (N, T, 128), 'video encoding')
+        _chk(venc.v_mask, torch.float32, (N, T), 'v_mask')
+        _chk(qenc.encoding, torch.float32, (Q, Lq, 128), 'query encoding')
+        _chk(qenc.q_mask, torch.float32, (Q, Lq), 'q_mask')
+        if ld == 0:
+            if out is None:
+                out = torch.empty(B, dtype=torch.float32, device=self.device)
+            _chk(out, torch.float32, (B,), 'out')
+        else:
+            if out is None:
+                raise ValueError('highlight_pairs: ld > 0 writes into a (Q, ld) matrix: pass it as out')
+            _chk(out, torch.float32, (Q, ld), 'out')       # (ld < N: the library refuses it by name)
+        if h_score is not None:
+            _chk(h_score, torch.float32, (B, T), 'h_score')
+        self._flush_loss()
+        ws = self._grow_ws(self.pairs_workspace_floats(B, T, Lq))
+        io = vsl_highlight_io()
+        p = io.pairs
+        p.B, p.T, p.Lq, p.N, p.Q = B, T, Lq, N, Q
+        p.params = _ptr(flat)
+        p.video_encoding, p.v_mask, p.query_encoding, p.q_mask = _ptr(venc.encoding), _ptr(venc.v_mask), _ptr(qenc.encoding), _ptr(qenc.q_mask)
+        p.video_index, p.query_index = _ptr(vidx), _ptr(qidx)
+        p.h_score, p.workspace = _ptr(h_score), _ptr(ws)
+        io.relevance, io.ld, io.out = RELEVANCE[relevance], ld, _ptr(out)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_highlight_pairs(self.h, C.byref(io), stream))
+        self._no_saves((flat, venc, qenc, vidx, qidx, out, h_score, ws))
+        return out
+
+    def select_topm(self, key, M):
+        """The best M of N per row of `key` on the device (include/vslnet_hip.h, vsl_select_topm; the written specification:
+        vslnet_amd.spans.select_topm_reference) -> VideoRanks(video (G, M) int32, relevance (G, M) fp32, count (G,) int32 = min(M, N)): key descending,
+        ties by the smaller index, -0.0 as +0.0.  `key`: (G, N) fp32 on the device, rows contiguous, any row stride >= N (a column slice of a wider
+        matrix works).  1 <= M <= 1024."""
+        self._need_video_ranking()
+        M = int(M)
+        if not -2 ** 31 <= M < 2 ** 31:
+            raise ValueError('select_topm: M=%d is not a C int' % M)
+        if key.dim() != 2 or key.dtype != torch.float32 or not key.is_cuda or (key.shape[1] > 1 and key.stride(1) != 1):
+            raise ValueError('select_topm: key must be a (G, N) cuda float32 tensor with contiguous rows, got %s %s' % (key.dtype, tuple(key.shape)))
+        G, N = key.shape
+        ld = int(key.stride(0)) if G > 1 else max(N, 1)
+        n = max(M, 0)
+        index = torch.empty(G, n, dtype=torch.int32, device=self.device)
+        val = torch.empty(G, n, dtype=torch.float32, device=self.device)
+        count = torch.empty(G, dtype=torch.int32, device=self.device)
+        io = vsl_select_io(G, N, ld, M, key.data_ptr(), index.data_ptr(), val.data_ptr(), count.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_select_topm(self.h, C.byref(io), stream))
+        return VideoRanks(index, val, count)
 
     def localize(self, flat, pad_vec, glove_vec, enc, video_index, word_ids, char_ids, q_mask):
         """Everything of forward() behind the video pass, for B queries against the resident encoding `enc`: query b is localised in video

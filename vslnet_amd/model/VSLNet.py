@@ -318,34 +318,93 @@ class VSLNet(nn.Module):
         self._engine_for(spans.start.device)
         return self._engine.merge_topk(spans, group_index, G, k_out, tag=tag)
 
-    def retrieve(self, venc, qenc, k, nms_iou=0.5, max_span=0, lengths=None, pairs_per_call=4096):
+    def rank_videos(self, venc, qenc, m, relevance='max', pairs_per_call=4096):
+        """The m most relevant videos of `venc` for every query of `qenc` -> VideoRanks(video (Q, m) int32, relevance (Q, m) float32, count (Q,) int32 =
+        min(m, N)), ranked: relevance descending, ties by the smaller video number; slots from count on hold -1, 0.  The relevance of a (query, video)
+        pair is the 'max' or the 'mean' of its query-guided highlight score over the video's valid clips (-inf for a video without one): the
+        forward up to the highlight layer, no predictor.  Every query runs against every video in the chunks `retrieve` uses -- all queries x a block
+        of videos, at most `pairs_per_call` pairs -- through highlight_pairs straight into one (Q, N) matrix; one select_topm ranks it.  1 <= m <= 1024.
+        A WindowEncoding is taken as the VideoEncoding it is: its "videos" are its windows.  Nothing goes through the host."""
+        self._shared_video_mode('rank_videos')
+        self._check_handle(venc, 'rank_videos', 'VideoEncoding')
+        self._check_handle(qenc, 'rank_videos', 'QueryEncoding')
+        return self._rank_videos(venc, qenc, m, relevance, pairs_per_call, 'rank_videos')
+
+    def _rank_videos(self, venc, qenc, m, relevance, pairs_per_call, what):
+        Q, N, dev = qenc.Q, venc.N, venc.encoding.device
+        if pairs_per_call < Q:
+            raise ValueError('%s: pairs_per_call=%d is less than one video for each of the %d queries' % (what, pairs_per_call, Q))
+        eng = self._engine_for(dev)
+        per = max(1, pairs_per_call // Q)                    # videos per chunk
+        queries = torch.arange(Q, dtype=torch.int32, device=dev)
+        matrix = torch.empty(Q, N, dtype=torch.float32, device=dev)
+        for v0 in range(0, N, per):
+            nv = min(per, N - v0)
+            qidx = queries.repeat_interleave(nv)            # pair (q, v) at q * nv + (v - v0), as in retrieve
+            vidx = torch.arange(v0, v0 + nv, dtype=torch.int32, device=dev).repeat(Q)
+            self._step += 1                                 # (a graph built on an earlier forward is stale: its saves are overwritten)
+            eng.highlight_pairs(self._flat, venc, qenc, vidx, qidx, relevance=relevance, out=matrix, ld=N)
+        return eng.select_topm(matrix, m)
+
+    def retrieve(self, venc, qenc, k, nms_iou=0.5, max_span=0, lengths=None, pairs_per_call=4096, prefilter=0, relevance='max', return_ranks=False):
         """The k best moments of every query of `qenc` over ALL videos of `venc` -> CorpusMoments shaped (Q, k): `tag` = the video (its number in
         `venc`), start / end = the clips in that video, `prob` = the ranking key, descending; ties by video, then by the per-video rank.
         Every query runs against every video in chunks of at most `pairs_per_call` pairs -- all queries x a block of videos: localize_pairs,
         extract_topk(k, nms_iou, max_span, want_prob=True) per pair, merge_topk per query -- and one second merge_topk joins the chunks.  NMS acts
-        inside a video.  `lengths` (N,): valid clips per video (default: the row sums of venc.v_mask).  Nothing goes through the host."""
-        from ..engine import TopkSpans
+        inside a video.  `lengths` (N,): valid clips per video (default: the row sums of venc.v_mask).  Nothing goes through the host.
+        `prefilter` = M >= 1 (coarse to fine): rank_videos(m = min(M, 1024), relevance) first, then the steps above over the Q min(M, N) selected
+        (query, video) pairs only, in chunks of `pairs_per_call` pairs.  A moment in a video the first stage did not select cannot be returned: the
+        result is that of the exhaustive search restricted to the selected pairs -- the exhaustive result itself, field by field, when M >= N.  `list`
+        then numbers the rows as the exhaustive search with this `pairs_per_call` numbers them.  M > 1024 means "all videos" when N <= 1024 and is
+        refused otherwise.  prefilter = 0: no first stage, the exhaustive search.  `return_ranks` (with prefilter): -> (CorpusMoments, the first stage's
+        VideoRanks)."""
+        from ..engine import TopkSpans, TOPM_MAX_M
         self._shared_video_mode('retrieve')
         self._check_handle(venc, 'retrieve', 'VideoEncoding')
         self._check_handle(qenc, 'retrieve', 'QueryEncoding')
         Q, N, dev = qenc.Q, venc.N, venc.encoding.device
         if pairs_per_call < Q:
             raise ValueError('retrieve: pairs_per_call=%d is less than one video for each of the %d queries' % (pairs_per_call, Q))
+        prefilter = int(prefilter)
+        if prefilter < 0:
+            raise ValueError('retrieve: prefilter=%d must be 0 (exhaustive) or the number of videos to keep per query' % prefilter)
+        if prefilter > TOPM_MAX_M and N > TOPM_MAX_M:
+            raise ValueError('retrieve: prefilter=%d with N=%d videos: the first stage selects at most %d videos per query' % (prefilter, N, TOPM_MAX_M))
+        if prefilter and not self._engine_for(dev).has_video_ranking:
+            raise VslError('retrieve: prefilter needs a library that can rank videos (vsl_highlight_pairs / vsl_select_topm are missing)')
         lengths = (venc.v_mask.sum(dim=1) if lengths is None else torch.as_tensor(lengths, device=dev)).to(torch.int32)
         per = max(1, pairs_per_call // Q)                    # videos per chunk
         queries = torch.arange(Q, dtype=torch.int32, device=dev)
-        first = []
-        for v0 in range(0, N, per):
-            nv = min(per, N - v0)
-            qidx = queries.repeat_interleave(nv)            # pair (q, v) at q * nv + (v - v0)
-            vidx = torch.arange(v0, v0 + nv, dtype=torch.int32, device=dev).repeat(Q)
-            _, sl, el = self.localize_pairs(venc, qenc, vidx, qidx)
-            spans = self.extract_topk(sl, el, k, nms_iou=nms_iou, max_span=max_span, lengths=lengths[vidx.long()], want_prob=True)
-            first.append(self.merge_topk(spans, qidx, Q, k, tag=vidx))
+        first, ranks = [], None
+        if prefilter:
+            ranks = self._rank_videos(venc, qenc, min(prefilter, TOPM_MAX_M), relevance, pairs_per_call, 'retrieve')
+            m = min(prefilter, N)                           # every query has exactly m selected videos
+            vall = ranks.video[:, :m].reshape(-1)           # pair (q, rank r) at q * m + r
+            qall = queries.repeat_interleave(m)
+            for p0 in range(0, Q * m, pairs_per_call):
+                vidx, qidx = vall[p0:p0 + pairs_per_call].contiguous(), qall[p0:p0 + pairs_per_call].contiguous()
+                _, sl, el = self.localize_pairs(venc, qenc, vidx, qidx)
+                spans = self.extract_topk(sl, el, k, nms_iou=nms_iou, max_span=max_span, lengths=lengths[vidx.long()], want_prob=True)
+                first.append(self.merge_topk(spans, qidx, Q, k, tag=vidx))
+        else:
+            for v0 in range(0, N, per):
+                nv = min(per, N - v0)
+                qidx = queries.repeat_interleave(nv)            # pair (q, v) at q * nv + (v - v0)
+                vidx = torch.arange(v0, v0 + nv, dtype=torch.int32, device=dev).repeat(Q)
+                _, sl, el = self.localize_pairs(venc, qenc, vidx, qidx)
+                spans = self.extract_topk(sl, el, k, nms_iou=nms_iou, max_span=max_span, lengths=lengths[vidx.long()], want_prob=True)
+                first.append(self.merge_topk(spans, qidx, Q, k, tag=vidx))
         if len(first) == 1:
-            return first[0]
-        cat = lambda name: torch.cat([getattr(m, name) for m in first]).contiguous()      # noqa: E731
-        return self.merge_topk(TopkSpans(cat('start'), cat('end'), cat('score'), cat('prob'), cat('count')), queries.repeat(len(first)), Q, k, tag=cat('tag'))
+            out = first[0]
+        else:
+            cat = lambda name: torch.cat([getattr(m, name) for m in first]).contiguous()      # noqa: E731
+            out = self.merge_topk(TopkSpans(cat('start'), cat('end'), cat('score'), cat('prob'), cat('count')), queries.repeat(len(first)), Q, k, tag=cat('tag'))
+        if prefilter:
+            # `list` as the exhaustive search reports it: the pair's row q * N + video of its single call, or row chunk * Q + q of its second merge
+            q = queries.unsqueeze(1)
+            row = q * N + out.tag if N <= per else torch.div(out.tag, per, rounding_mode='floor') * Q + q
+            out = out._replace(list=torch.where(out.tag >= 0, row, out.tag).to(torch.int32))
+        return (out, ranks) if return_ranks else out
 
     # ---- videos of any length: sliding windows, one ranked list of moments per (video, query) in the video's own clips (no reference counterpart) ----
     def encode_windows(self, videos, window, stride, windows_per_call=256):

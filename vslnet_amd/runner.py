@@ -337,15 +337,19 @@ def summarise_corpus(best_ious, found, k):
     return {'k': k, 'corpus_r_k_i5': r5, 'corpus_r_k_i7': r7, 'video_recall_k': rec}, text
 
 
-def eval_corpus(model, split, device, topk, videos_per_call=64, pairs_per_call=4096):
+def eval_corpus(model, split, device, topk, videos_per_call=64, pairs_per_call=4096, prefilter=0, relevance='max'):
     """Moment retrieval over the whole split (no reference counterpart): every record's query is run against EVERY video of a `data.ResidentSplit`,
     not only its own.  The videos are encoded once at the split's Tmax (split.encode, as eval_test_shared does), the queries batch by batch
     (VSLNet.encode_query), and VSLNet.retrieve returns each query's topk.k best moments over all videos, ranked on the device; one device-to-host
-    copy per batch brings (video, start, end, count) back.  -> (stats dict, text line) of summarise_corpus.  `topk`: a TopK(k, nms_iou, max_span)."""
+    copy per batch brings (video, start, end, count) back.  -> (stats dict, text line) of summarise_corpus.  `topk`: a TopK(k, nms_iou, max_span).
+    `prefilter` = M >= 1 (with `relevance`): VSLNet.retrieve's coarse-to-fine search, localising in the M best videos per query only.  The stats
+    then also hold 'prefilter_m' and 'prefilter_recall_m' -- prefilter video recall@M: the share of queries whose ground-truth video is among the M
+    selected (the first stage's VideoRanks; the set comes back in the same copy as the moments) -- and the text starts with that line."""
     del device
     if topk is None:
         raise ValueError('eval_corpus needs topk = TopK(k >= 1, nms_iou, max_span): the moments returned per query')
-    best, found = [], []
+    prefilter = int(prefilter or 0)
+    best, found, kept = [], [], []
     bs, n = split.batch_size, len(split.records)
     with torch.no_grad():
         venc = split.encode(model, videos_per_call=videos_per_call)
@@ -357,11 +361,24 @@ def eval_corpus(model, split, device, topk, videos_per_call=64, pairs_per_call=4
             word_ids = torch.index_select(split.d_words[:, :Lq], 0, idx_dev)
             char_ids = torch.index_select(split.d_chars[:, :Lq, :Lc], 0, idx_dev)
             qenc = model.encode_query(word_ids, char_ids, (word_ids != 0).float())
-            m = model.retrieve(venc, qenc, topk.k, nms_iou=topk.nms_iou, max_span=topk.max_span, pairs_per_call=max(pairs_per_call, len(idx)))
-            out = torch.cat([m.tag.long(), m.start, m.end, m.count[:, None].long()], dim=1).cpu().numpy()
+            per_call = max(pairs_per_call, len(idx))
+            if prefilter:
+                m, ranks = model.retrieve(venc, qenc, topk.k, nms_iou=topk.nms_iou, max_span=topk.max_span, pairs_per_call=per_call, prefilter=prefilter,
+                                          relevance=relevance, return_ranks=True)
+                out = torch.cat([m.tag.long(), m.start, m.end, m.count[:, None].long(), ranks.video.long()], dim=1).cpu().numpy()
+            else:
+                m = model.retrieve(venc, qenc, topk.k, nms_iou=topk.nms_iou, max_span=topk.max_span, pairs_per_call=per_call)
+                out = torch.cat([m.tag.long(), m.start, m.end, m.count[:, None].long()], dim=1).cpu().numpy()
             K = topk.k
             for q, i in enumerate(idx):
                 b, f = corpus_hits(out[q, :K], out[q, K:2 * K], out[q, 2 * K:3 * K], out[q, 3 * K], split.records[i], split.vid_of[i])
                 best.append(b)
                 found.append(f)
-    return summarise_corpus(best, found, topk.k)
+                if prefilter:
+                    kept.append(int(split.vid_of[i]) in out[q, 3 * K + 1:].tolist())
+    stats, text = summarise_corpus(best, found, topk.k)
+    if prefilter:
+        rec = float(np.mean(np.asarray(kept, dtype=np.float64)) * 100.0)
+        stats = dict(stats, prefilter_m=prefilter, prefilter_recall_m=rec)
+        text = 'Prefilter ({}) video recall@{}: {:.2f}\n'.format(relevance, prefilter, rec) + text
+    return stats, text

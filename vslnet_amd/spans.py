@@ -86,6 +86,38 @@ def merge_topk_reference(start, end, score, key, count, group_index, G, k_out, t
     return out_tag, out_list, out_start, out_end, out_score, out_key, out_count
 
 
+def pair_relevance_reference(h_score, v_mask_or_lengths, mode='max'):
+    """(B, T) highlight scores -> (B,) float32: one relevance per pair over its VALID clips (vsl_highlight_pairs).  Validity: a (B, T) mask (non-zero =
+    valid) or (B,) lengths (the first lengths[b] clips).  mode 'max': the maximum, exact; 'mean': sum / count in float64, rounded once to float32 (the
+    kernel sums in fp32: compare with a tolerance).  A pair without a valid clip gets -inf."""
+    if mode not in ('max', 'mean'):
+        raise ValueError("relevance must be 'max' or 'mean', got %r" % (mode,))
+    h = np.asarray(h_score, dtype=np.float32)
+    B, T = h.shape
+    v = np.asarray(v_mask_or_lengths)
+    valid = (v != 0) if v.ndim == 2 else (np.arange(T)[None, :] < v.reshape(B, 1))
+    out = np.full(B, -np.inf, dtype=np.float32)
+    for b in range(B):
+        x = h[b][valid[b]]
+        if x.size:
+            out[b] = x.max() if mode == 'max' else np.float32(x.astype(np.float64).sum() / x.size)
+    return out
+
+
+def select_topm_reference(key, M):
+    """(G, N) keys -> index (G, M) int32, key (G, M) float32, count (G,) int32: per row the first min(M, N) indices in the order key descending, ties by
+    the smaller index, ranked (vsl_select_topm).  -0.0 counts as +0.0: keys are compared -- and returned -- as key + 0.0.  Slots from count on: -1, 0."""
+    key = np.asarray(key, dtype=np.float32) + np.float32(0.0)
+    G, N = key.shape
+    n = min(int(M), N)
+    out_index, out_key = np.full((G, M), -1, dtype=np.int32), np.zeros((G, M), dtype=np.float32)
+    index = np.arange(N)
+    for g in range(G):
+        order = np.lexsort((index, -key[g]))[:n]
+        out_index[g, :n], out_key[g, :n] = order, key[g][order]
+    return out_index, out_key, np.full(G, n, dtype=np.int32)
+
+
 def window_table(L, window, stride):
     """The sliding windows over a video of L clips -> (start, length) int64 arrays: window w starts at clip w * stride; there is one window when
     L <= window, else ceil((L - window) / stride) + 1; the last one may be short: length = min(window, L - w * stride).  Every clip is covered when
