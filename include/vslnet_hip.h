@@ -333,6 +333,60 @@ int64_t vsl_shared_workspace_offset(vsl_handle h, int B, int N, int T, int Lq, i
 
 /* compute_loss + compute_highlight_loss (VSLNet_t7.py:67-72) and their gradient seeds */
 int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_stream);
+/* THE VIDEO RANKING LOSS: vsl_loss over GROUPS of pair rows, plus a softmax ranking term over every group's video relevances (no reference
+ * counterpart).  It trains the score the coarse half of a corpus search ranks videos by -- vsl_highlight_pairs' max / mean of h_score over the valid
+ * clips -- to put a query's own video in front of other videos.
+ * A batch of B pair rows is cut into G contiguous groups: group g is rows group_start[g] .. group_start[g + 1] - 1 (group_start[0] = 0,
+ * group_start[G] = B, every group at least one row); positive[g] is the row of the group's true (query, video) pair, every other row of the group is
+ * the same query against another video.  The consistency of the two tables is the CALLER'S precondition, as with vsl_shared_io.video_index; every
+ * loop is bounded by B, G and T whatever they hold.  The terms:
+ *   - span: vsl_loss' CE(start) + CE(end) summed over the POSITIVE rows only, times inv_pos.  A non-positive row contributes nothing: its
+ *     d_start_logits / d_end_logits rows are exactly 0 and neither its logits nor its labels are read;
+ *   - highlight: vsl_loss' loss over all B rows (a sampler passes all-zero h_labels on a negative row: nothing in another video is the query's moment);
+ *   - relevance r_b: the reduction of vsl_highlight_pairs over row b's valid clips (relevance = 0 max, 1 mean: the same additions in the same order;
+ *     -INFINITY without a valid clip), z_b = r_b * inv_temperature;
+ *   - rank: per group over its rows with a finite z: lse_g = m_g + logf(sum_b expf(z_b - m_g)) added in ascending b (m_g their maximum),
+ *     l_g = lse_g - z_positive; rank = inv_groups * sum_g l_g added in ascending g.  A group whose positive row has no valid clip is SKIPPED: no term,
+ *     no rank gradient, no hit;
+ *   - rank gradient: d r_b = w_rank * inv_groups * inv_temperature * (expf(z_b - lse_g) - [b == positive[g]]).  max: added to d_h_score[b][t*] only,
+ *     t* the first valid clip that attains the maximum; mean: d r_b / count_b added at every valid clip.  A masked clip gets the highlight seed alone
+ *     (0 under the mask);
+ *   - hits: the non-skipped groups whose positive row is first in the order (z descending, then the smaller row).
+ * losses[5] = loc, highlight, rank, w_loc loc + w_highlight highlight + w_rank rank, the mask sum used.
+ * The loss has ONE definition: the kernels are built from the device functions vsl_loss' kernels are built from.  With every group of size one and
+ * inv_pos = vsl_loss_io.inv_batch, at every w_rank (l_g = 0 and d r = 0 there): losses[0], losses[1] and losses[4] are bit for bit vsl_loss'
+ * losses[0], [1] and [3], and the three seeds compare equal to vsl_loss' as floats.
+ * No float atomic anywhere: per-row partials go through `scratch` and are re-reduced in index order; two runs give the same bits.
+ * A free-standing call like vsl_merge_topk: it touches no plan and no handle state and reads only what it is passed, so it is legal behind any
+ * training or saved forward; the caller hands the seeds to vsl_backward / vsl_backward_shared / vsl_backward_accumulate through vsl_io.d_* (fused_step
+ * works; vsl_io.fused_loss is simply not used on such a step).  TWO launches on the caller's stream: "group_loss_a" (one workgroup per row: the
+ * log-sum-exps, the highlight partial, the relevance, its argmax and count) and "group_loss_c" (a (ceil(T / 256), B) grid writes the seeds; block (0, 0)
+ * the loss values and the hits).
+ * Refused by name: NULL required pointers; B, G or T below 1; G above B; T above 4096; B above 65535 (a grid dimension); seeds not all-or-none;
+ * inv_temperature <= 0; relevance other than 0 or 1; a NULL label array with a non-zero weight for it (start_labels and end_labels: both or neither).
+ * Labels of a positive row outside [0, T) read outside the logits, as in vsl_loss.  Detect the feature by the presence of the symbols:
+ * VSL_ABI_VERSION does not change for an added entry point. */
+typedef struct vsl_group_loss_io {         /* zero-initialise; new fields are appended */
+    int32_t B, T, G;
+    const float* h_score; const float* start_logits; const float* end_logits; const float* v_mask;   /* (B, T)                                  */
+    const int64_t* start_labels; const int64_t* end_labels;   /* (B); read at positive rows only; NULL iff w_loc == 0                           */
+    const int64_t* h_labels;               /* (B, T); NULL iff w_highlight == 0                                                                */
+    const int32_t* group_start; const int32_t* positive;      /* (G + 1), (G), device                                                          */
+    float w_loc, w_highlight, w_rank;
+    float inv_pos;                         /* normaliser of the span CE: 1 / number of positive rows of the GLOBAL step                        */
+    float inv_groups;                      /* normaliser of the rank term                                                                      */
+    float mask_sum;                        /* as vsl_loss_io.mask_sum (<= 0: this call's own sum over all B rows)                              */
+    float inv_temperature;
+    int32_t relevance;                     /* 0 = max, 1 = mean: vsl_highlight_io.relevance                                                    */
+    float* losses;                         /* out, 5 floats: loc, highlight, rank, total, mask_sum used                                        */
+    int32_t* hits;                         /* out, nullable: number of groups whose positive row ranks first                                   */
+    float* pair_relevance;                 /* out (B), nullable                                                                                */
+    float* d_h_score; float* d_start_logits; float* d_end_logits;   /* out (B, T), all or none; overwritten                                    */
+    float* scratch;                        /* vsl_group_loss_scratch_floats(B, G) floats, caller-owned                                         */
+} vsl_group_loss_io;
+/* floats of vsl_group_loss_io.scratch: ten per-row arrays (log-sum-exps, CE term, highlight numerator, mask sum, relevance, argmax, count, group, z) */
+int vsl_group_loss_scratch_floats(int B, int G, int64_t* out);
+int vsl_group_loss(vsl_handle h, const vsl_group_loss_io* l, void* hip_stream);
 /* autograd backward of everything in vsl_forward (main_t7.py:110); needs the same io (workspace, seed) */
 int vsl_backward(vsl_handle h, const vsl_io* io, void* hip_stream);
 /* GRADIENT ACCUMULATION: one optimizer step over K micro-batches (no reference counterpart: main_t7.py steps once per batch).  vsl_backward_accumulate is

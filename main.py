@@ -40,6 +40,12 @@ What differs from the reference, by design:
     windows' moments merged on the device into the video's own clips) and Rank@1 / mean IoU of the first merged moment -- with `--topk K` also Rank@K
     over the K merged moments -- are reported.  0 (default): off, nothing printed or written changes.  `--mode train` only stores the flags in
     configs.json, where --mode test finds them as its defaults;
+  * `--rank_negatives n` (with `--rank_lambda`, `--rank_temperature`, `--rank_relevance max|mean`; `--mode train --share_videos`, `--data resident`,
+    `--optimizer fused`, `--accum_steps 1`): the video ranking loss.  `--batch_size` stays the number of pair ROWS of a step; a step takes
+    batch_size // (1 + n) queries, pairs each with its own video and with up to n other videos of the step (ResidentSplit.shards(negatives=n)) and
+    adds rank_lambda times a softmax ranking term over every query's video relevances -- the max / mean of the highlight score that
+    `--corpus_prefilter` ranks by -- to the loss (Engine.group_loss).  The log line then also shows the rank term and hits / groups.  0 (default):
+    nothing that is enqueued, printed or written changes.  --mode test takes the stored --rank_relevance as its default --corpus_relevance;
   * `--task synthetic` builds a small learnable dataset in the reference's record format (no dataset files needed).
 """
 import argparse
@@ -114,6 +120,12 @@ def build_parser():
                    'localise each query only in its M best videos (VSLNet.retrieve prefilter=M); also reports prefilter video recall@M.  0: every video')
     p.add_argument('--corpus_relevance', choices=('max', 'mean'), default='max', help='--corpus_prefilter: a video\'s relevance to a query is the max or '
                    'the mean of the highlight score over its clips')
+    p.add_argument('--rank_negatives', type=int, default=0, help='--mode train --share_videos: the video ranking loss -- every query is also paired with up '
+                   'to this many other videos of its step and a softmax ranking term over the videos\' relevances is added to the loss (0: off)')
+    p.add_argument('--rank_lambda', type=float, default=None, help='--rank_negatives: weight of the ranking term (1.0)')
+    p.add_argument('--rank_temperature', type=float, default=None, help='--rank_negatives: temperature of the softmax over the relevances (0.1)')
+    p.add_argument('--rank_relevance', choices=('max', 'mean'), default=None, help='--rank_negatives: the relevance of a video is the max or the mean of '
+                   'the highlight score over its clips (max); --mode test takes it as the default of --corpus_relevance')
     p.add_argument('--window', type=int, default=0, help='--mode test with --data resident: also evaluate every record by sliding windows of this many clips '
                    '(runner.eval_windows; at most --max_pos_len; 0: off)')
     p.add_argument('--window_stride', type=int, default=0, help='--window: clips between two window starts (1 .. --window; 0: half the window)')
@@ -156,6 +168,40 @@ def check_accum(configs, world):
             raise ValueError('--accum_steps > 1 with --share_videos is refused: the shared step accumulates at the library and Engine level only '
                              '(Engine.backward(accumulate=True))')
     return accum
+
+
+def rank_of(configs, world=1):
+    """--rank_negatives / --rank_lambda / --rank_temperature / --rank_relevance -> (n, lambda, temperature, relevance), or None (off; a configs.json from
+    before the flags has none).  The three options belong to --rank_negatives and are refused without it; in --mode train, n > 0 needs
+    --share_videos, --data resident, --optimizer fused and --accum_steps 1 (--mode test only reads what the run stored)."""
+    n = int(getattr(configs, 'rank_negatives', 0) or 0)
+    lam, temp, rel = (getattr(configs, k, None) for k in ('rank_lambda', 'rank_temperature', 'rank_relevance'))
+    if n < 0:
+        raise ValueError('--rank_negatives %d: at least 0 (0: off)' % n)
+    if n == 0:
+        for flag, v in (('--rank_lambda', lam), ('--rank_temperature', temp), ('--rank_relevance', rel)):
+            if v is not None:
+                raise ValueError('%s needs --rank_negatives n > 0: it belongs to the video ranking loss' % flag)
+        return None
+    lam, temp, rel = 1.0 if lam is None else float(lam), 0.1 if temp is None else float(temp), rel or 'max'
+    if not temp > 0:
+        raise ValueError('--rank_temperature %g: must be positive' % temp)
+    if rel not in ('max', 'mean'):
+        raise ValueError('--rank_relevance %r: max or mean' % (rel,))
+    if configs.mode.lower() == 'train':
+        if not getattr(configs, 'share_videos', False):
+            raise ValueError('--rank_negatives needs --share_videos: the negative rows are the same query against other videos of the step, which the shared step encodes once')
+        if configs.data != 'resident':
+            raise ValueError('--rank_negatives needs --data resident (the sampler gathers the step\'s videos out of the split held in device memory)')
+        if configs.optimizer != 'fused':
+            raise ValueError('--rank_negatives needs --optimizer fused (the step runs through the engine: forward_shared, group_loss, fused backward)')
+        if int(getattr(configs, 'accum_steps', 1) or 1) != 1:
+            raise ValueError('--rank_negatives needs --accum_steps 1: the ranking step does not accumulate')
+        if world > 1:
+            raise ValueError('--rank_negatives is single-process (world = %d): data parallel through a shared encoding is not supported' % world)
+        if 1 + n > int(configs.batch_size):
+            raise ValueError('--rank_negatives %d: a group of %d rows does not fit into --batch_size %d rows' % (n, 1 + n, configs.batch_size))
+    return n, lam, temp, rel
 
 
 def check_corpus(configs):
@@ -218,6 +264,9 @@ def train(configs, dataset, features, device, world, rank, log=print):
     model_dir = model_home(configs)
     accum = check_accum(configs, world)
     topk = topk_of(configs)
+    rank_loss = rank_of(configs, world)
+    if rank_loss is not None:                                               # (the resolved values go into configs.json)
+        configs.rank_negatives, configs.rank_lambda, configs.rank_temperature, configs.rank_relevance = rank_loss
     gen = torch.Generator().manual_seed(configs.seed)                       # same shuffle on every rank
     share = bool(getattr(configs, 'share_videos', False))
     if share:
@@ -231,6 +280,8 @@ def train(configs, dataset, features, device, world, rank, log=print):
         train_loader = data.ResidentSplit(dataset['train_set'], features, configs, device, train=True, generator=gen)
         test_loader = data.ResidentSplit(dataset['test_set'], features, configs, device, train=False)
         shards = (lambda: train_loader.shards(queries_per_video=configs.queries_per_video)) if share else (lambda: train_loader.shards(rank, world, micro_batches=accum))
+        if rank_loss is not None:
+            shards = lambda: train_loader.shards(negatives=rank_loss[0])
         log('dataset resident in HBM: %.1f MiB train, %.1f MiB test' % (train_loader.nbytes() / 2 ** 20, test_loader.nbytes() / 2 ** 20))
     elif configs.data == 'loader':
         train_loader = data.get_train_loader(dataset['train_set'], features, configs, pin=True, generator=gen)
@@ -238,7 +289,7 @@ def train(configs, dataset, features, device, world, rank, log=print):
         shards = lambda: data.loader_shards(train_loader, device, rank, world, micro_batches=accum)
     else:
         raise ValueError('Unknown --data {}!!!'.format(configs.data))
-    n_batches = len(train_loader)
+    n_batches = len(train_loader) if rank_loss is None else train_loader.steps_per_epoch(rank_loss[0])     # (batch_size // (1 + n) queries per step)
     configs.num_train_steps = n_batches * configs.epochs                    # main_t7.py:58
     if rank == 0:
         os.makedirs(model_dir, exist_ok=True)
@@ -295,8 +346,18 @@ def train(configs, dataset, features, device, world, rank, log=print):
                 if fused:
                     # this rank's rows, padded to the GLOBAL batch widths; the losses are normalised with the global batch
                     inv_batch, mask_sum = dp.global_normalisers(batch['lens_global'])
-                    parts = []
+                    parts, rank_log = [], None
                     for j, batch in enumerate(micro):
+                        if rank_loss is not None:       # the video ranking step: groups of rows, the loss as two launches of its own (never lazy)
+                            eng.forward_shared(flat, pad_vec, glove_vec, batch['word_ids'], batch['char_ids'], batch['vfeats'], batch['video_v_mask'],
+                                               (batch['word_ids'] != 0).float(), batch['video_index'], training=True, seed=(configs.seed << 20) + global_step)
+                            gl, hits, _, *seeds = eng.group_loss(batch['s_labels'], batch['e_labels'], batch['h_labels'], batch['group_start'], batch['positive'],
+                                                                 1.0, configs.highlight_lambda, rank_loss[1], rank_loss[2], rank_loss[3],
+                                                                 inv_pos=1.0 / batch['n_pos'], inv_groups=1.0 / batch['n_pos'], mask_sum=mask_sum)
+                            dp.backward_exchange_step(eng, xchg, grads, seeds, opt)
+                            parts.append(gl[3])
+                            rank_log = (gl, hits, batch['n_pos'])
+                            continue
                         if batch['vfeats'].shape[0] == 0:
                             # a rank without rows in this batch: zero bucket, same exchange calls, same (replicated) update
                             losses, seeds = torch.zeros(4, device=device), None
@@ -342,7 +403,10 @@ def train(configs, dataset, features, device, world, rank, log=print):
                         torch.distributed.all_reduce(t)
                         lv = float(t.item())
                     history.append((global_step, lv))
-                    log('step %6d | loss %.4f' % (global_step, lv))
+                    if fused and rank_log is not None:
+                        log('step %6d | loss %.4f | rank %.4f | hits %d/%d' % (global_step, lv, float(rank_log[0][2].item()), int(rank_log[1].item()), rank_log[2]))
+                    else:
+                        log('step %6d | loss %.4f' % (global_step, lv))
                 t3 = clock()
                 if trace is not None:
                     trace['log'] += t3 - t2
@@ -412,6 +476,10 @@ def test(configs, parser, argv, dataset, features, device, log=print):
     with open(os.path.join(model_dir, 'configs.json'), encoding='utf-8') as f:
         parser.set_defaults(**json.load(f))                                    # main_t7.py:136-138
     configs = parser.parse_args(argv)
+    rank_loss = rank_of(configs)
+    given = any(a == '--corpus_relevance' or a.startswith('--corpus_relevance=') for a in (sys.argv[1:] if argv is None else argv))
+    if rank_loss is not None and getattr(configs, 'corpus', False) and not given:
+        configs.corpus_relevance = rank_loss[3]                                # the relevance the run was trained to rank by
     model = VSLNet(configs=configs, word_vectors=dataset['word_vector']).to(device)
     model.load_state_dict(torch.load(runner.get_last_checkpoint(model_dir, suffix='t7'), map_location=device))
     model.eval()
@@ -461,7 +529,8 @@ def run(argv=None, log=print):
     parser = build_parser()
     configs = parser.parse_args(argv)
     world, rank, local = _dist_env()
-    check_accum(configs, world)                     # (before the dataset is built: a refused combination costs nothing)
+    rank_of(configs, world)                         # (before the dataset is built: a refused combination costs nothing)
+    check_accum(configs, world)
     topk_of(configs)
     check_corpus(configs)
     prefilter_of(configs)

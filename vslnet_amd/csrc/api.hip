@@ -466,6 +466,40 @@ int vsl_loss(vsl_handle h, const vsl_io* io, const vsl_loss_io* l, void* hip_str
     return 0;
 }
 
+int vsl_group_loss_scratch_floats(int B, int G, int64_t* out) {
+    if (!out) return fail("vsl_group_loss_scratch_floats: null argument");
+    if (B < 1) return fail("vsl_group_loss_scratch_floats: B=%d must be at least 1", B);
+    if (G < 1 || G > B) return fail("vsl_group_loss_scratch_floats: G=%d must be in [1, B=%d]", G, B);
+    *out = group_loss_scratch_floats(B, G);
+    return 0;
+}
+
+int vsl_group_loss(vsl_handle h, const vsl_group_loss_io* l, void* hip_stream) {
+    if (!h || !l) return fail("vsl_group_loss: null argument");
+    if (l->B < 1 || l->B > 65535) return fail("vsl_group_loss: B=%d must be in [1, 65535]", l->B);
+    if (l->T < 1 || l->T > MAX_L) return fail("vsl_group_loss: T=%d must be in [1, %d]", l->T, MAX_L);
+    if (l->G < 1 || l->G > l->B) return fail("vsl_group_loss: G=%d must be in [1, B=%d] (every group has at least one row)", l->G, l->B);
+    if (!l->h_score || !l->start_logits || !l->end_logits || !l->v_mask)
+        return fail("vsl_group_loss: h_score, start_logits, end_logits and v_mask are required inputs");
+    if (!l->group_start || !l->positive) return fail("vsl_group_loss: group_start and positive are required inputs");
+    if (!l->losses) return fail("vsl_group_loss: losses is NULL (the 5 output floats)");
+    if (!l->scratch) return fail("vsl_group_loss: scratch is NULL (vsl_group_loss_scratch_floats(B, G) floats)");
+    if ((l->d_h_score == nullptr) != (l->d_start_logits == nullptr) || (l->d_h_score == nullptr) != (l->d_end_logits == nullptr))
+        return fail("vsl_group_loss: gradient seed outputs must be all set or all null");
+    if (!(l->inv_temperature > 0.f)) return fail("vsl_group_loss: inv_temperature=%g must be positive", (double)l->inv_temperature);
+    if (l->relevance != 0 && l->relevance != 1) return fail("vsl_group_loss: relevance=%d must be 0 (max) or 1 (mean)", l->relevance);
+    if ((l->start_labels == nullptr) != (l->end_labels == nullptr)) return fail("vsl_group_loss: start_labels and end_labels must be both set or both null");
+    if (!l->start_labels && l->w_loc != 0.f) return fail("vsl_group_loss: start_labels / end_labels are NULL but w_loc=%g is not 0", (double)l->w_loc);
+    if (!l->h_labels && l->w_highlight != 0.f) return fail("vsl_group_loss: h_labels is NULL but w_highlight=%g is not 0", (double)l->w_highlight);
+    const GroupLossArgs a{l->start_logits, l->end_logits, l->h_score, l->start_labels, l->end_labels, l->h_labels, l->v_mask, l->group_start, l->positive,
+                          l->B, l->T, l->G, l->inv_pos, l->inv_groups, l->mask_sum, l->w_loc, l->w_highlight, l->w_rank, l->inv_temperature, l->relevance,
+                          l->scratch, l->losses, l->hits, l->pair_relevance, l->d_start_logits, l->d_end_logits, l->d_h_score};
+    { ProfScope ps(h, "group_loss_a"); launch_group_loss_a(a, (hipStream_t)hip_stream); }
+    { ProfScope ps(h, "group_loss_c"); launch_group_loss_c(a, (hipStream_t)hip_stream); }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 int vsl_backward(vsl_handle h, const vsl_io* io, void* hip_stream) {
     if (int rc = check_io(h, io)) return rc;
     if (int rc = check_ordinary_saves(h, io, "vsl_backward")) return rc;

@@ -13,36 +13,8 @@ namespace vsl {
 //   total = w_loc * (CE(start) + CE(end)) + w_hl * highlight      (main_t7.py:105-107 uses 1, 5)
 //   scratch layout (floats): [0,B) lse_s | [B,2B) lse_e | [2B,3B) ce | [3B,4B) hl numerator | [4B,5B) mask sum
 // =========================================================================================================
-__device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    v = is_max ? wave_max(v) : wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    const int nw = blockDim.x >> 6;
-    float r = red[0];
-    for (int i = 1; i < nw; ++i) r = is_max ? fmaxf(r, red[i]) : r + red[i];
-    return r;
-}
-// log-sum-exp of one sample's T logits by a 256-thread workgroup (every thread gets the result).  Every log-sum-exp of the loss comes from here
-// (k_loss_a -> scratch -> k_loss_c, k_loss_fused, and k_head_bwd's inline seeds of vsl_io.fused_loss), and every seed from loss_ce_seed /
-// loss_hl_seed (tile_bodies.hpp), so the seeds are the same bits whichever kernel computes them.
-__device__ __forceinline__ float loss_sample_lse(const float* __restrict__ x, int T, float* red) {
-    const int tid = threadIdx.x;
-    float mx = -3.0e38f;
-    for (int t = tid; t < T; t += 256) mx = fmaxf(mx, x[t]);
-    mx = block_reduce(mx, red, true);
-    float ss = 0.f;
-    for (int t = tid; t < T; t += 256) ss += expf(x[t] - mx);
-    ss = block_reduce(ss, red, false);
-    return mx + logf(ss);
-}
-// the four loss values from the batch sums of the CE terms (ce), of the highlight numerator (num) and the mask sum d
-__device__ __forceinline__ void loss_store(float* __restrict__ losses, float ce, float num, float d, float inv_batch, float w_loc, float w_hl) {
-    const float loc = ce * inv_batch;                                   // CrossEntropyLoss(mean) twice (:367-368)
-    const float hl = num / (d + 1e-12f);                                // (:298)
-    losses[0] = loc; losses[1] = hl; losses[2] = w_loc * loc + w_hl * hl; losses[3] = d;
-}
+// block_reduce, loss_sample_lse and loss_store: tile_bodies.hpp, beside the per-element terms and seeds (kernels_group_loss.hip builds the grouped
+// loss from the same functions)
 __global__ __launch_bounds__(256) void k_loss_a(const float* __restrict__ sl, const float* __restrict__ el,
                                                 const float* __restrict__ h, const int64_t* __restrict__ s_lab,
                                                 const int64_t* __restrict__ e_lab, const int64_t* __restrict__ h_lab,

@@ -3,34 +3,22 @@
 // functions of their inputs: the same bits on every run and for every position of a pair / a group in the call.
 #include "common.hpp"
 #include "launch.hpp"
+#include "rank_reduce.hpp"
 
 namespace vsl {
 
-// ---- k_pair_relevance: (B, T) highlight scores -> one float per pair.  One wave per pair, four pairs per workgroup.  Lane l visits clips l, l + 64, ...
-// in ascending order (its partial), then a 6-step xor butterfly joins the 64 partials: fp32 addition commutes, so every lane of a step forms the same sum
-// and the order of the additions is a function of T alone -- not of the pair, not of the run.  max is exact in any order.
+// ---- k_pair_relevance: (B, T) highlight scores -> one float per pair.  One wave per pair, four pairs per workgroup; the reduction and the order of its
+// additions: rank_reduce.hpp pair_row_reduce (shared with the training loss, kernels_group_loss.hip).
 __global__ __launch_bounds__(256) void k_pair_relevance(RelevanceArgs a) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= a.B) return;                                       // (wave-uniform; no barrier in this kernel)
     const float* h = a.hscore + (size_t)b * a.T;
     const float* m = a.vmask + (size_t)b * a.T;
-    float best = -INFINITY, sum = 0.f;
-    int cnt = 0;
-    for (int t = lane; t < a.T; t += 64) {
-        if (m[t] == 0.f) continue;
-        const float v = h[t];
-        best = fmaxf(best, v);
-        sum += v;
-        ++cnt;
-    }
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) {
-        best = fmaxf(best, __shfl_xor(best, x));
-        sum += __shfl_xor(sum, x);
-        cnt += __shfl_xor(cnt, x);
-    }
+    float best, sum;
+    int cnt;
+    pair_row_reduce(h, m, a.T, lane, best, sum, cnt);
     if (lane != 0) return;
-    const float r = cnt == 0 ? -INFINITY : a.mean ? sum / (float)cnt : best;
+    const float r = pair_row_relevance(best, sum, cnt, a.mean);
     const size_t o = a.ld > 0 ? (size_t)a.qidx[b] * (size_t)a.ld + (size_t)a.vidx[b] : (size_t)b;
     a.out[o] = r;
 }

@@ -421,6 +421,26 @@ struct SelectArgs {
     int32_t* out_count;                   // (G) = min(M, N)
 };
 void launch_select_topm(const SelectArgs& a, hipStream_t s);
+// the grouped training loss: vsl_loss's terms over B pair rows in G groups + a softmax ranking term over every group's relevances
+// (kernels_group_loss.hip; the semantics: include/vslnet_hip.h, vsl_group_loss).  Two launches: _a (one workgroup per row: the partials), _c (the seeds;
+// block (0, 0): the loss values and the hits)
+struct GroupLossArgs {
+    const float *sl, *el, *h;             // (B, T) start / end logits, highlight score
+    const int64_t *s_lab, *e_lab, *h_lab; // (B), (B), (B, T); s_lab / e_lab nullable together (no span loss), h_lab nullable (no highlight loss)
+    const float* vmask;                   // (B, T)
+    const int32_t *group_start, *positive;// (G + 1), (G), device
+    int B, T, G;
+    float inv_pos, inv_groups, mask_sum;  // mask_sum > 0: the caller's (global) mask sum ; otherwise the device sums vmask
+    float w_loc, w_hl, w_rank, inv_t;
+    int mean;                             // the relevance: 0 max, 1 mean (RelevanceArgs.mean)
+    float *scratch, *losses;              // group_loss_scratch_floats(B, G) floats (kernels_group_loss.hip) ; [5]: loc, hl, rank, total, mask_sum
+    int32_t* hits;                        // nullable
+    float* pair_relevance;                // (B), nullable
+    float *d_sl, *d_el, *d_h;             // gradient seeds (all null: the losses alone)
+};
+inline int64_t group_loss_scratch_floats(int B, int G) { (void)G; return 10 * (int64_t)B + 8; }     // (ten per-row arrays; G: none today)
+void launch_group_loss_a(const GroupLossArgs& a, hipStream_t s);
+void launch_group_loss_c(const GroupLossArgs& a, hipStream_t s);
 // windows over projected feature rows (kernels_window.hip; vsl_encode_windows): out (N, T, 128) = proj rows window_row[n] + t for t < window_len[n]
 // inside [0, rows), the projection of a zero feature row (0 + bias) elsewhere ; mask (N, T) = t < window_len[n]
 struct WindowGatherArgs {

@@ -92,6 +92,37 @@ __device__ __forceinline__ float loss_hl_seed(float p, float y, float m, float w
     // d BCE / dp = (p - y) / max(p (1 - p), 1e-12)   (torch's binary_cross_entropy_backward)
     return w_hl * loss_hl_weight(y) * m / (mask_sum + 1e-12f) * (p - y) / fmaxf(p * (1.f - p), 1e-12f);
 }
+// ... and what a whole sample / the batch needs (kernels_head.hip k_loss_*, kernels_group_loss.hip k_group_loss_*)
+__device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    v = is_max ? wave_max(v) : wave_sum(v);
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    const int nw = blockDim.x >> 6;
+    float r = red[0];
+    for (int i = 1; i < nw; ++i) r = is_max ? fmaxf(r, red[i]) : r + red[i];
+    return r;
+}
+// log-sum-exp of one sample's T logits by a 256-thread workgroup (every thread gets the result).  Every log-sum-exp of the loss comes from here
+// (k_loss_a -> scratch -> k_loss_c, k_loss_fused, and k_head_bwd's inline seeds of vsl_io.fused_loss), and every seed from loss_ce_seed /
+// loss_hl_seed (tile_bodies.hpp), so the seeds are the same bits whichever kernel computes them.
+__device__ __forceinline__ float loss_sample_lse(const float* __restrict__ x, int T, float* red) {
+    const int tid = threadIdx.x;
+    float mx = -3.0e38f;
+    for (int t = tid; t < T; t += 256) mx = fmaxf(mx, x[t]);
+    mx = block_reduce(mx, red, true);
+    float ss = 0.f;
+    for (int t = tid; t < T; t += 256) ss += expf(x[t] - mx);
+    ss = block_reduce(ss, red, false);
+    return mx + logf(ss);
+}
+// the four loss values from the batch sums of the CE terms (ce), of the highlight numerator (num) and the mask sum d
+__device__ __forceinline__ void loss_store(float* __restrict__ losses, float ce, float num, float d, float inv_batch, float w_loc, float w_hl) {
+    const float loc = ce * inv_batch;                                   // CrossEntropyLoss(mean) twice (:367-368)
+    const float hl = num / (d + 1e-12f);                                // (:298)
+    losses[0] = loc; losses[1] = hl; losses[2] = w_loc * loc + w_hl * hl; losses[3] = d;
+}
 // gating + HighLightLayer + CQConcatenate backward (VSLNet_t7.py:60, layers_t7.py:262-289 backward):  dgated = dg0 + dg1 + dg2 ;
 // dlogit = (sum_c dgated * f2 + dh_loss) * h (1 - h) ; df2 = dgated * h + dlogit * wh ; df1 = df2 W1 ; partials of wh / bh.
 // lds_dg0 != nullptr: dg0's tile is in LDS (stride LDP; rows >= R zero).  Gs / Fs: two [32][LDP] tiles (neither of them lds_dg0), dlg: 32 floats.

@@ -268,7 +268,7 @@ class ResidentSplit:
         gid = np.concatenate([np.full(len(groups[g]), k, dtype=np.int64) for k, g in enumerate(pick)])
         return order, gid
 
-    def shards(self, rank=0, world=1, order=None, queries_per_video=None, micro_batches=1):
+    def shards(self, rank=0, world=1, order=None, queries_per_video=None, micro_batches=1, negatives=0):
         """One dict per GLOBAL batch: this rank's rows on the device + what the losses need about the whole batch.
         queries_per_video=K (single process): the GROUPED order for the training step through a shared encoding (Engine.forward_shared) -- each
         video's records shuffled and cut into groups of at most K, the groups shuffled and concatenated up to batch_size (a group that crosses a
@@ -277,8 +277,19 @@ class ResidentSplit:
         once per epoch; K = 1 gives N = B, today's content.
         micro_batches=K > 1 (single process; gradient accumulation): K dicts per global batch instead of one, from ONE draw of the order -- piece j
         holds rows dp.micro_slices(B, K)[j] of the batch, padded to the batch's global T / Lq / Lc, with `row0` = its first row and `lens_global`
-        of the whole batch: what rank j of K would get.  A piece without rows (K > B: the last batch of an epoch) is yielded too, empty."""
+        of the whole batch: what rank j of K would get.  A piece without rows (K > B: the last batch of an epoch) is yielded too, empty.
+        negatives=n > 0 (single process, train split): the steps of the video ranking loss (Engine.group_loss), `_negative_shards`."""
         K = int(micro_batches)
+        if int(negatives) != 0:
+            if int(negatives) < 0:
+                raise ValueError('shards(negatives=%d): a count of rows, at least 0' % int(negatives))
+            if queries_per_video is not None or K > 1 or world != 1 or order is not None:
+                raise ValueError('shards(negatives=...) is single-process and draws its own order: not with queries_per_video, micro_batches > 1, '
+                                 'world > 1 or an explicit order')
+            if not self.train:
+                raise ValueError('shards(negatives=...) is for the train split: the negative rows carry training labels')
+            yield from self._negative_shards(int(negatives))
+            return
         if K < 1:
             raise ValueError('shards(micro_batches=%d): at least one' % K)
         if K > 1 and (world != 1 or queries_per_video is not None):
@@ -331,6 +342,59 @@ class ResidentSplit:
             if self.train:
                 b.update(s_labels=out[3], e_labels=out[4], h_labels=out[5])
             yield b
+
+    def steps_per_epoch(self, negatives=0):
+        """Steps of one epoch: len(self), or with shards(negatives=n) ceil(records / P) with P = batch_size // (1 + n) records per step."""
+        if not negatives:
+            return len(self)
+        if 1 + int(negatives) > self.batch_size:
+            raise ValueError('negatives=%d: a group of %d rows does not fit into batch_size=%d rows' % (negatives, 1 + int(negatives), self.batch_size))
+        P = self.batch_size // (1 + int(negatives))
+        return (len(self.records) + P - 1) // P
+
+    def _negative_shards(self, n):
+        """shards(negatives=n): batch_size stays the number of pair ROWS of a step (it sizes the workspace), so a step takes P = batch_size // (1 + n)
+        records in the shuffled order, gathers their distinct videos ONCE (`vfeats` (N, T, Dv), `video_v_mask`, T = the longest of them) and emits one
+        GROUP per record: its own pair first (the positive row), then up to n rows of the same query against other videos of the step, drawn without
+        replacement with the split's generator (a seed reproduces them); fewer when the step holds fewer distinct videos -- the groups are then
+        ragged.  The dict is _grouped_shards' plus `group_start` (G + 1) and `positive` (G) (int32, device) and `n_pos` = G.  A negative row repeats
+        the query's word_ids / char_ids and carries v_mask = video_v_mask[video_index], zero h_labels and the labels 0 (never read);
+        `lens_global` holds the ROW lengths, so dp.global_normalisers gives the row-wise mask sum."""
+        self.steps_per_epoch(n)                                            # (refuses n + 1 > batch_size)
+        P = self.batch_size // (1 + n)
+        order = self._order()
+        for a in range(0, len(order), P):
+            idx = order[a:a + P]
+            vrow, first = {}, []                                           # the step's distinct videos in order of appearance -> row of the video tensors
+            for i in idx:
+                if int(self.vid_of[i]) not in vrow:
+                    vrow[int(self.vid_of[i])] = len(first)
+                    first.append(int(i))
+            N = len(first)
+            rec, vid, group_start, positive = [], [], [0], []
+            for i in idx:
+                own = vrow[int(self.vid_of[i])]
+                others = [v for v in range(N) if v != own]
+                take = torch.randperm(len(others), generator=self.generator).numpy()[:n] if others else []
+                positive.append(len(rec))
+                rec += [int(i)] * (1 + len(take))
+                vid += [own] + [others[j] for j in take]
+                group_start.append(len(rec))
+            rec, vid = np.asarray(rec, dtype=np.int64), np.asarray(vid, dtype=np.int64)
+            is_pos = np.zeros(len(rec), dtype=np.int64)
+            is_pos[positive] = 1
+            vlens = self.lens[first]                                       # clips per VIDEO of the step
+            T, Lq, Lc = int(vlens.max()), int(self.nwords[idx].max()), int(self.nchars[idx].max())
+            up = lambda x, dt: torch.from_numpy(np.asarray(x).astype(dt)).to(self.device)
+            rec_dev, first_dev, vid_dev, pos_dev = up(rec, np.int64), up(first, np.int64), up(vid, np.int64), up(is_pos, np.int64)
+            out = self._gather(rec_dev, T, Lq, Lc, videos=first_dev)
+            ar = torch.arange(T, device=self.device)[None, :]
+            video_v_mask = (ar < self.d_lens[first_dev][:, None]).float()
+            yield {'records': [self.records[i] for i in rec], 'lens_global': vlens[vid], 'row0': 0, 'vfeats': out[0],
+                   'v_mask': video_v_mask[vid_dev].contiguous(), 'video_v_mask': video_v_mask, 'video_index': up(vid, np.int32),
+                   'word_ids': out[1], 'char_ids': out[2], 's_labels': out[3] * pos_dev, 'e_labels': out[4] * pos_dev,
+                   'h_labels': out[5] * pos_dev[:, None], 'group_start': up(group_start, np.int32), 'positive': up(positive, np.int32),
+                   'n_pos': len(idx)}
 
     def __iter__(self):
         for b in self.shards(0, 1):

@@ -114,6 +114,17 @@ class vsl_loss_io(C.Structure):
                 ('d_end_logits', C.c_void_p)]
 
 
+class vsl_group_loss_io(C.Structure):
+    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('G', C.c_int32),
+                ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('v_mask', C.c_void_p),
+                ('start_labels', C.c_void_p), ('end_labels', C.c_void_p), ('h_labels', C.c_void_p),
+                ('group_start', C.c_void_p), ('positive', C.c_void_p),
+                ('w_loc', C.c_float), ('w_highlight', C.c_float), ('w_rank', C.c_float), ('inv_pos', C.c_float), ('inv_groups', C.c_float),
+                ('mask_sum', C.c_float), ('inv_temperature', C.c_float), ('relevance', C.c_int32),
+                ('losses', C.c_void_p), ('hits', C.c_void_p), ('pair_relevance', C.c_void_p),
+                ('d_h_score', C.c_void_p), ('d_start_logits', C.c_void_p), ('d_end_logits', C.c_void_p), ('scratch', C.c_void_p)]
+
+
 class vsl_adamw(C.Structure):
     _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('weight_decay', C.c_float),
                 ('clip_norm', C.c_float), ('step', C.c_int32), ('hf_order', C.c_int32), ('norm_from_backward', C.c_int32)]
@@ -194,7 +205,7 @@ ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count',
                'vsl_backward_accumulate', 'vsl_extract_topk', 'vsl_input_grads', 'vsl_merge_topk',
                'vsl_encode_query_workspace_floats', 'vsl_encode_query', 'vsl_pairs_workspace_floats', 'vsl_localize_pairs',
                'vsl_encode_windows_workspace_floats', 'vsl_encode_windows', 'vsl_merge_windows',
-               'vsl_highlight_pairs', 'vsl_select_topm']
+               'vsl_highlight_pairs', 'vsl_select_topm', 'vsl_group_loss', 'vsl_group_loss_scratch_floats']
 ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
 
 
@@ -271,6 +282,9 @@ def load_library():
         lib.vsl_highlight_pairs.argtypes = [C.c_void_p, C.POINTER(vsl_highlight_io), C.c_void_p]
     if hasattr(lib, 'vsl_select_topm'):
         lib.vsl_select_topm.argtypes = [C.c_void_p, C.POINTER(vsl_select_io), C.c_void_p]
+    if hasattr(lib, 'vsl_group_loss'):                       # (likewise: the video ranking loss)
+        lib.vsl_group_loss_scratch_floats.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        lib.vsl_group_loss.argtypes = [C.c_void_p, C.POINTER(vsl_group_loss_io), C.c_void_p]
     if hasattr(lib, 'vsl_input_grads'):                      # (likewise: the gradient with respect to the video features)
         lib.vsl_input_grads.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p, C.c_void_p]
     lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
@@ -372,6 +386,9 @@ class Engine:
         # vsl_highlight_pairs / vsl_select_topm: rank the videos of a corpus by highlight score.  An older build has neither; highlight_pairs and
         # select_topm then raise (and VSLNet.retrieve serves prefilter=0 only)
         self.has_video_ranking = all(hasattr(self.lib, s) for s in ('vsl_highlight_pairs', 'vsl_select_topm'))
+        # vsl_group_loss: the span / highlight losses over groups of pair rows + the video ranking term.  An older build lacks it; group_loss then raises
+        self.has_group_loss = all(hasattr(self.lib, s) for s in ('vsl_group_loss', 'vsl_group_loss_scratch_floats'))
+        self._group_scratch = {}                        # (B, G) -> the call's scratch
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
         if pred is None:
@@ -995,6 +1012,69 @@ class Engine:
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._call(self.lib.vsl_loss(self.h, C.byref(io), C.byref(l), stream))
         return (losses,) + ((d[0], d[1], d[2]) if want_grads else (None, None, None))
+
+    def group_loss(self, start_labels, end_labels, h_labels, group_start, positive, w_loc=1.0, w_highlight=5.0, w_rank=1.0, temperature=0.1,
+                   relevance='max', inv_pos=None, inv_groups=None, mask_sum=0.0, want_grads=True, scores=None, start_logits=None, end_logits=None,
+                   v_mask=None):
+        """loss() over GROUPS of pair rows plus the video ranking term (include/vslnet_hip.h, vsl_group_loss; the written specification:
+        vslnet_amd.spans.group_loss_reference).  By default on the outputs of the LAST forward; explicit (B, T) tensors may be passed instead.
+        `group_start` (G + 1) / `positive` (G): int32 device tensors (anything else is converted and uploaded); their consistency is the caller's
+        precondition.  `start_labels` / `end_labels` may be None with w_loc == 0 and `h_labels` with w_highlight == 0.  inv_pos and inv_groups
+        default to 1 / G.  -> (losses[5]: loc, highlight, rank, total, mask sum used; hits: int32 scalar tensor; relevance (B,); d_h, d_sl, d_el --
+        None without want_grads).  Never lazy: the call is two launches of its own, and the seeds go to backward() like any others."""
+        if not self.has_group_loss:
+            raise VslError('the loaded library has no video ranking loss (vsl_group_loss / vsl_group_loss_scratch_floats are missing)')
+        if relevance not in ('max', 'mean'):
+            raise ValueError("group_loss: relevance must be 'max' or 'mean', got %r" % (relevance,))
+        if scores is not None:
+            B, T = scores.shape
+            for t, nm in ((scores, 'scores'), (start_logits, 'start_logits'), (end_logits, 'end_logits'), (v_mask, 'mask')):
+                _chk(t, torch.float32, (B, T), nm)
+            ptrs = (_ptr(scores), _ptr(start_logits), _ptr(end_logits), _ptr(v_mask))
+        else:
+            io = self._last
+            if io is None:
+                raise VslError('group_loss: no forward has run and no scores were passed')
+            B, T = io.B, io.T
+            ptrs = (io.h_score, io.start_logits, io.end_logits, io.v_mask)
+        group_start = torch.as_tensor(group_start).to(device=self.device, dtype=torch.int32).contiguous()
+        positive = torch.as_tensor(positive).to(device=self.device, dtype=torch.int32).contiguous()
+        G = int(positive.numel())
+        _chk(group_start, torch.int32, (G + 1,), 'group_start')
+        if (start_labels is None) != (end_labels is None):
+            raise ValueError('group_loss: start_labels and end_labels must be both given or both None')
+        if start_labels is not None:
+            _chk(start_labels, torch.int64, (B,), 'start_labels')
+            _chk(end_labels, torch.int64, (B,), 'end_labels')
+        if h_labels is not None:
+            _chk(h_labels, torch.int64, (B, T), 'h_labels')
+        self._flush_loss()
+        scratch = self._group_scratch.get((B, G))
+        if scratch is None and 1 <= G <= B:             # (anything else: the library refuses the call by name below)
+            n = C.c_int64()
+            self._call(self.lib.vsl_group_loss_scratch_floats(B, G, C.byref(n)))
+            scratch = self._group_scratch[(B, G)] = torch.empty(int(n.value), dtype=torch.float32, device=self.device)
+        losses = torch.empty(5, dtype=torch.float32, device=self.device)
+        hits = torch.empty((), dtype=torch.int32, device=self.device)
+        rel = torch.empty(B, dtype=torch.float32, device=self.device)
+        d = torch.empty(3, B, T, dtype=torch.float32, device=self.device) if want_grads else None
+        l = vsl_group_loss_io()
+        l.B, l.T, l.G = B, T, G
+        l.h_score, l.start_logits, l.end_logits, l.v_mask = ptrs
+        l.start_labels, l.end_labels, l.h_labels = _ptr(start_labels), _ptr(end_labels), _ptr(h_labels)
+        l.group_start, l.positive = _ptr(group_start), _ptr(positive)
+        l.w_loc, l.w_highlight, l.w_rank = float(w_loc), float(w_highlight), float(w_rank)
+        l.inv_pos = float(1.0 / max(G, 1) if inv_pos is None else inv_pos)
+        l.inv_groups = float(1.0 / max(G, 1) if inv_groups is None else inv_groups)
+        l.mask_sum = float(mask_sum)
+        l.inv_temperature = float(1.0 / temperature) if temperature > 0 else 0.0
+        l.relevance = int(relevance == 'mean')
+        l.losses, l.hits, l.pair_relevance, l.scratch = _ptr(losses), _ptr(hits), _ptr(rel), _ptr(scratch)
+        if want_grads:
+            l.d_h_score, l.d_start_logits, l.d_end_logits = _ptr(d[0]), _ptr(d[1]), _ptr(d[2])
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._call(self.lib.vsl_group_loss(self.h, C.byref(l), stream))
+        return (losses, hits, rel) + ((d[0], d[1], d[2]) if want_grads else (None, None, None))
 
     def _flush_loss(self):
         """Issue a pending lazy loss() as its own launch (the caller did not go on to backward() on its seeds)."""

@@ -125,6 +125,22 @@ class _LossFn(torch.autograd.Function):
         return None, None, saved[0] * g, None, None, None, None, None
 
 
+class _RankLossFn(torch.autograd.Function):
+    """compute_video_ranking_loss through the grouped loss kernels with the span and highlight weights at 0: the rank term and its seed alone."""
+
+    @staticmethod
+    def forward(ctx, model, h_score, mask, group_start, positive, temperature, relevance):
+        losses, _, _, d_h, _, _ = model._engine.group_loss(None, None, None, group_start, positive, w_loc=0.0, w_highlight=0.0, w_rank=1.0,
+                                                           temperature=temperature, relevance=relevance, scores=h_score, start_logits=h_score,
+                                                           end_logits=h_score, v_mask=mask)
+        ctx.save_for_backward(d_h)
+        return losses[2].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, ctx.saved_tensors[0] * g, None, None, None, None, None
+
+
 class VSLNet(nn.Module):
     def __init__(self, configs, word_vectors):
         super().__init__()
@@ -524,6 +540,14 @@ class VSLNet(nn.Module):
         B = scores.shape[0]
         z = torch.zeros(B, dtype=torch.int64, device=scores.device)
         return _LossFn.apply(self, 'hl', scores.contiguous(), None, z, z, labels.contiguous().long(), mask.contiguous().float())
+
+    def compute_video_ranking_loss(self, h_score, v_mask, group_start, positive, temperature=0.1, relevance='max'):
+        """The video ranking term of Engine.group_loss (include/vslnet_hip.h, vsl_group_loss; no reference counterpart): the B rows of `h_score` are G
+        contiguous groups (group_start (G + 1), positive (G)), each one query against several videos with its own video at row positive[g]; the
+        loss is the mean over the groups of -log softmax(relevance / temperature)[positive], the relevance being the 'max' / 'mean' of h_score over
+        the valid clips that rank_videos ranks by.  Differentiable with respect to h_score: loc + a * hl + b * rank works in eager mode."""
+        self._engine_for(h_score.device)
+        return _RankLossFn.apply(self, h_score.contiguous().float(), v_mask.contiguous().float(), group_start, positive, float(temperature), relevance)
 
     def compute_loss(self, start_logits, end_logits, start_labels, end_labels):
         B, T = start_logits.shape

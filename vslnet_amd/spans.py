@@ -86,10 +86,12 @@ def merge_topk_reference(start, end, score, key, count, group_index, G, k_out, t
     return out_tag, out_list, out_start, out_end, out_score, out_key, out_count
 
 
-def pair_relevance_reference(h_score, v_mask_or_lengths, mode='max'):
+def pair_relevance_reference(h_score, v_mask_or_lengths, mode='max', fp32_order=False):
     """(B, T) highlight scores -> (B,) float32: one relevance per pair over its VALID clips (vsl_highlight_pairs).  Validity: a (B, T) mask (non-zero =
     valid) or (B,) lengths (the first lengths[b] clips).  mode 'max': the maximum, exact; 'mean': sum / count in float64, rounded once to float32 (the
-    kernel sums in fp32: compare with a tolerance).  A pair without a valid clip gets -inf."""
+    kernel sums in fp32: compare with a tolerance).  A pair without a valid clip gets -inf.
+    fp32_order=True: the mean as the device forms it, addition for addition (rank_reduce.hpp pair_row_reduce): 64 fp32 partials, partial l over the
+    valid clips l, l + 64, ... ascending, joined by a six-step xor butterfly (32, 16, .., 1), then ONE fp32 division -- the device's bits."""
     if mode not in ('max', 'mean'):
         raise ValueError("relevance must be 'max' or 'mean', got %r" % (mode,))
     h = np.asarray(h_score, dtype=np.float32)
@@ -100,8 +102,90 @@ def pair_relevance_reference(h_score, v_mask_or_lengths, mode='max'):
     for b in range(B):
         x = h[b][valid[b]]
         if x.size:
-            out[b] = x.max() if mode == 'max' else np.float32(x.astype(np.float64).sum() / x.size)
+            if mode == 'max':
+                out[b] = x.max()
+            elif not fp32_order:
+                out[b] = np.float32(x.astype(np.float64).sum() / x.size)
+            else:
+                part = np.zeros(64, dtype=np.float32)
+                for t in np.flatnonzero(valid[b]):
+                    part[t % 64] = part[t % 64] + h[b, t]            # (float32 + float32 -> float32: one rounding)
+                for step in (32, 16, 8, 4, 2, 1):
+                    part = part + part[np.arange(64) ^ step]
+                out[b] = part[0] / np.float32(x.size)
     return out
+
+
+GroupLoss = namedtuple('GroupLoss', 'losses hits relevance d_h d_sl d_el')
+
+
+def group_loss_reference(h_score, start_logits, end_logits, v_mask, start_labels, end_labels, h_labels, group_start, positive, w_loc=1.0,
+                         w_highlight=5.0, w_rank=1.0, temperature=0.1, relevance='max', inv_pos=None, inv_groups=None, mask_sum=0.0):
+    """The written specification of vsl_group_loss (include/vslnet_hip.h) in float64 -> GroupLoss(losses (5,) float64: loc, highlight, rank, total,
+    mask sum used; hits int; relevance (B,) float32; d_h, d_sl, d_el (B, T) float64).  B pair rows in G contiguous groups, group g = rows
+    group_start[g] .. group_start[g + 1] - 1 with its true pair at row positive[g].  Everything is float64 on the float32 inputs EXCEPT the relevance,
+    which is pair_relevance_reference(fp32_order=True): the device's own float32 value, so that z = r / temperature carries no reduction error of
+    this function's.  `start_labels` / `end_labels` (read at positive rows only) and `h_labels` may be None with a zero weight.  inv_pos and
+    inv_groups default to 1 / G; mask_sum <= 0: the sum of v_mask."""
+    h = np.asarray(h_score, dtype=np.float32)
+    B, T = h.shape
+    m = np.asarray(v_mask, dtype=np.float32).astype(np.float64)
+    gs, pos = np.asarray(group_start, dtype=np.int64), np.asarray(positive, dtype=np.int64)
+    G = pos.size
+    if gs.size != G + 1 or gs[0] != 0 or gs[-1] != B or (np.diff(gs) < 1).any() or ((pos < gs[:-1]) | (pos >= gs[1:])).any():
+        raise ValueError('group_loss_reference: group_start / positive do not cut %d rows into %d non-empty groups with their positive rows' % (B, G))
+    if (start_labels is None or end_labels is None) and w_loc != 0 or h_labels is None and w_highlight != 0:
+        raise ValueError('group_loss_reference: labels may be None only with a zero weight')
+    inv_pos = 1.0 / G if inv_pos is None else float(inv_pos)
+    inv_groups = 1.0 / G if inv_groups is None else float(inv_groups)
+    inv_t = float(np.float32(1.0 / temperature))                  # (what the caller hands the device)
+    d_h, d_sl, d_el = np.zeros((B, T)), np.zeros((B, T)), np.zeros((B, T))
+    # span: CE(start) + CE(end) over the positive rows
+    ce = 0.0
+    if start_labels is not None and end_labels is not None:
+        for x, lab, d in ((start_logits, start_labels, d_sl), (end_logits, end_labels, d_el)):
+            x = np.asarray(x, dtype=np.float32).astype(np.float64)
+            for b in pos:
+                lse = np.log(np.exp(x[b] - x[b].max()).sum()) + x[b].max()
+                ce += lse - x[b, int(lab[b])]
+                d[b] = w_loc * inv_pos * np.exp(x[b] - lse)
+                d[b, int(lab[b])] -= w_loc * inv_pos
+    loc = ce * inv_pos
+    # highlight: the weighted BCE over all rows (BCELoss clamps its logs at -100)
+    den = float(mask_sum) if mask_sum > 0 else float(m.sum())
+    hl = 0.0
+    if h_labels is not None:
+        y = np.asarray(h_labels).astype(np.float64)
+        p = h.astype(np.float64)
+        q = 1.0 - p
+        with np.errstate(divide='ignore'):
+            lp, lq = np.maximum(np.log(p), -100.0), np.maximum(np.log(q), -100.0)
+        w = np.where(y == 0, 1.0, 2.0 * y)
+        hl = float((-(y * lp + (1.0 - y) * lq) * w * m).sum() / (den + 1e-12))
+        d_h += w_highlight * w * m / (den + 1e-12) * (p - y) / np.maximum(p * q, 1e-12)
+    # rank: softmax over every group's relevances
+    rel = pair_relevance_reference(h, v_mask, relevance, fp32_order=True)
+    valid = np.asarray(v_mask) != 0
+    z = rel.astype(np.float64) * inv_t
+    rank, hits = 0.0, 0
+    for g in range(G):
+        rows = [b for b in range(gs[g], gs[g + 1]) if np.isfinite(z[b])]
+        pb = int(pos[g])
+        if not np.isfinite(z[pb]):
+            continue                                              # skipped: the positive row has no valid clip
+        zz = z[rows]
+        lse = np.log(np.exp(zz - zz.max()).sum()) + zz.max()
+        rank += lse - z[pb]
+        hits += int(min(rows, key=lambda b: (-z[b], b)) == pb)
+        for b in rows:
+            dr = w_rank * inv_groups * inv_t * (np.exp(z[b] - lse) - (b == pb))
+            if relevance == 'max':
+                d_h[b, int(np.flatnonzero(valid[b] & (h[b] == rel[b]))[0])] += dr
+            else:
+                d_h[b, valid[b]] += dr / valid[b].sum()
+    rank *= inv_groups
+    losses = np.array([loc, hl, rank, w_loc * loc + w_highlight * hl + w_rank * rank, den])
+    return GroupLoss(losses, hits, rel, d_h, d_sl, d_el)
 
 
 def select_topm_reference(key, M):
