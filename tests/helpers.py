@@ -1,6 +1,10 @@
 """Shared helpers for the test-suite: golden fixture loading (tests/golden/*.npz, made by oracle/make_golden.py)."""
 import ast
+import functools
 import os
+import re
+import subprocess
+import tempfile
 from types import SimpleNamespace
 
 import numpy as np
@@ -24,6 +28,52 @@ def load_golden(name):
         assert np.allclose(got, ref, rtol=1e-12, atol=1e-12), 'regenerated weights differ from fixture: ' + k
     batch = {k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith('in.')}
     return cfg, P, batch, z
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# include/vslnet_hip.h as the tests read it: its text without comments, the fields of a struct, and the host compiler's layout of every struct
+# ---------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def header_source():
+    """include/vslnet_hip.h without its comments."""
+    return re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'vslnet_hip.h')).read(), flags=re.S)
+
+
+@functools.lru_cache(maxsize=None)
+def header_structs():
+    """{struct: [field names in order]} of every `typedef struct { ... } vsl_*;` of the header."""
+    out = {}
+    for body, name in re.findall(r'typedef struct\s*\w*\s*\{([^}]*)\}\s*(vsl_\w+);', header_source(), flags=re.S):
+        out[name] = [re.search(r'(\w+)\s*$', part).group(1) for decl in body.split(';') if decl.strip() for part in decl.split(',')]
+    return out
+
+
+def header_fields(struct):
+    return header_structs()[struct]
+
+
+@functools.lru_cache(maxsize=None)
+def header_layout():
+    """{struct: (sizeof, {field: offsetof})} of every struct of the header, from ONE program built with the host C compiler."""
+    cc = next((c for c in (os.environ.get('CC'), 'cc', 'gcc', 'clang', '/opt/rocm/llvm/bin/clang') if c and
+               subprocess.run(['sh', '-c', 'command -v ' + c], capture_output=True).returncode == 0), None)
+    assert cc, 'no host C compiler'
+    structs = header_structs()
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "vslnet_hip.h"', 'int main(void) {']
+    for name, fields in structs.items():
+        lines.append('    printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        lines += ['    printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (name, f, name, f) for f in fields]
+    lines += ['    return 0;', '}', '']
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, 's.c'), 'w') as f:
+            f.write('\n'.join(lines))
+        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), os.path.join(d, 's.c'), '-o', os.path.join(d, 's')], check=True)
+        printed = dict(line.split() for line in subprocess.run([os.path.join(d, 's')], capture_output=True, text=True, check=True).stdout.splitlines())
+    return {name: (int(printed[name]), {f: int(printed[name + '.' + f]) for f in fields}) for name, fields in structs.items()}
+
+
+def header_sizeof(struct):
+    return header_layout()[struct][0]
 
 
 def grad_tol(g_ref):

@@ -23,15 +23,13 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import vslnet_oracle as O
-from tests.helpers import ROOT
+from tests.helpers import ROOT, header_fields, header_sizeof
 from vslnet_amd.spans import merge_topk_reference
 
 NEW_SYMBOLS = ('vsl_merge_topk', 'vsl_encode_query_workspace_floats', 'vsl_encode_query', 'vsl_pairs_workspace_floats', 'vsl_localize_pairs')
@@ -46,16 +44,6 @@ def _header():
     return open(os.path.join(ROOT, 'include', 'vslnet_hip.h')).read()
 
 
-def _header_fields(struct):
-    src = re.sub(r'/\*.*?\*/', '', _header(), flags=re.S)
-    body = re.search(r'typedef struct\s*\w*\s*\{([^}]*)\} %s;' % struct, src, flags=re.S).group(1)
-    names = []
-    for decl in body.split(';'):
-        if decl.strip():
-            names += [re.search(r'(\w+)\s*$', part).group(1) for part in decl.split(',')]
-    return names
-
-
 def test_library_exports_the_merge_and_keeps_abi_9():
     from vslnet_amd import build, engine
     lib = ctypes.CDLL(build.build())
@@ -64,26 +52,11 @@ def test_library_exports_the_merge_and_keeps_abi_9():
         assert s in engine.ABI_SYMBOLS, s
     assert lib.vsl_abi_version() == 9 == engine.ABI_VERSION
     assert re.search(r'#define\s+VSL_ABI_VERSION\s+9\b', _header())
-    assert ctypes.sizeof(engine.vsl_io) == PARENT_SIZEOF_VSL_IO and _header_fields('vsl_io')[-1] == 'inference'
-    assert ctypes.sizeof(engine.vsl_localize_io) == PARENT_SIZEOF_VSL_LOCALIZE_IO
-    assert _header_fields('vsl_localize_io') == PARENT_LOCALIZE_FIELDS == [f[0] for f in engine.vsl_localize_io._fields_]
-    # the ctypes mirrors of the new structs: the header's field order and the host compiler's sizes
-    for struct in ('vsl_merge_io', 'vsl_encode_query_io', 'vsl_pairs_io'):
-        assert _header_fields(struct) == [f[0] for f in getattr(engine, struct)._fields_], struct
-    cc = next((c for c in (os.environ.get('CC'), 'cc', 'gcc', 'clang', '/opt/rocm/llvm/bin/clang') if c and
-               subprocess.run(['sh', '-c', 'command -v ' + c], capture_output=True).returncode == 0), None)
-    assert cc, 'no host C compiler'
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, 's.c'), 'w') as f:
-            f.write('#include <stdio.h>\n#include "vslnet_hip.h"\nint main(void) { printf("%zu %zu %zu %zu %zu\\n", sizeof(vsl_io), sizeof(vsl_localize_io), '
-                    'sizeof(vsl_merge_io), sizeof(vsl_encode_query_io), sizeof(vsl_pairs_io)); return 0; }\n')
-        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), os.path.join(d, 's.c'), '-o', os.path.join(d, 's')], check=True)
-        io_size, loc_size, merge_size, encq_size, pairs_size = (int(x) for x in subprocess.run([os.path.join(d, 's')], capture_output=True, text=True,
-                                                                                                check=True).stdout.split())
-    assert io_size == PARENT_SIZEOF_VSL_IO and loc_size == PARENT_SIZEOF_VSL_LOCALIZE_IO
-    assert ctypes.sizeof(engine.vsl_merge_io) == merge_size
-    assert ctypes.sizeof(engine.vsl_encode_query_io) == encq_size
-    assert ctypes.sizeof(engine.vsl_pairs_io) == pairs_size
+    # (the mirrors of vsl_merge_io, vsl_encode_query_io and vsl_pairs_io against the header and the host compiler: tests/test_abi_layout.py, as for
+    # every struct)
+    assert ctypes.sizeof(engine.vsl_io) == header_sizeof('vsl_io') == PARENT_SIZEOF_VSL_IO and header_fields('vsl_io')[-1] == 'inference'
+    assert ctypes.sizeof(engine.vsl_localize_io) == header_sizeof('vsl_localize_io') == PARENT_SIZEOF_VSL_LOCALIZE_IO
+    assert header_fields('vsl_localize_io') == PARENT_LOCALIZE_FIELDS == [f[0] for f in engine.vsl_localize_io._fields_]
 
 
 # ------------------------------------------------------------------------------------------------ 2. the specification (CPU)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import ROOT
+from tests.helpers import ROOT, header_fields
 from vslnet_amd.spans import group_loss_reference, pair_relevance_reference
 
 
@@ -25,8 +25,7 @@ def test_header_declares_the_group_loss_and_keeps_abi_9():
     assert re.search(r'int vsl_group_loss\(vsl_handle h, const vsl_group_loss_io\* l, void\* hip_stream\);', src)
     assert re.search(r'int vsl_group_loss_scratch_floats\(int B, int G, int64_t\* out\);', src)
     assert re.search(r'#define\s+VSL_ABI_VERSION\s+9\b', src) and engine.ABI_VERSION == 9      # an added entry point does not move the version
-    body = re.search(r'typedef struct vsl_group_loss_io \{([^}]*)\} vsl_group_loss_io;', src, flags=re.S).group(1)
-    names = [re.search(r'(\w+)\s*$', part).group(1) for decl in body.split(';') if decl.strip() for part in decl.split(',')]
+    names = header_fields('vsl_group_loss_io')
     assert names == [f[0] for f in engine.vsl_group_loss_io._fields_]                          # the ctypes mirror follows the header's field order
     assert names[:3] == ['B', 'T', 'G'] and names[-1] == 'scratch' and len(names) == 27
     # three int32, then 9 pointers (aligned at 16), 7 floats + 1 int32, 7 pointers

@@ -6,15 +6,13 @@ reference's goldens on its own, holds four times the batch the training plan hol
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import vslnet_oracle as O
-from tests.helpers import ROOT, check_routes, extreme_ragged, load_golden
+from tests.helpers import ROOT, check_routes, extreme_ragged, header_fields, header_sizeof, load_golden
 from tests.test_dispatch_boundaries import ROUTE_LABELS, predicted_routes
 
 # the labels of ROUTE_LABELS that are forward launches (forward.hip forward_full / enc_fwd)
@@ -38,26 +36,12 @@ def test_library_exports_the_inference_entry_and_abi_9():
 
 def test_ctypes_vsl_io_has_the_size_and_field_order_of_the_header():
     from vslnet_amd import engine
-    # field names, in order, from the header's struct body
-    src = re.sub(r'/\*.*?\*/', '', _header(), flags=re.S)
-    body = re.search(r'typedef struct \{([^}]*)\} vsl_io;', src, flags=re.S).group(1)
-    names = []
-    for decl in body.split(';'):
-        if decl.strip():
-            names += [re.search(r'(\w+)\s*$', part).group(1) for part in decl.split(',')]
+    names = header_fields('vsl_io')                                 # field names, in order, from the header's struct body
     assert names == [f[0] for f in engine.vsl_io._fields_], names
     assert names[-1] == 'inference'
-    # the size, from the host compiler
-    cc = next((c for c in (os.environ.get('CC'), 'cc', 'gcc', 'clang', '/opt/rocm/llvm/bin/clang') if c and
-               subprocess.run(['sh', '-c', 'command -v ' + c], capture_output=True).returncode == 0), None)
-    assert cc, 'no host C compiler'
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, 's.c'), 'w') as f:
-            f.write('#include <stdio.h>\n#include "vslnet_hip.h"\nint main(void) { printf("%zu %zu\\n", sizeof(vsl_io), sizeof(vsl_config)); return 0; }\n')
-        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), os.path.join(d, 's.c'), '-o', os.path.join(d, 's')], check=True)
-        io_size, cfg_size = (int(x) for x in subprocess.run([os.path.join(d, 's')], capture_output=True, text=True, check=True).stdout.split())
-    assert ctypes.sizeof(engine.vsl_io) == io_size
-    assert ctypes.sizeof(engine.vsl_config) == cfg_size
+    # the sizes, from the host compiler (every offset of every struct: tests/test_abi_layout.py)
+    assert ctypes.sizeof(engine.vsl_io) == header_sizeof('vsl_io')
+    assert ctypes.sizeof(engine.vsl_config) == header_sizeof('vsl_config')
 
 
 # ------------------------------------------------------------------------------------------------ 2. same bits as the saved path

@@ -13,8 +13,6 @@ import ctypes
 import json
 import os
 import re
-import subprocess
-import tempfile
 from collections import Counter
 from types import SimpleNamespace
 
@@ -23,7 +21,8 @@ import pytest
 import torch
 
 from oracle import vslnet_oracle as O
-from tests.helpers import (HIP_DROP_SITES, ROOT, assert_forced_relu_inside_noise, check_training_against_oracle, grad_tol, hip_dropout)
+from tests.helpers import (HIP_DROP_SITES, ROOT, assert_forced_relu_inside_noise, check_training_against_oracle, grad_tol, header_fields, header_sizeof,
+                           hip_dropout)
 
 NEW_SYMBOLS = ('vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset')
 SIZEOF_VSL_IO = 208             # ABI 9, `inference` last: the struct must not move
@@ -35,16 +34,6 @@ def _header():
     return open(os.path.join(ROOT, 'include', 'vslnet_hip.h')).read()
 
 
-def _header_fields(struct):
-    src = re.sub(r'/\*.*?\*/', '', _header(), flags=re.S)
-    body = re.search(r'typedef struct \{([^}]*)\} %s;' % struct, src, flags=re.S).group(1)
-    names = []
-    for decl in body.split(';'):
-        if decl.strip():
-            names += [re.search(r'(\w+)\s*$', part).group(1) for part in decl.split(',')]
-    return names
-
-
 def test_library_exports_the_shared_training_entry_points_and_keeps_abi_9():
     from vslnet_amd import build, engine
     lib = ctypes.CDLL(build.build())
@@ -54,18 +43,9 @@ def test_library_exports_the_shared_training_entry_points_and_keeps_abi_9():
         assert re.fullmatch(r'vsl_[a-z_]+', s)
     assert lib.vsl_abi_version() == 9 == engine.ABI_VERSION
     assert re.search(r'#define\s+VSL_ABI_VERSION\s+9\b', _header())
-    assert ctypes.sizeof(engine.vsl_io) == SIZEOF_VSL_IO and _header_fields('vsl_io')[-1] == 'inference'
-    assert _header_fields('vsl_shared_io') == [f[0] for f in engine.vsl_shared_io._fields_] == ['N', 'video_index', 'video_v_mask']
-    cc = next((c for c in (os.environ.get('CC'), 'cc', 'gcc', 'clang', '/opt/rocm/llvm/bin/clang') if c and
-               subprocess.run(['sh', '-c', 'command -v ' + c], capture_output=True).returncode == 0), None)
-    assert cc, 'no host C compiler'
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, 's.c'), 'w') as f:
-            f.write('#include <stdio.h>\n#include "vslnet_hip.h"\nint main(void) { printf("%zu %zu\\n", sizeof(vsl_io), sizeof(vsl_shared_io)); return 0; }\n')
-        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), os.path.join(d, 's.c'), '-o', os.path.join(d, 's')], check=True)
-        io_size, sh_size = (int(x) for x in subprocess.run([os.path.join(d, 's')], capture_output=True, text=True, check=True).stdout.split())
-    assert io_size == SIZEOF_VSL_IO
-    assert ctypes.sizeof(engine.vsl_shared_io) == sh_size
+    # (the mirror of vsl_shared_io against the host compiler's layout: tests/test_abi_layout.py, as for every struct)
+    assert ctypes.sizeof(engine.vsl_io) == header_sizeof('vsl_io') == SIZEOF_VSL_IO and header_fields('vsl_io')[-1] == 'inference'
+    assert header_fields('vsl_shared_io') == [f[0] for f in engine.vsl_shared_io._fields_] == ['N', 'video_index', 'video_v_mask']
 
 
 # ------------------------------------------------------------------------------------------------ 2. the oracle, restated (CPU)

@@ -17,8 +17,6 @@ the golden tolerances below (OFF_TILE_MOVED), as DESIGN section 7 records; the e
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 from collections import Counter
 
 import numpy as np
@@ -26,7 +24,7 @@ import pytest
 import torch
 
 from oracle import vslnet_oracle as O
-from tests.helpers import ROOT, check_routes, check_training_against_oracle, extreme_ragged, load_golden
+from tests.helpers import ROOT, check_routes, check_training_against_oracle, extreme_ragged, header_fields, header_sizeof, load_golden
 from tests.test_dispatch_boundaries import ROUTE_LABELS, predicted_routes
 
 FWD_LABELS = tuple(n for n in ROUTE_LABELS if not n.endswith('_bwd'))
@@ -39,16 +37,6 @@ def _header():
     return open(os.path.join(ROOT, 'include', 'vslnet_hip.h')).read()
 
 
-def _header_fields(struct):
-    src = re.sub(r'/\*.*?\*/', '', _header(), flags=re.S)
-    body = re.search(r'typedef struct \{([^}]*)\} %s;' % struct, src, flags=re.S).group(1)
-    names = []
-    for decl in body.split(';'):
-        if decl.strip():
-            names += [re.search(r'(\w+)\s*$', part).group(1) for part in decl.split(',')]
-    return names
-
-
 def test_library_exports_the_shared_video_entry_points_and_keeps_abi_9():
     from vslnet_amd import build, engine
     lib = ctypes.CDLL(build.build())
@@ -57,23 +45,8 @@ def test_library_exports_the_shared_video_entry_points_and_keeps_abi_9():
         assert s in engine.ABI_SYMBOLS, s
     assert lib.vsl_abi_version() == 9 == engine.ABI_VERSION
     assert re.search(r'#define\s+VSL_ABI_VERSION\s+9\b', _header())
-    assert ctypes.sizeof(engine.vsl_io) == PARENT_SIZEOF_VSL_IO and _header_fields('vsl_io')[-1] == 'inference'
-    # the ctypes mirrors: the header's field order ...
-    for struct in ('vsl_encode_io', 'vsl_localize_io'):
-        assert _header_fields(struct) == [f[0] for f in getattr(engine, struct)._fields_], struct
-    # ... and the host compiler's sizes
-    cc = next((c for c in (os.environ.get('CC'), 'cc', 'gcc', 'clang', '/opt/rocm/llvm/bin/clang') if c and
-               subprocess.run(['sh', '-c', 'command -v ' + c], capture_output=True).returncode == 0), None)
-    assert cc, 'no host C compiler'
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, 's.c'), 'w') as f:
-            f.write('#include <stdio.h>\n#include "vslnet_hip.h"\nint main(void) { printf("%zu %zu %zu\\n", sizeof(vsl_io), sizeof(vsl_encode_io), '
-                    'sizeof(vsl_localize_io)); return 0; }\n')
-        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), os.path.join(d, 's.c'), '-o', os.path.join(d, 's')], check=True)
-        io_size, enc_size, loc_size = (int(x) for x in subprocess.run([os.path.join(d, 's')], capture_output=True, text=True, check=True).stdout.split())
-    assert io_size == PARENT_SIZEOF_VSL_IO
-    assert ctypes.sizeof(engine.vsl_encode_io) == enc_size
-    assert ctypes.sizeof(engine.vsl_localize_io) == loc_size
+    # (the mirrors of vsl_encode_io and vsl_localize_io against the header and the host compiler: tests/test_abi_layout.py, as for every struct)
+    assert ctypes.sizeof(engine.vsl_io) == header_sizeof('vsl_io') == PARENT_SIZEOF_VSL_IO and header_fields('vsl_io')[-1] == 'inference'
 
 
 # ------------------------------------------------------------------------------------------------ 2. the oracle, restated (CPU)

@@ -6,8 +6,6 @@ import inspect
 import math
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -80,21 +78,8 @@ def test_header_declares_the_entry_points_and_the_mirrors_match():
     for s in ('vsl_highlight_pairs', 'vsl_select_topm'):
         assert hasattr(lib, s) and s in engine.ABI_SYMBOLS, s
     assert 'kernels_rank.hip' in build.SOURCES
-    # field order and the host compiler's sizes
-    for struct in ('vsl_highlight_io', 'vsl_select_io'):
-        body = re.search(r'typedef struct %s \{([^}]*)\} %s;' % (struct, struct), src, flags=re.S).group(1)
-        names = [re.search(r'(\w+)\s*$', part).group(1) for decl in body.split(';') if decl.strip() for part in decl.split(',')]
-        assert names == [f[0] for f in getattr(engine, struct)._fields_], struct
-    cc = next((c for c in (os.environ.get('CC'), 'cc', 'gcc', 'clang', '/opt/rocm/llvm/bin/clang') if c and
-               subprocess.run(['sh', '-c', 'command -v ' + c], capture_output=True).returncode == 0), None)
-    assert cc, 'no host C compiler'
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, 's.c'), 'w') as f:
-            f.write('#include <stdio.h>\n#include "vslnet_hip.h"\nint main(void) { printf("%zu %zu %zu\\n", sizeof(vsl_pairs_io), sizeof(vsl_highlight_io), '
-                    'sizeof(vsl_select_io)); return 0; }\n')
-        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), os.path.join(d, 's.c'), '-o', os.path.join(d, 's')], check=True)
-        sizes = [int(x) for x in subprocess.run([os.path.join(d, 's')], capture_output=True, text=True, check=True).stdout.split()]
-    assert sizes == [ctypes.sizeof(engine.vsl_pairs_io), ctypes.sizeof(engine.vsl_highlight_io), ctypes.sizeof(engine.vsl_select_io)]
+    # (the mirrors of vsl_pairs_io, vsl_highlight_io and vsl_select_io against the header and the host compiler: tests/test_abi_layout.py, as for
+    # every struct)
     assert engine.TOPM_MAX_M == 1024 and re.search(r'constexpr int TOPM_MAX_M = 1024;', open(os.path.join(ROOT, 'vslnet_amd', 'csrc', 'launch.hpp')).read())
 
 

@@ -7,14 +7,29 @@
 
 using namespace vsl;
 
+// the bf16 throughput mode reads the features eight to a lane
+static int check_bf16_features(const vsl_handle_s* h, const void* video_features_bf16) {
+    if (video_features_bf16 && (h->cfg.video_feature_dim % 8 != 0))
+        return fail("bf16 features need video_feature_dim %% 8 == 0 (got %d)", h->cfg.video_feature_dim);
+    return 0;
+}
+
 static int check_io(vsl_handle_s* h, const vsl_io* io) {
     if (!h || !io) return fail("null handle / io");
     if (!io->params || (!h->cfg.word_table && (!io->pad_vec || !io->glove_vec)) || !io->word_ids || !io->char_ids || (!io->video_features && !io->video_features_bf16) ||
         !io->v_mask || !io->q_mask || !io->h_score || !io->start_logits || !io->end_logits || !io->workspace)
         return fail("vsl_io has a null device pointer");
-    if (io->video_features_bf16 && (h->cfg.video_feature_dim % 8 != 0))
-        return fail("bf16 features need video_feature_dim %% 8 == 0 (got %d)", h->cfg.video_feature_dim);
-    return 0;
+    return check_bf16_features(h, io->video_features_bf16);
+}
+
+// The vsl_io of an evaluation-only entry point (vsl_encode_video, vsl_localize, ...): zeroed but for the shape of its plan's key, the parameters, the
+// workspace and inference = 1; the entry point adds the pointers its sequence reads.
+static vsl_io eval_io(int B, int T, int Lq, int Lc, const float* params, float* workspace) {
+    vsl_io io;
+    memset(&io, 0, sizeof io);
+    io.B = B; io.T = T; io.Lq = Lq; io.Lc = Lc;
+    io.params = params; io.workspace = workspace; io.inference = 1;
+    return io;
 }
 
 static int workspace_floats(vsl_handle_s* h, PlanKind kind, int B, int T, int Lq, int Lc, int64_t* out, int N = 0) {
@@ -265,6 +280,41 @@ static int backward(vsl_handle_s* h, const vsl_io* io, const vsl_shared_io* sh, 
     return 0;
 }
 
+// what vsl_localize_pairs and vsl_highlight_pairs (`who`) refuse alike: the shape and the two resident encodings with their masks and indices
+static int check_pairs_io(const vsl_pairs_io* l, const char* who) {
+    if (l->B < 1) return fail("%s: B=%d pairs (at least one)", who, l->B);
+    if (l->N < 1) return fail("%s: N=%d videos in the encoding (at least one)", who, l->N);
+    if (l->Q < 1) return fail("%s: Q=%d queries in the encoding (at least one)", who, l->Q);
+    if (l->Lq > MAX_LQ) return fail("%s: Lq=%d > %d query words", who, l->Lq, MAX_LQ);
+    if (l->T > MAX_L) return fail("%s: T=%d > %d clips", who, l->T, MAX_L);
+    if (!l->video_encoding) return fail("%s: video_encoding is NULL (the output of vsl_encode_video for the same T and params)", who);
+    if (!l->query_encoding) return fail("%s: query_encoding is NULL (the output of vsl_encode_query for the same Lq and params)", who);
+    if (!l->v_mask) return fail("%s: v_mask is NULL (the (N, T) clip mask of the video encoding)", who);
+    if (!l->q_mask) return fail("%s: q_mask is NULL (the (Q, Lq) word mask of the query encoding)", who);
+    if (!l->video_index) return fail("%s: video_index is NULL (the video of each pair)", who);
+    if (!l->query_index) return fail("%s: query_index is NULL (the query of each pair)", who);
+    return 0;
+}
+
+// what vsl_merge_topk and vsl_merge_windows (`who`; IO: vsl_merge_io / vsl_merge_windows_io) refuse alike: the shape and the lists they read
+template <class IO>
+static int check_merge_io(vsl_handle_s* h, const IO* io, const char* who) {
+    if (!h || !io) return fail("%s: null argument", who);
+    if (io->B < 1) return fail("%s: B=%d must be at least 1", who, io->B);
+    if (io->G < 1) return fail("%s: G=%d must be at least 1", who, io->G);
+    if (io->K < 1 || io->K > TOPK_MAX_K) return fail("%s: K=%d must be in [1, %d]", who, io->K, TOPK_MAX_K);
+    if (io->K_out < 1 || io->K_out > TOPK_MAX_K) return fail("%s: K_out=%d must be in [1, %d]", who, io->K_out, TOPK_MAX_K);
+    if (!io->start || !io->end || !io->score || !io->key || !io->count) return fail("%s: start, end, score, key and count are required inputs", who);
+    if (!io->group_index) return fail("%s: null group_index", who);
+    return 0;
+}
+
+// measuring switch of tools/merge_rate.py: the merge kernels without their cached heads
+static bool merge_rescan_all() {
+    static const bool on = getenv("VSL_MERGE_RESCAN_ALL") != nullptr;
+    return on;
+}
+
 extern "C" {
 
 int vsl_forward(vsl_handle h, const vsl_io* io, void* hip_stream) {
@@ -299,13 +349,9 @@ int vsl_encode_video(vsl_handle h, const vsl_encode_io* e, void* hip_stream) {
     if (e->N < 1) return fail("vsl_encode_video: N=%d videos (at least one)", e->N);
     if (!e->params || (!e->video_features && !e->video_features_bf16) || !e->v_mask || !e->video_encoding || !e->workspace)
         return fail("vsl_encode_io has a null device pointer");
-    if (e->video_features_bf16 && (h->cfg.video_feature_dim % 8 != 0))
-        return fail("bf16 features need video_feature_dim %% 8 == 0 (got %d)", h->cfg.video_feature_dim);
-    vsl_io io;
-    memset(&io, 0, sizeof io);
-    io.B = e->N; io.T = e->T;
-    io.params = e->params; io.video_features = e->video_features; io.video_features_bf16 = e->video_features_bf16; io.v_mask = e->v_mask;
-    io.workspace = e->workspace; io.inference = 1;
+    if (int rc = check_bf16_features(h, e->video_features_bf16)) return rc;
+    vsl_io io = eval_io(e->N, e->T, 0, 0, e->params, e->workspace);
+    io.video_features = e->video_features; io.video_features_bf16 = e->video_features_bf16; io.v_mask = e->v_mask;
     // (FwdInfer: nothing saved -- vsl_backward in this workspace and vsl_workspace_offset are refused as after an inference forward)
     return enqueue(h, &io, PlanKind::Encode, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) { forward_encode(c, e->video_encoding); });
 }
@@ -320,13 +366,10 @@ int vsl_localize(vsl_handle h, const vsl_localize_io* l, void* hip_stream) {
     if (!l->params || (!h->cfg.word_table && (!l->pad_vec || !l->glove_vec)) || !l->word_ids || !l->char_ids || !l->q_mask || !l->h_score || !l->start_logits ||
         !l->end_logits || !l->workspace)
         return fail("vsl_localize_io has a null device pointer");
-    vsl_io io;
-    memset(&io, 0, sizeof io);
-    io.B = l->B; io.T = l->T; io.Lq = l->Lq; io.Lc = l->Lc;
-    io.params = l->params; io.pad_vec = l->pad_vec; io.glove_vec = l->glove_vec;
+    vsl_io io = eval_io(l->B, l->T, l->Lq, l->Lc, l->params, l->workspace);
+    io.pad_vec = l->pad_vec; io.glove_vec = l->glove_vec;
     io.word_ids = l->word_ids; io.char_ids = l->char_ids; io.q_mask = l->q_mask;
     io.h_score = l->h_score; io.start_logits = l->start_logits; io.end_logits = l->end_logits;
-    io.workspace = l->workspace; io.inference = 1;
     return enqueue(h, &io, PlanKind::Localize, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) {
         io.v_mask = c.W(c.p->vmask);          // every kernel behind the join reads the gathered (B, T) mask
         forward_localize(c, CqContext{l->video_encoding, l->video_index}, l->v_mask);
@@ -342,13 +385,9 @@ int vsl_encode_windows(vsl_handle h, const vsl_encode_windows_io* e, void* hip_s
         return fail("vsl_encode_windows_io has a null device pointer");
     if (!e->window_row) return fail("vsl_encode_windows: window_row is NULL (the first feature row of each window)");
     if (!e->window_len) return fail("vsl_encode_windows: window_len is NULL (the valid clips of each window)");
-    if (e->video_features_bf16 && (h->cfg.video_feature_dim % 8 != 0))
-        return fail("bf16 features need video_feature_dim %% 8 == 0 (got %d)", h->cfg.video_feature_dim);
-    vsl_io io;
-    memset(&io, 0, sizeof io);
-    io.B = e->N; io.T = e->T;
-    io.params = e->params; io.video_features = e->video_features; io.video_features_bf16 = e->video_features_bf16; io.v_mask = e->v_mask;
-    io.workspace = e->workspace; io.inference = 1;
+    if (int rc = check_bf16_features(h, e->video_features_bf16)) return rc;
+    vsl_io io = eval_io(e->N, e->T, 0, 0, e->params, e->workspace);
+    io.video_features = e->video_features; io.video_features_bf16 = e->video_features_bf16; io.v_mask = e->v_mask;
     // (the shape's refusals, by name: build_windows_plan.  FwdInfer: nothing saved -- vsl_backward in this workspace and vsl_workspace_offset are
     // refused as after an inference forward)
     return enqueue(h, &io, PlanKind::EncodeWindows, nullptr, hip_stream, vsl_handle_s::FwdInfer,
@@ -363,12 +402,9 @@ int vsl_encode_query(vsl_handle h, const vsl_encode_query_io* e, void* hip_strea
     if (e->Q < 1) return fail("vsl_encode_query: Q=%d queries (at least one)", e->Q);
     if (!e->params || (!h->cfg.word_table && (!e->pad_vec || !e->glove_vec)) || !e->word_ids || !e->char_ids || !e->q_mask || !e->query_encoding || !e->workspace)
         return fail("vsl_encode_query_io has a null device pointer");
-    vsl_io io;
-    memset(&io, 0, sizeof io);
-    io.B = e->Q; io.Lq = e->Lq; io.Lc = e->Lc;
-    io.params = e->params; io.pad_vec = e->pad_vec; io.glove_vec = e->glove_vec;
+    vsl_io io = eval_io(e->Q, 0, e->Lq, e->Lc, e->params, e->workspace);
+    io.pad_vec = e->pad_vec; io.glove_vec = e->glove_vec;
     io.word_ids = e->word_ids; io.char_ids = e->char_ids; io.q_mask = e->q_mask;
-    io.workspace = e->workspace; io.inference = 1;
     // (FwdInfer: nothing saved -- vsl_backward in this workspace and vsl_workspace_offset are refused as after an inference forward)
     return enqueue(h, &io, PlanKind::EncodeQuery, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) { forward_encode_query(c, e->query_encoding); });
 }
@@ -380,24 +416,10 @@ int vsl_pairs_workspace_floats(vsl_handle h, int B, int T, int Lq, int64_t* out)
 
 int vsl_localize_pairs(vsl_handle h, const vsl_pairs_io* l, void* hip_stream) {
     if (!h || !l) return fail("null handle / io");
-    if (l->B < 1) return fail("vsl_localize_pairs: B=%d pairs (at least one)", l->B);
-    if (l->N < 1) return fail("vsl_localize_pairs: N=%d videos in the encoding (at least one)", l->N);
-    if (l->Q < 1) return fail("vsl_localize_pairs: Q=%d queries in the encoding (at least one)", l->Q);
-    if (l->Lq > MAX_LQ) return fail("vsl_localize_pairs: Lq=%d > %d query words", l->Lq, MAX_LQ);
-    if (l->T > MAX_L) return fail("vsl_localize_pairs: T=%d > %d clips", l->T, MAX_L);
-    if (!l->video_encoding) return fail("vsl_localize_pairs: video_encoding is NULL (the output of vsl_encode_video for the same T and params)");
-    if (!l->query_encoding) return fail("vsl_localize_pairs: query_encoding is NULL (the output of vsl_encode_query for the same Lq and params)");
-    if (!l->v_mask) return fail("vsl_localize_pairs: v_mask is NULL (the (N, T) clip mask of the video encoding)");
-    if (!l->q_mask) return fail("vsl_localize_pairs: q_mask is NULL (the (Q, Lq) word mask of the query encoding)");
-    if (!l->video_index) return fail("vsl_localize_pairs: video_index is NULL (the video of each pair)");
-    if (!l->query_index) return fail("vsl_localize_pairs: query_index is NULL (the query of each pair)");
+    if (int rc = check_pairs_io(l, "vsl_localize_pairs")) return rc;
     if (!l->params || !l->h_score || !l->start_logits || !l->end_logits || !l->workspace) return fail("vsl_pairs_io has a null device pointer");
-    vsl_io io;
-    memset(&io, 0, sizeof io);
-    io.B = l->B; io.T = l->T; io.Lq = l->Lq; io.Lc = PAIRS_PLAN_LC;
-    io.params = l->params;
+    vsl_io io = eval_io(l->B, l->T, l->Lq, PAIRS_PLAN_LC, l->params, l->workspace);
     io.h_score = l->h_score; io.start_logits = l->start_logits; io.end_logits = l->end_logits;
-    io.workspace = l->workspace; io.inference = 1;
     return enqueue(h, &io, PlanKind::LocalizePairs, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) {
         io.v_mask = c.W(c.p->vmask);          // every kernel behind the join reads the gathered (B, T) mask
         forward_pairs(c, CqContext{l->video_encoding, l->video_index, l->query_encoding, l->q_mask, l->query_index}, l->v_mask);
@@ -408,27 +430,13 @@ int vsl_localize_pairs(vsl_handle h, const vsl_pairs_io* l, void* hip_stream) {
 int vsl_highlight_pairs(vsl_handle h, const vsl_highlight_io* r, void* hip_stream) {
     if (!h || !r) return fail("null handle / io");
     const vsl_pairs_io* l = &r->pairs;
-    if (l->B < 1) return fail("vsl_highlight_pairs: B=%d pairs (at least one)", l->B);
-    if (l->N < 1) return fail("vsl_highlight_pairs: N=%d videos in the encoding (at least one)", l->N);
-    if (l->Q < 1) return fail("vsl_highlight_pairs: Q=%d queries in the encoding (at least one)", l->Q);
-    if (l->Lq > MAX_LQ) return fail("vsl_highlight_pairs: Lq=%d > %d query words", l->Lq, MAX_LQ);
-    if (l->T > MAX_L) return fail("vsl_highlight_pairs: T=%d > %d clips", l->T, MAX_L);
-    if (!l->video_encoding) return fail("vsl_highlight_pairs: video_encoding is NULL (the output of vsl_encode_video for the same T and params)");
-    if (!l->query_encoding) return fail("vsl_highlight_pairs: query_encoding is NULL (the output of vsl_encode_query for the same Lq and params)");
-    if (!l->v_mask) return fail("vsl_highlight_pairs: v_mask is NULL (the (N, T) clip mask of the video encoding)");
-    if (!l->q_mask) return fail("vsl_highlight_pairs: q_mask is NULL (the (Q, Lq) word mask of the query encoding)");
-    if (!l->video_index) return fail("vsl_highlight_pairs: video_index is NULL (the video of each pair)");
-    if (!l->query_index) return fail("vsl_highlight_pairs: query_index is NULL (the query of each pair)");
+    if (int rc = check_pairs_io(l, "vsl_highlight_pairs")) return rc;
     if (!l->params || !l->workspace) return fail("vsl_highlight_io has a null device pointer");
     if (r->relevance != 0 && r->relevance != 1) return fail("vsl_highlight_pairs: relevance=%d must be 0 (max) or 1 (mean)", r->relevance);
     if (!r->out) return fail("vsl_highlight_pairs: out is NULL (the relevance of each pair)");
     if (r->ld < 0 || (r->ld > 0 && r->ld < l->N))
         return fail("vsl_highlight_pairs: ld=%d must be 0 (out is (B)) or at least N=%d (out is a (Q, ld) matrix)", r->ld, l->N);
-    vsl_io io;
-    memset(&io, 0, sizeof io);
-    io.B = l->B; io.T = l->T; io.Lq = l->Lq; io.Lc = PAIRS_PLAN_LC;
-    io.params = l->params;
-    io.workspace = l->workspace; io.inference = 1;
+    vsl_io io = eval_io(l->B, l->T, l->Lq, PAIRS_PLAN_LC, l->params, l->workspace);
     return enqueue(h, &io, PlanKind::LocalizePairs, nullptr, hip_stream, vsl_handle_s::FwdInfer, [&](Ctx& c) {
         io.v_mask = c.W(c.p->vmask);          // every kernel behind the join reads the gathered (B, T) mask
         io.h_score = l->h_score ? l->h_score : c.W(c.p->p1.out);      // (no predictor runs: the first pass' output slot, (B T, 128), is free)
@@ -567,38 +575,24 @@ int vsl_extract_topk(vsl_handle h, const vsl_topk_io* io, void* hip_stream) {
 }
 
 int vsl_merge_topk(vsl_handle h, const vsl_merge_io* io, void* hip_stream) {
-    if (!h || !io) return fail("vsl_merge_topk: null argument");
-    if (io->B < 1) return fail("vsl_merge_topk: B=%d must be at least 1", io->B);
-    if (io->G < 1) return fail("vsl_merge_topk: G=%d must be at least 1", io->G);
-    if (io->K < 1 || io->K > TOPK_MAX_K) return fail("vsl_merge_topk: K=%d must be in [1, %d]", io->K, TOPK_MAX_K);
-    if (io->K_out < 1 || io->K_out > TOPK_MAX_K) return fail("vsl_merge_topk: K_out=%d must be in [1, %d]", io->K_out, TOPK_MAX_K);
-    if (!io->start || !io->end || !io->score || !io->key || !io->count) return fail("vsl_merge_topk: start, end, score, key and count are required inputs");
-    if (!io->group_index) return fail("vsl_merge_topk: null group_index");
+    if (int rc = check_merge_io(h, io, "vsl_merge_topk")) return rc;
     if (io->tag_per_slot && !io->tag) return fail("vsl_merge_topk: tag_per_slot needs a (B, K) tag");
     if (!io->out_tag || !io->out_list || !io->out_start || !io->out_end || !io->out_score || !io->out_key || !io->out_count)
         return fail("vsl_merge_topk: out_tag, out_list, out_start, out_end, out_score, out_key and out_count are required outputs");
-    static const bool rescan_all = getenv("VSL_MERGE_RESCAN_ALL") != nullptr;      // (measuring switch of tools/merge_rate.py: the kernel without its cached heads)
     launch_merge_topk(MergeArgs{io->start, io->end, io->score, io->key, io->count, io->group_index, io->tag, io->B, io->K, io->G, io->K_out,
-                                io->tag_per_slot != 0, rescan_all, io->out_tag, io->out_list, io->out_start, io->out_end, io->out_score, io->out_key,
+                                io->tag_per_slot != 0, merge_rescan_all(), io->out_tag, io->out_list, io->out_start, io->out_end, io->out_score, io->out_key,
                                 io->out_count}, (hipStream_t)hip_stream);
     HIP_OK(hipGetLastError());
     return 0;
 }
 
 int vsl_merge_windows(vsl_handle h, const vsl_merge_windows_io* io, void* hip_stream) {
-    if (!h || !io) return fail("vsl_merge_windows: null argument");
-    if (io->B < 1) return fail("vsl_merge_windows: B=%d must be at least 1", io->B);
-    if (io->G < 1) return fail("vsl_merge_windows: G=%d must be at least 1", io->G);
-    if (io->K < 1 || io->K > TOPK_MAX_K) return fail("vsl_merge_windows: K=%d must be in [1, %d]", io->K, TOPK_MAX_K);
-    if (io->K_out < 1 || io->K_out > TOPK_MAX_K) return fail("vsl_merge_windows: K_out=%d must be in [1, %d]", io->K_out, TOPK_MAX_K);
+    if (int rc = check_merge_io(h, io, "vsl_merge_windows")) return rc;
     if (!(io->nms_iou >= 0.f && io->nms_iou <= 1.f)) return fail("vsl_merge_windows: nms_iou=%g must be in [0, 1]", (double)io->nms_iou);
-    if (!io->start || !io->end || !io->score || !io->key || !io->count) return fail("vsl_merge_windows: start, end, score, key and count are required inputs");
-    if (!io->group_index) return fail("vsl_merge_windows: null group_index");
     if (!io->out_list || !io->out_start || !io->out_end || !io->out_score || !io->out_key || !io->out_count)
         return fail("vsl_merge_windows: out_list, out_start, out_end, out_score, out_key and out_count are required outputs");
-    static const bool rescan_all = getenv("VSL_MERGE_RESCAN_ALL") != nullptr;      // (measuring switch: the kernel without its cached heads)
     launch_merge_windows(MergeWindowsArgs{io->start, io->end, io->score, io->key, io->count, io->group_index, io->offset, io->B, io->K, io->G, io->K_out,
-                                          io->nms_iou, rescan_all, io->out_list, io->out_start, io->out_end, io->out_score, io->out_key, io->out_count},
+                                          io->nms_iou, merge_rescan_all(), io->out_list, io->out_start, io->out_end, io->out_score, io->out_key, io->out_count},
                          (hipStream_t)hip_stream);
     HIP_OK(hipGetLastError());
     return 0;

@@ -95,18 +95,29 @@ bool query_fused(const Ctx& c) {
 
 // ---- the stages: each enqueues on c.s and reads nothing but its arguments, the plan and the call's vsl_io
 
-// VisualProjection + encoder application 0 over the clips of the plan's video half (B x T; N x T in a shared training step); `out`: the caller's encoding (vsl_encode_video), nullptr = the plan's own buffer
-static void video_branch(Ctx& c, float* out) {
+// VisualProjection of the call's features (fp32, or bf16: the throughput mode) over `rows` feature rows into `dst`
+static void vproj_fwd(Ctx& c, float* dst, int rows) {
     const vsl_config& cf = c.h->cfg; const ModelP& P = c.h->P; const ModelPk& K = c.h->K;
-    const Plan& p = *c.p; const vsl_io& io = *c.io;
-    const int Nv = p.NV(), R = Nv * p.T;
-    if (io.video_features_bf16)      // bf16 throughput mode
-        LAUNCH("vproj_fwd", launch_vproj_fwd_bf16(io.video_features_bf16, reinterpret_cast<const uint16_t*>(c.PK(K.va_f16)), c.P(P.va_b), c.W(p.vf), R,
+    const vsl_io& io = *c.io;
+    if (io.video_features_bf16)
+        LAUNCH("vproj_fwd", launch_vproj_fwd_bf16(io.video_features_bf16, reinterpret_cast<const uint16_t*>(c.PK(K.va_f16)), c.P(P.va_b), dst, rows,
                                                   cf.video_feature_dim, c.drop(SITE_VIS), c.s));
     else
-        LAUNCH("vproj_fwd", launch_vproj_fwd3(io.video_features, reinterpret_cast<const uint16_t*>(c.PK(K.va_f3)), c.P(P.va_b), c.W(p.vf), R, cf.video_feature_dim,
+        LAUNCH("vproj_fwd", launch_vproj_fwd3(io.video_features, reinterpret_cast<const uint16_t*>(c.PK(K.va_f3)), c.P(P.va_b), dst, rows, cf.video_feature_dim,
                                               c.drop(SITE_VIS), c.s));
-    enc_fwd(c, P.fe, K.fe, p.ve, c.W(p.vf), c.video_mask(), Nv, 0, nullptr, out);
+}
+
+// jobs first .. first + n - 1 of the handle's pack table: the matrix-core operands of the call's parameters into the plan's pack area
+static void pack_jobs(Ctx& c, int first, int n) {
+    LAUNCH("pack", launch_pack(c.io->params, c.W(c.p->pack), c.h->jobs_dev + first, n, c.s));
+}
+
+// VisualProjection + encoder application 0 over the clips of the plan's video half (B x T; N x T in a shared training step); `out`: the caller's encoding (vsl_encode_video), nullptr = the plan's own buffer
+static void video_branch(Ctx& c, float* out) {
+    const Plan& p = *c.p;
+    const int Nv = p.NV();
+    vproj_fwd(c, c.W(p.vf), Nv * p.T);
+    enc_fwd(c, c.h->P.fe, c.h->K.fe, p.ve, c.W(p.vf), c.video_mask(), Nv, 0, nullptr, out);
 }
 
 // a pack launch another stream's kernel has to wait for: its stop event and its record in the profiler's ledger (nullptr / -1: nothing to wait for)
@@ -274,11 +285,11 @@ static PackWait side_packs(Ctx& c, hipStream_t sp) {
     const int nj = (int)h->jobs.size(), head = h->jobs_char + h->jobs_first, nj1 = h->jobs_query;
     hipStream_t keep = c.s;
     c.s = sp;
-    LAUNCH("pack", launch_pack(c.io->params, c.W(c.p->pack), h->jobs_dev + head, nj1, c.s));
+    pack_jobs(c, head, nj1);
     PackWait w;
     w.ev = h->last_event(sp);
     w.rec = h->prof_on ? (int)h->prof_recs.size() - 1 : -1;
-    LAUNCH("pack", launch_pack(c.io->params, c.W(c.p->pack), h->jobs_dev + head + nj1, nj - head - nj1, c.s));
+    pack_jobs(c, head + nj1, nj - head - nj1);
     c.s = keep;
     return w;
 }
@@ -300,11 +311,11 @@ void forward_full(Ctx& c) {
         // workgroups x 125 KB of LDS -- starts right behind it and runs beside the remaining packs and VisualProjection, not beside the video
         // pass' conv block (which it kept off 160 CUs: 49 us in the step against 25 alone, profiles/r05_notes.md section 9); the Embedding
         // linear's operand is packed on the third stream meanwhile.
-        LAUNCH("pack", launch_pack(c.io->params, c.W(p.pack), h->jobs_dev, nfirst, c.s));
+        pack_jobs(c, 0, nfirst);
         c.order2(c.main, sq, sp);
         emb_pack = side_packs(c, sp);
     } else {
-        LAUNCH("pack", launch_pack(c.io->params, c.W(p.pack), h->jobs_dev, nj, c.s));
+        pack_jobs(c, 0, nj);
         c.order(c.main, sq);        // fork: the query branch (embedding + query encoder pass) runs beside the video branch
     }
     // The video branch (VisualProjection 19 + conv block 35 + attention 24 us) and the query branch (embedding 30 + linear 17 +
@@ -327,8 +338,7 @@ void forward_full(Ctx& c) {
 // vsl_encode_video: the video half alone -- the shared encoder's and VisualProjection's operands, the projection, encoder application 0
 // into the caller's buffer.  One stream: there is no query branch to run beside it.
 void forward_encode(Ctx& c, float* video_encoding) {
-    const vsl_handle_s* h = c.h;
-    LAUNCH("pack", launch_pack(c.io->params, c.W(c.p->pack), h->jobs_dev + h->jobs_char, h->jobs_first, c.s));
+    pack_jobs(c, c.h->jobs_char, c.h->jobs_first);
     video_branch(c, video_encoding);
 }
 
@@ -336,18 +346,12 @@ void forward_encode(Ctx& c, float* video_encoding) {
 // every window's rows (and of the projection of a zero row behind its length) into the slot the encoder reads, the (N, T) mask into the caller's
 // buffer, then encoder application 0 over the windows into the caller's encoding.  One stream, as forward_encode.
 void forward_encode_windows(Ctx& c, const int32_t* window_row, const int32_t* window_len, float* v_mask, float* video_encoding) {
-    const vsl_handle_s* h = c.h;
-    const vsl_config& cf = h->cfg; const ModelP& P = h->P; const ModelPk& K = h->K;
-    const Plan& p = *c.p; const vsl_io& io = *c.io;
-    LAUNCH("pack", launch_pack(io.params, c.W(p.pack), h->jobs_dev + h->jobs_char, h->jobs_first, c.s));
-    if (io.video_features_bf16)
-        LAUNCH("vproj_fwd", launch_vproj_fwd_bf16(io.video_features_bf16, reinterpret_cast<const uint16_t*>(c.PK(K.va_f16)), c.P(P.va_b), c.W(p.wproj), p.rows,
-                                                  cf.video_feature_dim, c.drop(SITE_VIS), c.s));
-    else
-        LAUNCH("vproj_fwd", launch_vproj_fwd3(io.video_features, reinterpret_cast<const uint16_t*>(c.PK(K.va_f3)), c.P(P.va_b), c.W(p.wproj), p.rows, cf.video_feature_dim,
-                                              c.drop(SITE_VIS), c.s));
+    const ModelP& P = c.h->P;
+    const Plan& p = *c.p;
+    pack_jobs(c, c.h->jobs_char, c.h->jobs_first);
+    vproj_fwd(c, c.W(p.wproj), p.rows);
     LAUNCH("window_gather", launch_window_gather(WindowGatherArgs{c.W(p.wproj), c.P(P.va_b), window_row, window_len, c.W(p.vf), v_mask, p.B, p.T, p.rows}, c.s));
-    enc_fwd(c, P.fe, K.fe, p.ve, c.W(p.vf), v_mask, p.B, 0, nullptr, video_encoding);
+    enc_fwd(c, P.fe, c.h->K.fe, p.ve, c.W(p.vf), v_mask, p.B, 0, nullptr, video_encoding);
 }
 
 // vsl_encode_query: the query half alone into the caller's buffer -- the char-conv image and the shared encoder's operands (the head of the first
@@ -356,8 +360,8 @@ void forward_encode_windows(Ctx& c, const int32_t* window_row, const int32_t* wi
 void forward_encode_query(Ctx& c, float* query_encoding) {
     const vsl_handle_s* h = c.h;
     const int head = h->jobs_char + h->jobs_first;
-    LAUNCH("pack", launch_pack(c.io->params, c.W(c.p->pack), h->jobs_dev, head - h->jobs_va, c.s));
-    LAUNCH("pack", launch_pack(c.io->params, c.W(c.p->pack), h->jobs_dev + head, h->jobs_query, c.s));
+    pack_jobs(c, 0, head - h->jobs_va);
+    pack_jobs(c, head, h->jobs_query);
     query_branch(c, PackWait{}, query_encoding);
 }
 
@@ -371,13 +375,13 @@ void forward_localize(Ctx& c, CqContext ctx, const float* vmask_nt) {
     hipStream_t sp = c.side(1);
     const bool split3 = c.side(0) != c.main && sp != c.main;
     PackWait emb_pack;
-    LAUNCH("pack", launch_pack(c.io->params, c.W(p.pack), h->jobs_dev, nfirst, c.s));
+    pack_jobs(c, 0, nfirst);
     if (split3) {
         c.order(c.main, sp);
         emb_pack = side_packs(c, sp);
         c.s = sp;
     } else {
-        LAUNCH("pack", launch_pack(c.io->params, c.W(p.pack), h->jobs_dev + head, nj - head, c.s));
+        pack_jobs(c, head, nj - head);
     }
     // the per-query clip mask, beside the query branch; first read by the CQ kernels, behind the join with its stream
     LAUNCH("vmask_gather", launch_vmask_gather(vmask_nt, ctx.vidx, c.W(p.vmask), p.B, p.T, c.s));
@@ -400,7 +404,7 @@ static void pairs_pack_and_mask(Ctx& c, CqContext ctx, const float* vmask_nt) {
     // the per-pair clip mask, beside the pack; first read by the CQ kernels, behind the join with its stream
     LAUNCH("vmask_gather", launch_vmask_gather(vmask_nt, ctx.vidx, c.W(p.vmask), p.B, p.T, c.s));
     c.s = c.main;
-    LAUNCH("pack", launch_pack(c.io->params, c.W(p.pack), h->jobs_dev + rest, nj - rest, c.s));
+    pack_jobs(c, rest, nj - rest);
     if (split) c.order(sp, c.main);
 }
 

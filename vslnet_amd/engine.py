@@ -6,53 +6,13 @@ if the shared library is missing or no MI355X is visible, construction raises.
 """
 import ctypes as C
 import os
-from collections import namedtuple
-from types import SimpleNamespace
 
 import torch
 
-from . import build as _build
-
-_LIB = None
-
-
-class vsl_config(C.Structure):
-    _fields_ = [('dim', C.c_int32), ('num_heads', C.c_int32), ('max_pos_len', C.c_int32),
-                ('video_feature_dim', C.c_int32), ('word_dim', C.c_int32), ('char_dim', C.c_int32),
-                ('word_size', C.c_int32), ('char_size', C.c_int32), ('predictor', C.c_int32), ('drop_rate', C.c_float),
-                ('word_table', C.c_int32)]
-
-
-class vsl_io(C.Structure):
-    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('Lq', C.c_int32), ('Lc', C.c_int32),
-                ('params', C.c_void_p), ('pad_vec', C.c_void_p), ('glove_vec', C.c_void_p),
-                ('word_ids', C.c_void_p), ('char_ids', C.c_void_p), ('video_features', C.c_void_p),
-                ('v_mask', C.c_void_p), ('q_mask', C.c_void_p),
-                ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p),
-                ('workspace', C.c_void_p), ('training', C.c_int32), ('seed', C.c_uint64),
-                ('d_h_score', C.c_void_p), ('d_start_logits', C.c_void_p), ('d_end_logits', C.c_void_p),
-                ('grads', C.c_void_p), ('sample_offset', C.c_int32), ('video_features_bf16', C.c_void_p),
-                ('early_grads_event', C.c_void_p),
-                ('fused_step', C.c_void_p),        # (NULL unless Engine.backward(fused_step=...): an older build loaded for an A/B run reads zeros here)
-                ('fused_loss', C.c_void_p),        # (NULL unless the last loss() was lazy=True)
-                ('inference', C.c_int32)]          # (1: Engine.forward(inference=True); an older build loaded for an A/B run never reads it)
-
-
-class vsl_encode_io(C.Structure):
-    _fields_ = [('N', C.c_int32), ('T', C.c_int32), ('params', C.c_void_p), ('video_features', C.c_void_p), ('video_features_bf16', C.c_void_p),
-                ('v_mask', C.c_void_p), ('video_encoding', C.c_void_p), ('workspace', C.c_void_p)]
-
-
-class vsl_localize_io(C.Structure):
-    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('Lq', C.c_int32), ('Lc', C.c_int32), ('N', C.c_int32),
-                ('params', C.c_void_p), ('pad_vec', C.c_void_p), ('glove_vec', C.c_void_p),
-                ('word_ids', C.c_void_p), ('char_ids', C.c_void_p), ('q_mask', C.c_void_p),
-                ('video_encoding', C.c_void_p), ('v_mask', C.c_void_p), ('video_index', C.c_void_p),
-                ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('workspace', C.c_void_p)]
-
-
-class vsl_shared_io(C.Structure):
-    _fields_ = [('N', C.c_int32), ('video_index', C.c_void_p), ('video_v_mask', C.c_void_p)]
+from .abi import (ABI_SYMBOLS, ABI_VERSION, FEATURES, PROTOTYPES, RELEVANCE, TOPM_MAX_M, CorpusMoments, LongMoments, TopkSpans, VideoRanks, VslError,  # noqa: F401
+                  WindowMoments, load_library, vsl_adamw, vsl_config, vsl_encode_io, vsl_encode_query_io, vsl_encode_windows_io, vsl_fused_step,
+                  vsl_group_loss_io, vsl_highlight_io, vsl_io, vsl_localize_io, vsl_loss_io, vsl_merge_io, vsl_merge_windows_io, vsl_pairs_io,
+                  vsl_select_io, vsl_shared_io, vsl_topk_io)
 
 
 class VideoEncoding:
@@ -67,34 +27,6 @@ class VideoEncoding:
         self.owner, self.epoch = owner, epoch
 
 
-class vsl_encode_query_io(C.Structure):
-    _fields_ = [('Q', C.c_int32), ('Lq', C.c_int32), ('Lc', C.c_int32), ('params', C.c_void_p), ('pad_vec', C.c_void_p), ('glove_vec', C.c_void_p),
-                ('word_ids', C.c_void_p), ('char_ids', C.c_void_p), ('q_mask', C.c_void_p), ('query_encoding', C.c_void_p), ('workspace', C.c_void_p)]
-
-
-class vsl_pairs_io(C.Structure):
-    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('Lq', C.c_int32), ('N', C.c_int32), ('Q', C.c_int32),
-                ('params', C.c_void_p), ('video_encoding', C.c_void_p), ('v_mask', C.c_void_p), ('query_encoding', C.c_void_p), ('q_mask', C.c_void_p),
-                ('video_index', C.c_void_p), ('query_index', C.c_void_p),
-                ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('workspace', C.c_void_p)]
-
-
-class vsl_highlight_io(C.Structure):
-    _fields_ = [('pairs', vsl_pairs_io), ('relevance', C.c_int32), ('ld', C.c_int32), ('out', C.c_void_p)]
-
-
-class vsl_select_io(C.Structure):
-    _fields_ = [('G', C.c_int32), ('N', C.c_int32), ('ld', C.c_int32), ('M', C.c_int32), ('key', C.c_void_p), ('out_index', C.c_void_p),
-                ('out_key', C.c_void_p), ('out_count', C.c_void_p)]
-
-
-# what Engine.select_topm / VSLNet.rank_videos return, per group (query): (G, m) int32 video (the index), fp32 relevance (the key), (G,) int32 count =
-# min(m, N); ranked: relevance descending, ties by the smaller index; slots from count[g] on hold -1, 0
-VideoRanks = namedtuple('VideoRanks', 'video relevance count')
-RELEVANCE = {'max': 0, 'mean': 1}                   # vsl_highlight_io.relevance
-TOPM_MAX_M = 1024                                   # vsl_select_topm: the largest M
-
-
 class QueryEncoding:
     """What Engine.encode_query returns: the shared feature encoder's output for Q queries padded to Lq words (embedded at Lc chars per word), and
     their word masks.  It belongs to its Lq and Lc and to the parameter values it was computed with (include/vslnet_hip.h).  `owner` / `epoch` are
@@ -105,71 +37,6 @@ class QueryEncoding:
         self.encoding, self.q_mask = encoding, q_mask
         self.Q, self.Lq, self.Lc = int(encoding.shape[0]), int(encoding.shape[1]), int(Lc)
         self.owner, self.epoch = owner, epoch
-
-
-class vsl_loss_io(C.Structure):
-    _fields_ = [('start_labels', C.c_void_p), ('end_labels', C.c_void_p), ('h_labels', C.c_void_p),
-                ('w_loc', C.c_float), ('w_highlight', C.c_float), ('inv_batch', C.c_float), ('mask_sum', C.c_float),
-                ('losses', C.c_void_p), ('d_h_score', C.c_void_p), ('d_start_logits', C.c_void_p),
-                ('d_end_logits', C.c_void_p)]
-
-
-class vsl_group_loss_io(C.Structure):
-    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('G', C.c_int32),
-                ('h_score', C.c_void_p), ('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('v_mask', C.c_void_p),
-                ('start_labels', C.c_void_p), ('end_labels', C.c_void_p), ('h_labels', C.c_void_p),
-                ('group_start', C.c_void_p), ('positive', C.c_void_p),
-                ('w_loc', C.c_float), ('w_highlight', C.c_float), ('w_rank', C.c_float), ('inv_pos', C.c_float), ('inv_groups', C.c_float),
-                ('mask_sum', C.c_float), ('inv_temperature', C.c_float), ('relevance', C.c_int32),
-                ('losses', C.c_void_p), ('hits', C.c_void_p), ('pair_relevance', C.c_void_p),
-                ('d_h_score', C.c_void_p), ('d_start_logits', C.c_void_p), ('d_end_logits', C.c_void_p), ('scratch', C.c_void_p)]
-
-
-class vsl_adamw(C.Structure):
-    _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('weight_decay', C.c_float),
-                ('clip_norm', C.c_float), ('step', C.c_int32), ('hf_order', C.c_int32), ('norm_from_backward', C.c_int32)]
-
-
-class vsl_fused_step(C.Structure):
-    _fields_ = [('params', C.c_void_p), ('exp_avg', C.c_void_p), ('exp_avg_sq', C.c_void_p), ('hp', vsl_adamw), ('grad_norm_out', C.c_void_p)]
-
-
-class vsl_topk_io(C.Structure):
-    _fields_ = [('start_logits', C.c_void_p), ('end_logits', C.c_void_p), ('valid_len', C.c_void_p),
-                ('B', C.c_int), ('T', C.c_int), ('K', C.c_int), ('nms_iou', C.c_float), ('max_span', C.c_int),
-                ('start_index', C.c_void_p), ('end_index', C.c_void_p), ('score', C.c_void_p), ('prob', C.c_void_p), ('count', C.c_void_p)]
-
-
-# what Engine.extract_topk returns: (B, K) int64 start / end, (B, K) fp32 score (the logit sum) and prob (None without want_prob), (B,) int32 count;
-# slots from count[b] on hold -1, -1, -inf, 0
-TopkSpans = namedtuple('TopkSpans', 'start end score prob count')
-
-
-class vsl_merge_io(C.Structure):
-    _fields_ = [('B', C.c_int), ('K', C.c_int), ('G', C.c_int), ('K_out', C.c_int),
-                ('start', C.c_void_p), ('end', C.c_void_p), ('score', C.c_void_p), ('key', C.c_void_p), ('count', C.c_void_p),
-                ('group_index', C.c_void_p), ('tag', C.c_void_p), ('tag_per_slot', C.c_int32),
-                ('out_tag', C.c_void_p), ('out_list', C.c_void_p), ('out_start', C.c_void_p), ('out_end', C.c_void_p),
-                ('out_score', C.c_void_p), ('out_key', C.c_void_p), ('out_count', C.c_void_p)]
-
-
-# what Engine.merge_topk returns, per group: (G, k_out) int32 tag and list (the input list a slot came from), int64 start / end, fp32 score and prob
-# (the ranking key), (G,) int32 count; slots from count[g] on hold -1, -1, -1, -1, -inf, 0
-CorpusMoments = namedtuple('CorpusMoments', 'tag list start end score prob count')
-
-
-class vsl_encode_windows_io(C.Structure):
-    _fields_ = [('rows', C.c_int32), ('N', C.c_int32), ('T', C.c_int32), ('params', C.c_void_p), ('video_features', C.c_void_p),
-                ('video_features_bf16', C.c_void_p), ('window_row', C.c_void_p), ('window_len', C.c_void_p), ('video_encoding', C.c_void_p),
-                ('v_mask', C.c_void_p), ('workspace', C.c_void_p)]
-
-
-class vsl_merge_windows_io(C.Structure):
-    _fields_ = [('B', C.c_int), ('K', C.c_int), ('G', C.c_int), ('K_out', C.c_int), ('nms_iou', C.c_float),
-                ('start', C.c_void_p), ('end', C.c_void_p), ('score', C.c_void_p), ('key', C.c_void_p), ('count', C.c_void_p),
-                ('group_index', C.c_void_p), ('offset', C.c_void_p),
-                ('out_list', C.c_void_p), ('out_start', C.c_void_p), ('out_end', C.c_void_p), ('out_score', C.c_void_p), ('out_key', C.c_void_p),
-                ('out_count', C.c_void_p)]
 
 
 class WindowEncoding(VideoEncoding):
@@ -183,124 +50,6 @@ class WindowEncoding(VideoEncoding):
         super().__init__(encoding, v_mask, owner=owner, epoch=epoch)
         self.video_of_window, self.offset_of_window, self.window_len = video_of_window, offset_of_window, window_len
         self.lengths, self.first_window, self.window, self.stride = lengths, first_window, int(window), int(stride)
-
-
-# what Engine.merge_windows returns, per group: (G, k_out) int32 list (the input list a slot came from), int64 start / end in the video's own clips,
-# fp32 score and prob (the ranking key), (G,) int32 count; slots from count[g] on hold -1, -1, -1, -inf, 0
-WindowMoments = namedtuple('WindowMoments', 'list start end score prob count')
-# what VSLNet.localize_long returns, per (video, query) pair: the same with `window` (the row of the WindowEncoding a moment came from) in place of `list`
-LongMoments = namedtuple('LongMoments', 'window start end score prob count')
-
-
-class VslError(RuntimeError):
-    pass
-
-
-ABI_SYMBOLS = ['vsl_last_error', 'vsl_create', 'vsl_destroy', 'vsl_param_count', 'vsl_param_info', 'vsl_param_floats',
-               'vsl_workspace_floats', 'vsl_forward', 'vsl_loss', 'vsl_backward', 'vsl_extract_index',
-               'vsl_adamw_step', 'vsl_workspace_offset', 'vsl_profile_select', 'vsl_profile_read', 'vsl_profile_launch', 'vsl_abi_version',
-               'vsl_early_grad_offset', 'vsl_debug_rnn_launches', 'vsl_inference_workspace_floats',
-               'vsl_encode_workspace_floats', 'vsl_encode_video', 'vsl_localize_workspace_floats', 'vsl_localize',
-               'vsl_shared_workspace_floats', 'vsl_forward_shared', 'vsl_backward_shared', 'vsl_shared_workspace_offset',
-               'vsl_backward_accumulate', 'vsl_extract_topk', 'vsl_input_grads', 'vsl_merge_topk',
-               'vsl_encode_query_workspace_floats', 'vsl_encode_query', 'vsl_pairs_workspace_floats', 'vsl_localize_pairs',
-               'vsl_encode_windows_workspace_floats', 'vsl_encode_windows', 'vsl_merge_windows',
-               'vsl_highlight_pairs', 'vsl_select_topm', 'vsl_group_loss', 'vsl_group_loss_scratch_floats']
-ABI_VERSION = 9                                     # include/vslnet_hip.h: VSL_ABI_VERSION
-
-
-def load_library():
-    """dlopen libvslnet_hip.so (building it in-tree with hipcc when stale/missing).  Raises if that fails."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    path = os.environ.get('VSLNET_HIP_LIB')        # A/B runs: an alternative build of the same ABI
-    if not path:
-        path = _build.LIB
-        if not os.path.exists(path) or _build._stale():
-            # several ranks of one node may get here together (torch.distributed.run): one builds, the others wait for it
-            import fcntl
-            os.makedirs(_build.LIBDIR, exist_ok=True)
-            with open(os.path.join(_build.LIBDIR, '.build.lock'), 'w') as lock:
-                fcntl.flock(lock, fcntl.LOCK_EX)
-                try:
-                    if not os.path.exists(path) or _build._stale():
-                        path = _build.build()
-                finally:
-                    fcntl.flock(lock, fcntl.LOCK_UN)
-    lib = C.CDLL(path)
-    explicit = bool(os.environ.get('VSLNET_HIP_LIB'))     # an A/B baseline built from an older revision (tools/build_base.py) may predate the check:
-    #                                                       new vsl_io fields are appended, so an older library simply does not read them
-    if not explicit and (not hasattr(lib, 'vsl_abi_version') or lib.vsl_abi_version() != ABI_VERSION):
-        raise VslError('%s implements another ABI version than this binding (%d): rebuild it (python -m vslnet_amd.build --force)' % (path, ABI_VERSION))
-    if hasattr(lib, 'vsl_debug_rnn_launches'):
-        lib.vsl_debug_rnn_launches.argtypes = [C.c_uint64]
-        lib.vsl_debug_rnn_launches.restype = C.c_uint64
-    if hasattr(lib, 'vsl_early_grad_offset'):
-        lib.vsl_early_grad_offset.argtypes = [C.c_void_p]
-        lib.vsl_early_grad_offset.restype = C.c_int64
-    lib.vsl_last_error.restype = C.c_char_p
-    lib.vsl_create.argtypes = [C.POINTER(vsl_config), C.POINTER(C.c_void_p)]
-    lib.vsl_destroy.argtypes = [C.c_void_p]
-    lib.vsl_param_count.argtypes = [C.c_void_p]
-    lib.vsl_param_floats.argtypes = [C.c_void_p]
-    lib.vsl_param_floats.restype = C.c_int64
-    lib.vsl_param_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
-                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    lib.vsl_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    if hasattr(lib, 'vsl_inference_workspace_floats'):       # (absent from an older build loaded through VSLNET_HIP_LIB for an A/B run)
-        lib.vsl_inference_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    if hasattr(lib, 'vsl_localize'):                         # (likewise: one encoding per video, many queries)
-        lib.vsl_encode_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-        lib.vsl_localize_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-        lib.vsl_encode_video.argtypes = [C.c_void_p, C.POINTER(vsl_encode_io), C.c_void_p]
-        lib.vsl_localize.argtypes = [C.c_void_p, C.POINTER(vsl_localize_io), C.c_void_p]
-    if hasattr(lib, 'vsl_forward_shared'):                   # (likewise: training through a shared video encoding)
-        lib.vsl_shared_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-        lib.vsl_forward_shared.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
-        lib.vsl_backward_shared.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
-        lib.vsl_shared_workspace_offset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
-        lib.vsl_shared_workspace_offset.restype = C.c_int64
-    if hasattr(lib, 'vsl_backward_accumulate'):              # (likewise: gradient accumulation)
-        lib.vsl_backward_accumulate.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p]
-    if hasattr(lib, 'vsl_extract_topk'):                     # (likewise: top-K spans with temporal NMS)
-        lib.vsl_extract_topk.argtypes = [C.c_void_p, C.POINTER(vsl_topk_io), C.c_void_p]
-    if hasattr(lib, 'vsl_encode_query'):                     # (likewise: one encoding per query)
-        lib.vsl_encode_query_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-        lib.vsl_encode_query.argtypes = [C.c_void_p, C.POINTER(vsl_encode_query_io), C.c_void_p]
-    if hasattr(lib, 'vsl_localize_pairs'):                   # (likewise: pairs of resident encodings)
-        lib.vsl_pairs_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-        lib.vsl_localize_pairs.argtypes = [C.c_void_p, C.POINTER(vsl_pairs_io), C.c_void_p]
-    if hasattr(lib, 'vsl_merge_topk'):                       # (likewise: the merge of top-K lists per group)
-        lib.vsl_merge_topk.argtypes = [C.c_void_p, C.POINTER(vsl_merge_io), C.c_void_p]
-    if hasattr(lib, 'vsl_encode_windows'):                   # (likewise: sliding windows over a long video)
-        lib.vsl_encode_windows_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-        lib.vsl_encode_windows.argtypes = [C.c_void_p, C.POINTER(vsl_encode_windows_io), C.c_void_p]
-    if hasattr(lib, 'vsl_merge_windows'):                    # (likewise: the cross-window merge)
-        lib.vsl_merge_windows.argtypes = [C.c_void_p, C.POINTER(vsl_merge_windows_io), C.c_void_p]
-    if hasattr(lib, 'vsl_highlight_pairs'):                  # (likewise: the coarse half of a corpus search)
-        lib.vsl_highlight_pairs.argtypes = [C.c_void_p, C.POINTER(vsl_highlight_io), C.c_void_p]
-    if hasattr(lib, 'vsl_select_topm'):
-        lib.vsl_select_topm.argtypes = [C.c_void_p, C.POINTER(vsl_select_io), C.c_void_p]
-    if hasattr(lib, 'vsl_group_loss'):                       # (likewise: the video ranking loss)
-        lib.vsl_group_loss_scratch_floats.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int64)]
-        lib.vsl_group_loss.argtypes = [C.c_void_p, C.POINTER(vsl_group_loss_io), C.c_void_p]
-    if hasattr(lib, 'vsl_input_grads'):                      # (likewise: the gradient with respect to the video features)
-        lib.vsl_input_grads.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_shared_io), C.c_void_p, C.c_void_p]
-    lib.vsl_forward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
-    lib.vsl_loss.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.POINTER(vsl_loss_io), C.c_void_p]
-    lib.vsl_backward.argtypes = [C.c_void_p, C.POINTER(vsl_io), C.c_void_p]
-    lib.vsl_extract_index.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.vsl_adamw_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(vsl_adamw), C.c_void_p, C.c_void_p]
-    lib.vsl_workspace_offset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
-    lib.vsl_workspace_offset.restype = C.c_int64
-    lib.vsl_profile_select.argtypes = [C.c_void_p, C.c_char_p]
-    lib.vsl_profile_read.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    if hasattr(lib, 'vsl_profile_launch'):       # (absent from an older build loaded through VSLNET_HIP_LIB for an A/B run)
-        lib.vsl_profile_launch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                           C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    _LIB = lib
-    return lib
 
 
 def _ptr(t):
@@ -346,8 +95,16 @@ def check_hw_queues():
         warnings.warn('vslnet_amd: ' + msg + ' -- continuing (%s)' % ('VSL_ALLOW_FEW_HW_QUEUES=1' if rccl_multi else 'no multi-rank RCCL group: nothing to lose'))
 
 
+def _c_int(who, **values):
+    """(ctypes would wrap them: max_span = 2 ** 32 must not arrive as 0 = unlimited; the library checks the ranges)"""
+    for name, v in values.items():
+        if not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError('%s: %s=%d is not a C int' % (who, name, v))
+
+
 class Engine:
     """One `vsl_handle` + caller-owned buffers.  Mirrors what VSLNet.__init__ / forward / backward need."""
+    h = None                                                # (until vsl_create has succeeded: what __del__ of a half-built engine finds)
 
     def __init__(self, configs, device=None, word_table=None):
         """`word_table=True` (or configs.word_table): WordEmbedding(word_vectors=None), the trainable nn.Embedding branch
@@ -359,35 +116,10 @@ class Engine:
         self.lib = load_library()
         # vsl_io.fused_loss / fused_step (ABI 8): an older build loaded through VSLNET_HIP_LIB for an A/B run takes the separate calls instead
         self.has_fused_io = hasattr(self.lib, 'vsl_abi_version') and self.lib.vsl_abi_version() >= 8
-        # vsl_io.inference (ABI 9): an older build has no forward-only plan; forward(inference=True) then raises and the module's no_grad path
-        # keeps the saved path.  `use_inference = False` forces that on a current build too (A/B runs, tests)
-        self.has_inference = hasattr(self.lib, 'vsl_inference_workspace_floats')
-        self.use_inference = True
-        # vsl_encode_video / vsl_localize: one encoding per video, many queries against it.  An older build has neither; both methods then raise
-        self.has_shared_video = hasattr(self.lib, 'vsl_encode_video') and hasattr(self.lib, 'vsl_localize')
-        # vsl_forward_shared / vsl_backward_shared: a training step over N videos and B queries.  An older build has neither; forward_shared then raises
-        self.has_shared_train = hasattr(self.lib, 'vsl_forward_shared') and hasattr(self.lib, 'vsl_backward_shared')
-        # vsl_backward_accumulate: a backward that adds to the gradient bucket (one optimizer step over K micro-batches).  An older build lacks it;
-        # backward(accumulate=True) then raises
-        self.has_grad_accumulation = hasattr(self.lib, 'vsl_backward_accumulate')
-        # vsl_extract_topk: the K best spans per sample with temporal NMS.  An older build lacks it; extract_topk then raises
-        self.has_topk = hasattr(self.lib, 'vsl_extract_topk')
-        # vsl_input_grads: the gradient with respect to the video features, one launch behind a backward.  An older build lacks it; input_grads then raises
-        self.has_input_grads = hasattr(self.lib, 'vsl_input_grads')
-        # vsl_merge_topk: the k_out best moments of every group of top-K lists (a search over several videos).  An older build lacks it; merge_topk then raises
-        self.has_merge_topk = hasattr(self.lib, 'vsl_merge_topk')
-        # vsl_encode_query: the query half of the inference forward, once per query.  An older build lacks it; encode_query then raises
-        # ... and vsl_localize_pairs, which reads it: both or neither
-        self.has_query_encoding = all(hasattr(self.lib, s) for s in ('vsl_encode_query', 'vsl_encode_query_workspace_floats', 'vsl_localize_pairs',
-                                                                     'vsl_pairs_workspace_floats'))
-        # vsl_encode_windows / vsl_merge_windows: sliding windows over a video of any length.  An older build has neither; encode_windows and
-        # merge_windows then raise
-        self.has_windows = all(hasattr(self.lib, s) for s in ('vsl_encode_windows', 'vsl_encode_windows_workspace_floats', 'vsl_merge_windows'))
-        # vsl_highlight_pairs / vsl_select_topm: rank the videos of a corpus by highlight score.  An older build has neither; highlight_pairs and
-        # select_topm then raise (and VSLNet.retrieve serves prefilter=0 only)
-        self.has_video_ranking = all(hasattr(self.lib, s) for s in ('vsl_highlight_pairs', 'vsl_select_topm'))
-        # vsl_group_loss: the span / highlight losses over groups of pair rows + the video ranking term.  An older build lacks it; group_loss then raises
-        self.has_group_loss = all(hasattr(self.lib, s) for s in ('vsl_group_loss', 'vsl_group_loss_scratch_floats'))
+        # has_inference, has_shared_video, ...: what an older build lacks, the methods that need it refuse (_need).  Plain attributes: tests clear them
+        for flag, (symbols, _) in FEATURES.items():
+            setattr(self, 'has_' + flag, all(hasattr(self.lib, s) for s in symbols))
+        self.use_inference = True                           # `False` keeps the module's no_grad path on the saved path on a current build too (A/B runs, tests)
         self._group_scratch = {}                        # (B, G) -> the call's scratch
         self.inference_forwards = 0                          # inference forwards issued so far (tests, tools/infer_rate.py)
         pred = {'rnn': 0, 'transformer': 1}.get(configs.predictor)
@@ -416,14 +148,16 @@ class Engine:
         for i in range(self.lib.vsl_param_count(h)):
             self._call(self.lib.vsl_param_info(h, i, name, 256, C.byref(off), C.byref(num), C.byref(nd), dims))
             self.layout.append((name.value.decode(), off.value, num.value, tuple(dims[j] for j in range(nd.value))))
-        self._ws, self._grown = None, False
-        self._last = None
+        self._ws, self._grown = None, False                 # the one shared workspace (workspace())
+        self._last = None                                   # the vsl_io of the last forward (a marker with inference = 1 behind a call that saved nothing)
+        self._last_ws = None                                # the workspace it ran in (None where nothing was saved)
         self._last_shared = None                            # the vsl_shared_io of the last forward when that was forward_shared (loss / backward / ws_view dispatch on it)
-        self._pending_loss = None
+        self._keep = None                                   # every tensor the last call's io points to, alive until the backward
+        self._pending_loss = None                           # a lazy loss(): (vsl_loss_io, the forward's vsl_io, its tensors)
 
     def __del__(self):
         try:
-            if getattr(self, 'h', None):
+            if self.h:
                 self.lib.vsl_destroy(self.h)
         except Exception:
             pass
@@ -435,6 +169,14 @@ class Engine:
                 raise IndexError(msg)                       # the reference raises IndexError from nn.Embedding here
             raise VslError(msg)
 
+    def _need(self, flag):
+        """The refusal of a method whose entry points the loaded library lacks (abi.FEATURES)."""
+        if not getattr(self, 'has_' + flag):
+            raise VslError(FEATURES[flag][1])
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
     # ---- flat parameter bucket helpers -------------------------------------------------------------------
     def new_flat(self):
         return torch.zeros(self.param_floats, dtype=torch.float32, device=self.device)
@@ -442,53 +184,52 @@ class Engine:
     def views(self, flat):
         return {n: flat[o:o + k].view(shp) for n, o, k, shp in self.layout}
 
-    def inference_workspace_floats(self, B, T, Lq, Lc):
-        """Floats an inference forward of this shape needs (the forward-only plan; vslnet_hip.h)."""
-        if not self.has_inference:
-            raise VslError('the loaded library has no inference mode (vsl_inference_workspace_floats is missing)')
+    # ---- the workspace: floats per shape and call, one buffer ----------------------------------------------
+    def _floats(self, query, *shape):
+        """What the library's `query` (one of its *_workspace_floats) answers for this shape."""
         n = C.c_int64()
         with torch.cuda.device(self.device):
-            self._call(self.lib.vsl_inference_workspace_floats(self.h, B, T, Lq, Lc, C.byref(n)))
+            self._call(query(self.h, *shape, C.byref(n)))
         return int(n.value)
+
+    def inference_workspace_floats(self, B, T, Lq, Lc):
+        """Floats an inference forward of this shape needs (the forward-only plan; vslnet_hip.h)."""
+        self._need('inference')
+        return self._floats(self.lib.vsl_inference_workspace_floats, B, T, Lq, Lc)
 
     def workspace_floats(self, B, T, Lq, Lc):
         """Floats a training (or saved-path evaluation) forward + backward of this shape needs."""
-        n = C.c_int64()
-        with torch.cuda.device(self.device):
-            self._call(self.lib.vsl_workspace_floats(self.h, B, T, Lq, Lc, C.byref(n)))
-        return int(n.value)
-
-    def _need_shared_video(self):
-        if not self.has_shared_video:
-            raise VslError('the loaded library has no shared-video entry points (vsl_encode_video / vsl_localize are missing)')
+        return self._floats(self.lib.vsl_workspace_floats, B, T, Lq, Lc)
 
     def encode_workspace_floats(self, N, T):
         """Floats an encode_video call of N videos padded to T clips needs (operand packs + one encoder application's scratch)."""
-        self._need_shared_video()
-        n = C.c_int64()
-        with torch.cuda.device(self.device):
-            self._call(self.lib.vsl_encode_workspace_floats(self.h, N, T, C.byref(n)))
-        return int(n.value)
+        self._need('shared_video')
+        return self._floats(self.lib.vsl_encode_workspace_floats, N, T)
 
     def localize_workspace_floats(self, B, T, Lq, Lc):
         """Floats a localize call of this shape needs (the inference plan without a video pass + the (B, T) gathered mask)."""
-        self._need_shared_video()
-        n = C.c_int64()
-        with torch.cuda.device(self.device):
-            self._call(self.lib.vsl_localize_workspace_floats(self.h, B, T, Lq, Lc, C.byref(n)))
-        return int(n.value)
+        self._need('shared_video')
+        return self._floats(self.lib.vsl_localize_workspace_floats, B, T, Lq, Lc)
 
     def shared_workspace_floats(self, B, N, T, Lq, Lc):
         """Floats a shared training step of B queries over N videos needs (the training plan with the video half sized by N, + dCv and the grouping)."""
-        self._need_shared_train()
-        n = C.c_int64()
-        with torch.cuda.device(self.device):
-            self._call(self.lib.vsl_shared_workspace_floats(self.h, B, N, T, Lq, Lc, C.byref(n)))
-        return int(n.value)
+        self._need('shared_train')
+        return self._floats(self.lib.vsl_shared_workspace_floats, B, N, T, Lq, Lc)
 
-    def _need_shared_train(self):
-        if not self.has_shared_train:
-            raise VslError('the loaded library has no shared-encoding training step (vsl_forward_shared / vsl_backward_shared are missing)')
+    def encode_windows_workspace_floats(self, N, T, rows):
+        """Floats an encode_windows call of N windows of T clips over `rows` feature rows needs (the encode plan of (N, T) + rows * 128)."""
+        self._need('windows')
+        return self._floats(self.lib.vsl_encode_windows_workspace_floats, int(N), int(T), int(rows))
+
+    def encode_query_workspace_floats(self, Q, Lq, Lc):
+        """Floats an encode_query call of Q queries padded to Lq words of Lc chars needs (operand packs + the query branch's scratch)."""
+        self._need('query_encoding')
+        return self._floats(self.lib.vsl_encode_query_workspace_floats, Q, Lq, Lc)
+
+    def pairs_workspace_floats(self, B, T, Lq):
+        """Floats a localize_pairs call of this shape needs (the localize plan without the query branch's scratch)."""
+        self._need('query_encoding')
+        return self._floats(self.lib.vsl_pairs_workspace_floats, B, T, Lq)
 
     def _grow_ws(self, n):
         """The one shared workspace (see workspace()), grown to at least `n` floats."""
@@ -507,10 +248,7 @@ class Engine:
         visits hundreds of shapes -- a workspace per shape would grow without bound beside the HBM-resident dataset.
         Inference forwards share it: their plan is a fraction of the training plan of the same shape, so they only ever grow it for a
         shape training has not seen."""
-        n = C.c_int64()
-        with torch.cuda.device(self.device):
-            self._call((self.lib.vsl_inference_workspace_floats if inference else self.lib.vsl_workspace_floats)(self.h, B, T, Lq, Lc, C.byref(n)))
-        return self._grow_ws(n.value)
+        return self._grow_ws(self._floats(self.lib.vsl_inference_workspace_floats if inference else self.lib.vsl_workspace_floats, B, T, Lq, Lc))
 
     def ws_view(self, name, shape):
         """Saved activation `name` of the LAST forward as a tensor view (parity tests)."""
@@ -528,7 +266,75 @@ class Engine:
             n *= s
         return self._last_ws[off:off + n].view(shape)
 
+    # ---- the checks the calls share: each returns what its caller hands to the library -----------------------
+    def _check_query(self, B, Lq, Lc, word_ids, char_ids, q_mask, pad_vec, glove_vec):
+        """The query side of a call -> the (pad_vec, glove_vec) it uses."""
+        _chk(word_ids, torch.int64, (B, Lq), 'word_ids')
+        _chk(char_ids, torch.int64, (B, Lq, Lc), 'char_ids')
+        _chk(q_mask, torch.float32, (B, Lq), 'q_mask')
+        if self.cfg.word_table:
+            return None, None                           # rows 0, 1, 2.. of the trainable table inside `flat` stand in
+        _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
+        _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
+        return pad_vec, glove_vec
+
+    def _check_features(self, feats, rows):
+        """The video features of a call, `rows` + (video_feature_dim,) in fp32 or bf16 -> the (video_features, video_features_bf16) pointer pair."""
+        bf16 = feats.dtype == torch.bfloat16
+        _chk(feats, torch.bfloat16 if bf16 else torch.float32, tuple(rows) + (self.cfg.video_feature_dim,), 'video_features')
+        return (None, _ptr(feats)) if bf16 else (_ptr(feats), None)
+
+    def _index(self, who, index, n, name, holder):
+        """An index into a batch or an encoding of `n` entries: a device tensor is trusted (no synchronising read), anything else range-checked and
+        uploaded as int32."""
+        if isinstance(index, torch.Tensor) and index.is_cuda:
+            return index.to(torch.int32).contiguous()
+        host = torch.as_tensor(index).to(torch.int64).reshape(-1)
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n):
+            raise ValueError('%s: %s out of range: values in [%d, %d], %s' % (who, name, int(host.min()), int(host.max()), holder % n))
+        return host.to(torch.int32).to(self.device)
+
+    def _check_spans(self, who, spans, group_index, G, k_out):
+        """The TopkSpans of B lists a merge reads and their groups -> (B, K, G, k_out)."""
+        if spans.prob is None:
+            raise ValueError('%s: the spans carry no prob to rank by (extract_topk(want_prob=True))' % who)
+        B, K = spans.start.shape
+        G, k_out = int(G), int(k_out)
+        _c_int(who, G=G, k_out=k_out)
+        _chk(spans.start, torch.int64, (B, K), 'spans.start')
+        _chk(spans.end, torch.int64, (B, K), 'spans.end')
+        _chk(spans.score, torch.float32, (B, K), 'spans.score')
+        _chk(spans.prob, torch.float32, (B, K), 'spans.prob')
+        _chk(spans.count, torch.int32, (B,), 'spans.count')
+        _chk(group_index, torch.int32, (B,), 'group_index')
+        return B, K, G, k_out
+
+    def _check_scores(self, scores, start_logits, end_logits, v_mask):
+        """Explicit outputs handed to loss() / group_loss() in place of the last forward's -> (B, T, their four pointers)."""
+        B, T = scores.shape
+        for t, nm in ((scores, 'scores'), (start_logits, 'start_logits'), (end_logits, 'end_logits'), (v_mask, 'mask')):
+            _chk(t, torch.float32, (B, T), nm)
+        return B, T, (_ptr(scores), _ptr(start_logits), _ptr(end_logits), _ptr(v_mask))
+
+    def _out3(self, B, T):
+        """(3, B, T): h_score / start_logits / end_logits of a forward, or their three gradient seeds."""
+        return torch.empty(3, B, T, dtype=torch.float32, device=self.device)
+
     # ---- the three calls ------------------------------------------------------------------------------------
+    def _train_io(self, flat, pad_vec, glove_vec, word_ids, char_ids, feats, v_mask, q_mask, out, ws, training, seed):
+        """The vsl_io of forward() / forward_shared() over checked arguments (`feats`: _check_features' pointer pair)."""
+        io = vsl_io()
+        io.B, io.T = out.shape[1:]
+        io.Lq, io.Lc = char_ids.shape[1:]
+        io.params, io.pad_vec, io.glove_vec = _ptr(flat), _ptr(pad_vec), _ptr(glove_vec)
+        io.word_ids, io.char_ids = _ptr(word_ids), _ptr(char_ids)
+        io.video_features, io.video_features_bf16 = feats
+        io.v_mask, io.q_mask = _ptr(v_mask), _ptr(q_mask)
+        io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
+        io.workspace = _ptr(ws)
+        io.training, io.seed = int(bool(training)), int(seed) & 0xFFFFFFFFFFFFFFFF
+        return io
+
     def forward(self, flat, pad_vec, glove_vec, word_ids, char_ids, vfeats, v_mask, q_mask, training=False, seed=0,
                 sample_offset=0, inference=False):
         """`inference=True`: a forward that will not be differentiated (vsl_io.inference): kernels that save nothing, the forward-only
@@ -541,37 +347,20 @@ class Engine:
         logit tolerance, and its measured ceiling -- every conv-block GEMM as one product too -- was 1.07 x; profiles/r05_notes.md section 9.)"""
         if inference and training:
             raise ValueError('inference=True and training=True exclude each other (the inference kernels have no dropout)')
-        if inference and not self.has_inference:
-            raise VslError('the loaded library has no inference mode (vsl_inference_workspace_floats is missing)')
+        if inference:
+            self._need('inference')
         B, T, Dv = vfeats.shape
-        bf16 = vfeats.dtype == torch.bfloat16
         Lq, Lc = char_ids.shape[1], char_ids.shape[2]
         _chk(flat, torch.float32, (self.param_floats,), 'params')
-        _chk(word_ids, torch.int64, (B, Lq), 'word_ids')
-        _chk(char_ids, torch.int64, (B, Lq, Lc), 'char_ids')
-        _chk(vfeats, torch.bfloat16 if bf16 else torch.float32, (B, T, self.cfg.video_feature_dim), 'video_features')
+        feats = self._check_features(vfeats, (B, T))
         _chk(v_mask, torch.float32, (B, T), 'v_mask')
-        _chk(q_mask, torch.float32, (B, Lq), 'q_mask')
-        if self.cfg.word_table:
-            pad_vec = glove_vec = None                  # rows 0, 1, 2.. of the trainable table inside `flat` stand in
-        else:
-            _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
-            _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
+        pad_vec, glove_vec = self._check_query(B, Lq, Lc, word_ids, char_ids, q_mask, pad_vec, glove_vec)
         self._flush_loss()                              # before anything touches the workspace: a pending lazy loss points into it (loss_scratch)
         ws = self.workspace(B, T, Lq, Lc, inference=inference)
-        out = torch.empty(3, B, T, dtype=torch.float32, device=self.device)
-        io = vsl_io()
-        io.B, io.T, io.Lq, io.Lc = B, T, Lq, Lc
-        io.params, io.pad_vec, io.glove_vec = _ptr(flat), _ptr(pad_vec), _ptr(glove_vec)
-        io.word_ids, io.char_ids = _ptr(word_ids), _ptr(char_ids)
-        io.video_features, io.video_features_bf16 = (None, _ptr(vfeats)) if bf16 else (_ptr(vfeats), None)
-        io.v_mask, io.q_mask = _ptr(v_mask), _ptr(q_mask)
-        io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
-        io.workspace = _ptr(ws)
-        io.training, io.seed, io.sample_offset = int(bool(training)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset)
-        io.inference = int(bool(inference))
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_forward(self.h, C.byref(io), stream))
+        out = self._out3(B, T)
+        io = self._train_io(flat, pad_vec, glove_vec, word_ids, char_ids, feats, v_mask, q_mask, out, ws, training, seed)
+        io.sample_offset, io.inference = int(sample_offset), int(bool(inference))
+        self._call(self.lib.vsl_forward(self.h, C.byref(io), self._stream()))
         self._last, self._last_ws, self._last_shared = io, ws, None      # (io.inference marks it: backward() and ws_view() raise on an inference forward)
         self.inference_forwards += int(bool(inference))
         # keep every tensor the io struct points to alive until the backward
@@ -587,56 +376,34 @@ class Engine:
         drop_rate 0 the step is the ordinary one on the replicated batch, otherwise a different but equally valid stochastic estimate.
         `video_v_mask` is the (N, T) per-video mask; the (B, T) per-query mask is built here.  `video_index` as a list / numpy array / CPU tensor
         is range-checked and uploaded as int32; a DEVICE tensor (int32 or int64) is trusted.  `training=False`: the saved evaluation path."""
-        self._need_shared_train()
+        self._need('shared_train')
         if video_features.dim() != 3 or video_features.shape[0] < 1:
             raise ValueError('forward_shared: video_features must be (N, T, video_feature_dim) with N >= 1 videos, got %s' % (tuple(video_features.shape),))
         N, T, Dv = video_features.shape
-        bf16 = video_features.dtype == torch.bfloat16
         B, Lq, Lc = char_ids.shape
-        if isinstance(video_index, torch.Tensor) and video_index.is_cuda:
-            vidx = video_index.to(torch.int32).contiguous()
-        else:
-            host = torch.as_tensor(video_index).to(torch.int64).reshape(-1)
-            if host.numel() and (int(host.min()) < 0 or int(host.max()) >= N):
-                raise ValueError('forward_shared: video_index out of range: values in [%d, %d], the batch holds %d videos' % (int(host.min()), int(host.max()), N))
-            vidx = host.to(torch.int32).to(self.device)
+        vidx = self._index('forward_shared', video_index, N, 'video_index', 'the batch holds %d videos')
         _chk(vidx, torch.int32, (B,), 'video_index')
         _chk(flat, torch.float32, (self.param_floats,), 'params')
-        _chk(word_ids, torch.int64, (B, Lq), 'word_ids')
-        _chk(char_ids, torch.int64, (B, Lq, Lc), 'char_ids')
-        _chk(video_features, torch.bfloat16 if bf16 else torch.float32, (N, T, self.cfg.video_feature_dim), 'video_features')
+        feats = self._check_features(video_features, (N, T))
         _chk(video_v_mask, torch.float32, (N, T), 'video_v_mask')
-        _chk(q_mask, torch.float32, (B, Lq), 'q_mask')
-        if self.cfg.word_table:
-            pad_vec = glove_vec = None
-        else:
-            _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
-            _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
+        pad_vec, glove_vec = self._check_query(B, Lq, Lc, word_ids, char_ids, q_mask, pad_vec, glove_vec)
         self._flush_loss()
         ws = self._grow_ws(self.shared_workspace_floats(B, N, T, Lq, Lc))
         v_mask = video_v_mask.index_select(0, vidx.long()).contiguous()       # the (B, T) per-query mask
-        out = torch.empty(3, B, T, dtype=torch.float32, device=self.device)
-        io = vsl_io()
-        io.B, io.T, io.Lq, io.Lc = B, T, Lq, Lc
-        io.params, io.pad_vec, io.glove_vec = _ptr(flat), _ptr(pad_vec), _ptr(glove_vec)
-        io.word_ids, io.char_ids = _ptr(word_ids), _ptr(char_ids)
-        io.video_features, io.video_features_bf16 = (None, _ptr(video_features)) if bf16 else (_ptr(video_features), None)
-        io.v_mask, io.q_mask = _ptr(v_mask), _ptr(q_mask)
-        io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
-        io.workspace = _ptr(ws)
-        io.training, io.seed = int(bool(training)), int(seed) & 0xFFFFFFFFFFFFFFFF
+        out = self._out3(B, T)
+        io = self._train_io(flat, pad_vec, glove_vec, word_ids, char_ids, feats, v_mask, q_mask, out, ws, training, seed)
         sh = vsl_shared_io()
         sh.N, sh.video_index, sh.video_v_mask = N, _ptr(vidx), _ptr(video_v_mask)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_forward_shared(self.h, C.byref(io), C.byref(sh), stream))
+        self._call(self.lib.vsl_forward_shared(self.h, C.byref(io), C.byref(sh), self._stream()))
         self._last, self._last_ws, self._last_shared = io, ws, sh
         self._keep = (flat, pad_vec, glove_vec, word_ids, char_ids, video_features, video_v_mask, v_mask, vidx, q_mask, out, ws)
         return out[0], out[1], out[2]
 
-    # ---- one encoding per video, many queries against it (evaluation only) ---------------------------------
-    def _no_saves(self, keep):
-        """encode_video / localize ran in the shared workspace: whatever an earlier training forward saved there is gone, so backward() and
-        ws_view() raise until the next saved-path forward (a marker in place of that forward's io, as after forward(inference=True))."""
+    # ---- evaluation only: resident encodings and what reads them ---------------------------------------------
+    def _eval_call(self, entry, io, keep):
+        """Issue an evaluation-only call.  It ran in the shared workspace: whatever an earlier training forward saved there is gone, so backward()
+        and ws_view() raise until the next saved-path forward (a marker in place of that forward's io, as after forward(inference=True))."""
+        self._call(entry(self.h, C.byref(io), self._stream()))
         mark = vsl_io()
         mark.inference = 1
         self._last, self._last_ws, self._keep, self._last_shared = mark, None, keep, None
@@ -645,13 +412,12 @@ class Engine:
         """VisualProjection + the video pass of the shared feature encoder for N videos, once: -> VideoEncoding (encoding (N, T, 128), v_mask (N, T)).
         No dropout, nothing saved.  `vfeats` in torch.bfloat16 selects the bf16 throughput mode, as in forward().  The encoding is the `venc`
         of forward() on these videos, bit for bit, and belongs to this T and to these parameter values."""
-        self._need_shared_video()
+        self._need('shared_video')
         if vfeats.dim() != 3 or vfeats.shape[0] < 1:
             raise ValueError('encode_video: video_features must be (N, T, video_feature_dim) with N >= 1 videos, got %s' % (tuple(vfeats.shape),))
         N, T, Dv = vfeats.shape
-        bf16 = vfeats.dtype == torch.bfloat16
         _chk(flat, torch.float32, (self.param_floats,), 'params')
-        _chk(vfeats, torch.bfloat16 if bf16 else torch.float32, (N, T, self.cfg.video_feature_dim), 'video_features')
+        feats = self._check_features(vfeats, (N, T))
         _chk(v_mask, torch.float32, (N, T), 'v_mask')
         self._flush_loss()
         ws = self._grow_ws(self.encode_workspace_floats(N, T))
@@ -659,25 +425,10 @@ class Engine:
         io = vsl_encode_io()
         io.N, io.T = N, T
         io.params = _ptr(flat)
-        io.video_features, io.video_features_bf16 = (None, _ptr(vfeats)) if bf16 else (_ptr(vfeats), None)
+        io.video_features, io.video_features_bf16 = feats
         io.v_mask, io.video_encoding, io.workspace = _ptr(v_mask), _ptr(enc), _ptr(ws)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_encode_video(self.h, C.byref(io), stream))
-        self._no_saves((flat, vfeats, v_mask, enc, ws))
+        self._eval_call(self.lib.vsl_encode_video, io, (flat, vfeats, v_mask, enc, ws))
         return VideoEncoding(enc, v_mask)
-
-    # ---- sliding windows over a video of any length (evaluation only) ---------------------------------------
-    def _need_windows(self):
-        if not self.has_windows:
-            raise VslError('the loaded library has no sliding windows (vsl_encode_windows / vsl_merge_windows are missing)')
-
-    def encode_windows_workspace_floats(self, N, T, rows):
-        """Floats an encode_windows call of N windows of T clips over `rows` feature rows needs (the encode plan of (N, T) + rows * 128)."""
-        self._need_windows()
-        n = C.c_int64()
-        with torch.cuda.device(self.device):
-            self._call(self.lib.vsl_encode_windows_workspace_floats(self.h, int(N), int(T), int(rows), C.byref(n)))
-        return int(n.value)
 
     def encode_windows(self, flat, feats, window_row, window_len, T, out=None, out_mask=None):
         """VisualProjection ONCE over the (rows, video_feature_dim) feature rows `feats`, then the video pass of the shared feature encoder over N
@@ -686,13 +437,12 @@ class Engine:
         encode_video on the materialised zero-padded windows, which are never built.  `window_row` / `window_len`: (N,) int32 DEVICE tensors; a row
         outside the features is treated as padding.  `feats` in torch.bfloat16 selects the bf16 throughput mode.  `out` / `out_mask`: contiguous
         fp32 cuda tensors of those shapes to write into (slices of a larger encoding)."""
-        self._need_windows()
+        self._need('windows')
         if feats.dim() != 2:
             raise ValueError('encode_windows: the features must be (rows, video_feature_dim), got %s' % (tuple(feats.shape),))
         rows, N, T = int(feats.shape[0]), int(window_row.numel()), int(T)
-        bf16 = feats.dtype == torch.bfloat16
         _chk(flat, torch.float32, (self.param_floats,), 'params')
-        _chk(feats, torch.bfloat16 if bf16 else torch.float32, (rows, self.cfg.video_feature_dim), 'video_features')
+        feat_ptrs = self._check_features(feats, (rows,))
         _chk(window_row, torch.int32, (N,), 'window_row')
         _chk(window_len, torch.int32, (N,), 'window_len')
         self._flush_loss()
@@ -704,12 +454,10 @@ class Engine:
         io = vsl_encode_windows_io()
         io.rows, io.N, io.T = rows, N, T
         io.params = _ptr(flat)
-        io.video_features, io.video_features_bf16 = (None, _ptr(feats)) if bf16 else (_ptr(feats), None)
+        io.video_features, io.video_features_bf16 = feat_ptrs
         io.window_row, io.window_len = _ptr(window_row), _ptr(window_len)
         io.video_encoding, io.v_mask, io.workspace = _ptr(enc), _ptr(mask), _ptr(ws)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_encode_windows(self.h, C.byref(io), stream))
-        self._no_saves((flat, feats, window_row, window_len, enc, mask, ws))
+        self._eval_call(self.lib.vsl_encode_windows, io, (flat, feats, window_row, window_len, enc, mask, ws))
         return VideoEncoding(enc, mask)
 
     def merge_windows(self, spans, group_index, G, k_out, offset=None, nms_iou=0.5):
@@ -718,20 +466,8 @@ class Engine:
         window-local indices (extract_topk(want_prob=True); the ranking key is its `prob`); `group_index` (B,) int32 on the device: the (query, video)
         pair of list b, a value outside [0, G) drops the list; `offset` (B,) int32 on the device: the first clip of list b's window (None: 0).  Two
         candidates at the same global span are reported once at every nms_iou."""
-        self._need_windows()
-        if spans.prob is None:
-            raise ValueError('merge_windows: the spans carry no prob to rank by (extract_topk(want_prob=True))')
-        B, K = spans.start.shape
-        G, k_out = int(G), int(k_out)
-        for name, v in (('G', G), ('k_out', k_out)):         # (ctypes would wrap them; the library checks the ranges)
-            if not -2 ** 31 <= v < 2 ** 31:
-                raise ValueError('merge_windows: %s=%d is not a C int' % (name, v))
-        _chk(spans.start, torch.int64, (B, K), 'spans.start')
-        _chk(spans.end, torch.int64, (B, K), 'spans.end')
-        _chk(spans.score, torch.float32, (B, K), 'spans.score')
-        _chk(spans.prob, torch.float32, (B, K), 'spans.prob')
-        _chk(spans.count, torch.int32, (B,), 'spans.count')
-        _chk(group_index, torch.int32, (B,), 'group_index')
+        self._need('windows')
+        B, K, G, k_out = self._check_spans('merge_windows', spans, group_index, G, k_out)
         if offset is not None:
             _chk(offset, torch.int32, (B,), 'offset')
         n = max(G, 0), max(k_out, 0)
@@ -742,39 +478,19 @@ class Engine:
         io = vsl_merge_windows_io(B, K, G, k_out, float(nms_iou), spans.start.data_ptr(), spans.end.data_ptr(), spans.score.data_ptr(),
                                   spans.prob.data_ptr(), spans.count.data_ptr(), group_index.data_ptr(), offset.data_ptr() if offset is not None else None,
                                   lst.data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(), f32[0].data_ptr(), f32[1].data_ptr(), count.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_merge_windows(self.h, C.byref(io), stream))
+        self._call(self.lib.vsl_merge_windows(self.h, C.byref(io), self._stream()))
         return WindowMoments(lst, i64[0], i64[1], f32[0], f32[1], count)
-
-    def _need_query_encoding(self):
-        if not self.has_query_encoding:
-            raise VslError('the loaded library has no query encodings (vsl_encode_query / vsl_localize_pairs are missing)')
-
-    def encode_query_workspace_floats(self, Q, Lq, Lc):
-        """Floats an encode_query call of Q queries padded to Lq words of Lc chars needs (operand packs + the query branch's scratch)."""
-        self._need_query_encoding()
-        n = C.c_int64()
-        with torch.cuda.device(self.device):
-            self._call(self.lib.vsl_encode_query_workspace_floats(self.h, Q, Lq, Lc, C.byref(n)))
-        return int(n.value)
 
     def encode_query(self, flat, pad_vec, glove_vec, word_ids, char_ids, q_mask):
         """The word + char embedding, the Embedding linear and the query pass of the shared feature encoder for Q queries, once: -> QueryEncoding
         (encoding (Q, Lq, 128), q_mask (Q, Lq)).  No dropout, nothing saved.  The encoding is the `qenc` of forward() on these queries, bit for bit,
         and belongs to this Lq / Lc and to these parameter values."""
-        self._need_query_encoding()
+        self._need('query_encoding')
         if char_ids.dim() != 3 or char_ids.shape[0] < 1:
             raise ValueError('encode_query: char_ids must be (Q, Lq, Lc) with Q >= 1 queries, got %s' % (tuple(char_ids.shape),))
         Q, Lq, Lc = char_ids.shape
         _chk(flat, torch.float32, (self.param_floats,), 'params')
-        _chk(word_ids, torch.int64, (Q, Lq), 'word_ids')
-        _chk(char_ids, torch.int64, (Q, Lq, Lc), 'char_ids')
-        _chk(q_mask, torch.float32, (Q, Lq), 'q_mask')
-        if self.cfg.word_table:
-            pad_vec = glove_vec = None
-        else:
-            _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
-            _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
+        pad_vec, glove_vec = self._check_query(Q, Lq, Lc, word_ids, char_ids, q_mask, pad_vec, glove_vec)
         self._flush_loss()
         ws = self._grow_ws(self.encode_query_workspace_floats(Q, Lq, Lc))
         enc = torch.empty(Q, Lq, 128, dtype=torch.float32, device=self.device)
@@ -783,27 +499,34 @@ class Engine:
         io.params, io.pad_vec, io.glove_vec = _ptr(flat), _ptr(pad_vec), _ptr(glove_vec)
         io.word_ids, io.char_ids, io.q_mask = _ptr(word_ids), _ptr(char_ids), _ptr(q_mask)
         io.query_encoding, io.workspace = _ptr(enc), _ptr(ws)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_encode_query(self.h, C.byref(io), stream))
-        self._no_saves((flat, pad_vec, glove_vec, word_ids, char_ids, q_mask, enc, ws))
+        self._eval_call(self.lib.vsl_encode_query, io, (flat, pad_vec, glove_vec, word_ids, char_ids, q_mask, enc, ws))
         return QueryEncoding(enc, q_mask, Lc)
 
-    def pairs_workspace_floats(self, B, T, Lq):
-        """Floats a localize_pairs call of this shape needs (the localize plan without the query branch's scratch)."""
-        self._need_query_encoding()
-        n = C.c_int64()
-        with torch.cuda.device(self.device):
-            self._call(self.lib.vsl_pairs_workspace_floats(self.h, B, T, Lq, C.byref(n)))
-        return int(n.value)
-
-    def _pair_index(self, index, n, name, what):
-        """an index of localize_pairs: a device tensor is trusted (no synchronising read), anything else range-checked and uploaded as int32"""
-        if isinstance(index, torch.Tensor) and index.is_cuda:
-            return index.to(torch.int32).contiguous()
-        host = torch.as_tensor(index).to(torch.int64).reshape(-1)
-        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n):
-            raise ValueError('localize_pairs: %s out of range: values in [%d, %d], the encoding holds %d %s' % (name, int(host.min()), int(host.max()), n, what))
-        return host.to(torch.int32).to(self.device)
+    def _pairs(self, who, p, flat, venc, qenc, video_index, query_index):
+        """What localize_pairs and highlight_pairs share: the checks of the two resident encodings and of the pairs' indices (host values are
+        range-checked, device tensors trusted), and the vsl_pairs_io `p` up to its outputs and its workspace.  -> (vidx, qidx), B = vidx.numel()."""
+        if not isinstance(venc, VideoEncoding):
+            raise TypeError('%s: venc must be the VideoEncoding that encode_video returned' % who)
+        if not isinstance(qenc, QueryEncoding):
+            raise TypeError('%s: qenc must be the QueryEncoding that encode_query returned' % who)
+        N, T, Q, Lq = venc.N, venc.T, qenc.Q, qenc.Lq
+        vidx = self._index(who, video_index, N, 'video_index', 'the encoding holds %d videos')
+        qidx = self._index(who, query_index, Q, 'query_index', 'the encoding holds %d queries')
+        B = int(vidx.numel())
+        if B < 1:
+            raise ValueError('%s: no pairs' % who)
+        _chk(vidx, torch.int32, (B,), 'video_index')
+        _chk(qidx, torch.int32, (B,), 'query_index')
+        _chk(flat, torch.float32, (self.param_floats,), 'params')
+        _chk(venc.encoding, torch.float32, (N, T, 128), 'video encoding')
+        _chk(venc.v_mask, torch.float32, (N, T), 'v_mask')
+        _chk(qenc.encoding, torch.float32, (Q, Lq, 128), 'query encoding')
+        _chk(qenc.q_mask, torch.float32, (Q, Lq), 'q_mask')
+        p.B, p.T, p.Lq, p.N, p.Q = B, T, Lq, N, Q
+        p.params = _ptr(flat)
+        p.video_encoding, p.v_mask, p.query_encoding, p.q_mask = _ptr(venc.encoding), _ptr(venc.v_mask), _ptr(qenc.encoding), _ptr(qenc.q_mask)
+        p.video_index, p.query_index = _ptr(vidx), _ptr(qidx)
+        return vidx, qidx
 
     def localize_pairs(self, flat, venc, qenc, video_index, query_index):
         """localize() with no query branch: pair b is query query_index[b] of the resident QueryEncoding `qenc` in video video_index[b] of the resident
@@ -811,42 +534,16 @@ class Engine:
         char_ids[query_index], q_mask[query_index] -- bit for bit where the query encoding does not depend on the query's position in its batch
         (include/vslnet_hip.h).  Indices as in localize(): host values are range-checked, device tensors trusted.
         `flat` must hold the parameter values both encodings were computed with (VSLNet.localize_pairs checks that through the handles' epochs)."""
-        self._need_query_encoding()
-        if not isinstance(venc, VideoEncoding):
-            raise TypeError('localize_pairs: venc must be the VideoEncoding that encode_video returned')
-        if not isinstance(qenc, QueryEncoding):
-            raise TypeError('localize_pairs: qenc must be the QueryEncoding that encode_query returned')
-        N, T, Q, Lq = venc.N, venc.T, qenc.Q, qenc.Lq
-        vidx = self._pair_index(video_index, N, 'video_index', 'videos')
-        qidx = self._pair_index(query_index, Q, 'query_index', 'queries')
-        B = int(vidx.numel())
-        if B < 1:
-            raise ValueError('localize_pairs: no pairs')
-        _chk(vidx, torch.int32, (B,), 'video_index')
-        _chk(qidx, torch.int32, (B,), 'query_index')
-        _chk(flat, torch.float32, (self.param_floats,), 'params')
-        _chk(venc.encoding, torch.float32, (N, T, 128), 'video encoding')
-        _chk(venc.v_mask, torch.float32, (N, T), 'v_mask')
-        _chk(qenc.encoding, torch.float32, (Q, Lq, 128), 'query encoding')
-        _chk(qenc.q_mask, torch.float32, (Q, Lq), 'q_mask')
-        self._flush_loss()
-        ws = self._grow_ws(self.pairs_workspace_floats(B, T, Lq))
-        out = torch.empty(3, B, T, dtype=torch.float32, device=self.device)
+        self._need('query_encoding')
         io = vsl_pairs_io()
-        io.B, io.T, io.Lq, io.N, io.Q = B, T, Lq, N, Q
-        io.params = _ptr(flat)
-        io.video_encoding, io.v_mask, io.query_encoding, io.q_mask = _ptr(venc.encoding), _ptr(venc.v_mask), _ptr(qenc.encoding), _ptr(qenc.q_mask)
-        io.video_index, io.query_index = _ptr(vidx), _ptr(qidx)
+        vidx, qidx = self._pairs('localize_pairs', io, flat, venc, qenc, video_index, query_index)
+        self._flush_loss()
+        ws = self._grow_ws(self.pairs_workspace_floats(io.B, io.T, io.Lq))
+        out = self._out3(io.B, io.T)
         io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
         io.workspace = _ptr(ws)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_localize_pairs(self.h, C.byref(io), stream))
-        self._no_saves((flat, venc, qenc, vidx, qidx, out, ws))
+        self._eval_call(self.lib.vsl_localize_pairs, io, (flat, venc, qenc, vidx, qidx, out, ws))
         return out[0], out[1], out[2]
-
-    def _need_video_ranking(self):
-        if not self.has_video_ranking:
-            raise VslError('the loaded library cannot rank videos (vsl_highlight_pairs / vsl_select_topm are missing)')
 
     def highlight_pairs(self, flat, venc, qenc, video_index, query_index, relevance='max', out=None, ld=0, h_score=None):
         """localize_pairs() that stops behind the highlight layer, plus one relevance per pair (include/vslnet_hip.h, vsl_highlight_pairs; the written
@@ -854,29 +551,16 @@ class Engine:
         -> `out`.  ld == 0: out is (B,) (allocated when None).  ld >= venc.N: out is a caller-owned (Q, ld) fp32 matrix and pair b goes to
         out[query_index[b], video_index[b]] -- a relevance matrix filled chunk by chunk.  `h_score`: an optional (B, T) buffer that receives the
         scores, bit for bit those of localize_pairs.  Indices as in localize_pairs: host values are range-checked, device tensors trusted."""
-        self._need_video_ranking()
-        self._need_query_encoding()
+        self._need('video_ranking')
+        self._need('query_encoding')
         if relevance not in RELEVANCE:
             raise ValueError("highlight_pairs: relevance must be 'max' or 'mean', got %r" % (relevance,))
-        if not isinstance(venc, VideoEncoding):
-            raise TypeError('highlight_pairs: venc must be the VideoEncoding that encode_video returned')
-        if not isinstance(qenc, QueryEncoding):
-            raise TypeError('highlight_pairs: qenc must be the QueryEncoding that encode_query returned')
-        N, T, Q, Lq = venc.N, venc.T, qenc.Q, qenc.Lq
-        vidx = self._pair_index(video_index, N, 'video_index', 'videos')
-        qidx = self._pair_index(query_index, Q, 'query_index', 'queries')
-        B, ld = int(vidx.numel()), int(ld)
-        if B < 1:
-            raise ValueError('highlight_pairs: no pairs')
+        io = vsl_highlight_io()
+        p = io.pairs
+        vidx, qidx = self._pairs('highlight_pairs', p, flat, venc, qenc, video_index, query_index)
+        B, T, ld = p.B, p.T, int(ld)
         if not 0 <= ld < 2 ** 31:
             raise ValueError('highlight_pairs: ld=%d is not a non-negative C int' % ld)
-        _chk(vidx, torch.int32, (B,), 'video_index')
-        _chk(qidx, torch.int32, (B,), 'query_index')
-        _chk(flat, torch.float32, (self.param_floats,), 'params')
-        _chk(venc.encoding, torch.float32, (N, T, 128), 'video encoding')
-        _chk(venc.v_mask, torch.float32, (N, T), 'v_mask')
-        _chk(qenc.encoding, torch.float32, (Q, Lq, 128), 'query encoding')
-        _chk(qenc.q_mask, torch.float32, (Q, Lq), 'q_mask')
         if ld == 0:
             if out is None:
                 out = torch.empty(B, dtype=torch.float32, device=self.device)
@@ -884,22 +568,14 @@ class Engine:
         else:
             if out is None:
                 raise ValueError('highlight_pairs: ld > 0 writes into a (Q, ld) matrix: pass it as out')
-            _chk(out, torch.float32, (Q, ld), 'out')       # (ld < N: the library refuses it by name)
+            _chk(out, torch.float32, (p.Q, ld), 'out')     # (ld < N: the library refuses it by name)
         if h_score is not None:
             _chk(h_score, torch.float32, (B, T), 'h_score')
         self._flush_loss()
-        ws = self._grow_ws(self.pairs_workspace_floats(B, T, Lq))
-        io = vsl_highlight_io()
-        p = io.pairs
-        p.B, p.T, p.Lq, p.N, p.Q = B, T, Lq, N, Q
-        p.params = _ptr(flat)
-        p.video_encoding, p.v_mask, p.query_encoding, p.q_mask = _ptr(venc.encoding), _ptr(venc.v_mask), _ptr(qenc.encoding), _ptr(qenc.q_mask)
-        p.video_index, p.query_index = _ptr(vidx), _ptr(qidx)
+        ws = self._grow_ws(self.pairs_workspace_floats(B, T, p.Lq))
         p.h_score, p.workspace = _ptr(h_score), _ptr(ws)
         io.relevance, io.ld, io.out = RELEVANCE[relevance], ld, _ptr(out)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_highlight_pairs(self.h, C.byref(io), stream))
-        self._no_saves((flat, venc, qenc, vidx, qidx, out, h_score, ws))
+        self._eval_call(self.lib.vsl_highlight_pairs, io, (flat, venc, qenc, vidx, qidx, out, h_score, ws))
         return out
 
     def select_topm(self, key, M):
@@ -907,10 +583,9 @@ class Engine:
         vslnet_amd.spans.select_topm_reference) -> VideoRanks(video (G, M) int32, relevance (G, M) fp32, count (G,) int32 = min(M, N)): key descending,
         ties by the smaller index, -0.0 as +0.0.  `key`: (G, N) fp32 on the device, rows contiguous, any row stride >= N (a column slice of a wider
         matrix works).  1 <= M <= 1024."""
-        self._need_video_ranking()
+        self._need('video_ranking')
         M = int(M)
-        if not -2 ** 31 <= M < 2 ** 31:
-            raise ValueError('select_topm: M=%d is not a C int' % M)
+        _c_int('select_topm', M=M)
         if key.dim() != 2 or key.dtype != torch.float32 or not key.is_cuda or (key.shape[1] > 1 and key.stride(1) != 1):
             raise ValueError('select_topm: key must be a (G, N) cuda float32 tensor with contiguous rows, got %s %s' % (key.dtype, tuple(key.shape)))
         G, N = key.shape
@@ -920,8 +595,7 @@ class Engine:
         val = torch.empty(G, n, dtype=torch.float32, device=self.device)
         count = torch.empty(G, dtype=torch.int32, device=self.device)
         io = vsl_select_io(G, N, ld, M, key.data_ptr(), index.data_ptr(), val.data_ptr(), count.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_select_topm(self.h, C.byref(io), stream))
+        self._call(self.lib.vsl_select_topm(self.h, C.byref(io), self._stream()))
         return VideoRanks(index, val, count)
 
     def localize(self, flat, pad_vec, glove_vec, enc, video_index, word_ids, char_ids, q_mask):
@@ -931,35 +605,22 @@ class Engine:
         `video_index` as a list / numpy array / CPU tensor is range-checked here and uploaded as int32; a DEVICE tensor (int32 or int64) is
         trusted -- no synchronising read -- and an index outside [0, enc.N) then reads outside the encoding.
         `flat` must hold the parameter values `enc` was computed with (VSLNet.localize checks that through the handle's epoch)."""
-        self._need_shared_video()
+        self._need('shared_video')
         if not isinstance(enc, VideoEncoding):
             raise TypeError('localize: enc must be the VideoEncoding that encode_video returned')
         N, T = enc.N, enc.T
         B, Lq, Lc = char_ids.shape
-        if isinstance(video_index, torch.Tensor) and video_index.is_cuda:
-            vidx = video_index.to(torch.int32).contiguous()
-        else:
-            host = torch.as_tensor(video_index).to(torch.int64).reshape(-1)
-            if host.numel() and (int(host.min()) < 0 or int(host.max()) >= N):
-                raise ValueError('localize: video_index out of range: values in [%d, %d], the encoding holds %d videos' % (int(host.min()), int(host.max()), N))
-            vidx = host.to(torch.int32).to(self.device)
+        vidx = self._index('localize', video_index, N, 'video_index', 'the encoding holds %d videos')
         if B < 1:
             raise ValueError('localize: empty query batch')
         _chk(vidx, torch.int32, (B,), 'video_index')
         _chk(flat, torch.float32, (self.param_floats,), 'params')
         _chk(enc.encoding, torch.float32, (N, T, 128), 'encoding')
         _chk(enc.v_mask, torch.float32, (N, T), 'v_mask')
-        _chk(word_ids, torch.int64, (B, Lq), 'word_ids')
-        _chk(char_ids, torch.int64, (B, Lq, Lc), 'char_ids')
-        _chk(q_mask, torch.float32, (B, Lq), 'q_mask')
-        if self.cfg.word_table:
-            pad_vec = glove_vec = None
-        else:
-            _chk(pad_vec, torch.float32, (1, self.cfg.word_dim), 'pad_vec')
-            _chk(glove_vec, torch.float32, (self.cfg.word_size - 2, self.cfg.word_dim), 'glove_vec')
+        pad_vec, glove_vec = self._check_query(B, Lq, Lc, word_ids, char_ids, q_mask, pad_vec, glove_vec)
         self._flush_loss()
         ws = self._grow_ws(self.localize_workspace_floats(B, T, Lq, Lc))
-        out = torch.empty(3, B, T, dtype=torch.float32, device=self.device)
+        out = self._out3(B, T)
         io = vsl_localize_io()
         io.B, io.T, io.Lq, io.Lc, io.N = B, T, Lq, Lc, N
         io.params, io.pad_vec, io.glove_vec = _ptr(flat), _ptr(pad_vec), _ptr(glove_vec)
@@ -967,9 +628,7 @@ class Engine:
         io.video_encoding, io.v_mask, io.video_index = _ptr(enc.encoding), _ptr(enc.v_mask), _ptr(vidx)
         io.h_score, io.start_logits, io.end_logits = _ptr(out[0]), _ptr(out[1]), _ptr(out[2])
         io.workspace = _ptr(ws)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_localize(self.h, C.byref(io), stream))
-        self._no_saves((flat, pad_vec, glove_vec, enc, vidx, word_ids, char_ids, q_mask, out, ws))
+        self._eval_call(self.lib.vsl_localize, io, (flat, pad_vec, glove_vec, enc, vidx, word_ids, char_ids, q_mask, out, ws))
         return out[0], out[1], out[2]
 
     def loss(self, start_labels, end_labels, h_labels, w_loc=1.0, w_highlight=5.0, inv_batch=None, mask_sum=0.0,
@@ -982,21 +641,19 @@ class Engine:
         in between (another forward / loss / a backward on other seeds) issues the pending loss first."""
         io = self._last
         if scores is not None:
-            B, T = scores.shape
-            for t, nm in ((scores, 'scores'), (start_logits, 'start_logits'), (end_logits, 'end_logits'), (v_mask, 'mask')):
-                _chk(t, torch.float32, (B, T), nm)
+            B, T, ptrs = self._check_scores(scores, start_logits, end_logits, v_mask)
             io2 = vsl_io()
             C.memmove(C.byref(io2), C.byref(io), C.sizeof(vsl_io))
             if (B, T) != (io.B, io.T):
                 raise ValueError('loss inputs (%d, %d) do not match the last forward (%d, %d)' % (B, T, io.B, io.T))
-            io2.h_score, io2.start_logits, io2.end_logits, io2.v_mask = _ptr(scores), _ptr(start_logits), _ptr(end_logits), _ptr(v_mask)
+            io2.h_score, io2.start_logits, io2.end_logits, io2.v_mask = ptrs
             io = io2
         B, T = io.B, io.T
         _chk(start_labels, torch.int64, (B,), 'start_labels')
         _chk(end_labels, torch.int64, (B,), 'end_labels')
         _chk(h_labels, torch.int64, (B, T), 'h_labels')
         losses = torch.empty(4, dtype=torch.float32, device=self.device)
-        d = torch.empty(3, B, T, dtype=torch.float32, device=self.device) if want_grads else None
+        d = self._out3(B, T) if want_grads else None
         l = vsl_loss_io()
         l.start_labels, l.end_labels, l.h_labels = _ptr(start_labels), _ptr(end_labels), _ptr(h_labels)
         l.w_loc, l.w_highlight = float(w_loc), float(w_highlight)
@@ -1009,8 +666,7 @@ class Engine:
         if lazy and want_grads and scores is None and self.has_fused_io:
             self._pending_loss = (l, io, (start_labels, end_labels, h_labels, losses, d))
             return losses, d[0], d[1], d[2]
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_loss(self.h, C.byref(io), C.byref(l), stream))
+        self._call(self.lib.vsl_loss(self.h, C.byref(io), C.byref(l), self._stream()))
         return (losses,) + ((d[0], d[1], d[2]) if want_grads else (None, None, None))
 
     def group_loss(self, start_labels, end_labels, h_labels, group_start, positive, w_loc=1.0, w_highlight=5.0, w_rank=1.0, temperature=0.1,
@@ -1022,15 +678,11 @@ class Engine:
         precondition.  `start_labels` / `end_labels` may be None with w_loc == 0 and `h_labels` with w_highlight == 0.  inv_pos and inv_groups
         default to 1 / G.  -> (losses[5]: loc, highlight, rank, total, mask sum used; hits: int32 scalar tensor; relevance (B,); d_h, d_sl, d_el --
         None without want_grads).  Never lazy: the call is two launches of its own, and the seeds go to backward() like any others."""
-        if not self.has_group_loss:
-            raise VslError('the loaded library has no video ranking loss (vsl_group_loss / vsl_group_loss_scratch_floats are missing)')
-        if relevance not in ('max', 'mean'):
+        self._need('group_loss')
+        if relevance not in RELEVANCE:
             raise ValueError("group_loss: relevance must be 'max' or 'mean', got %r" % (relevance,))
         if scores is not None:
-            B, T = scores.shape
-            for t, nm in ((scores, 'scores'), (start_logits, 'start_logits'), (end_logits, 'end_logits'), (v_mask, 'mask')):
-                _chk(t, torch.float32, (B, T), nm)
-            ptrs = (_ptr(scores), _ptr(start_logits), _ptr(end_logits), _ptr(v_mask))
+            B, T, ptrs = self._check_scores(scores, start_logits, end_logits, v_mask)
         else:
             io = self._last
             if io is None:
@@ -1057,7 +709,7 @@ class Engine:
         losses = torch.empty(5, dtype=torch.float32, device=self.device)
         hits = torch.empty((), dtype=torch.int32, device=self.device)
         rel = torch.empty(B, dtype=torch.float32, device=self.device)
-        d = torch.empty(3, B, T, dtype=torch.float32, device=self.device) if want_grads else None
+        d = self._out3(B, T) if want_grads else None
         l = vsl_group_loss_io()
         l.B, l.T, l.G = B, T, G
         l.h_score, l.start_logits, l.end_logits, l.v_mask = ptrs
@@ -1068,21 +720,19 @@ class Engine:
         l.inv_groups = float(1.0 / max(G, 1) if inv_groups is None else inv_groups)
         l.mask_sum = float(mask_sum)
         l.inv_temperature = float(1.0 / temperature) if temperature > 0 else 0.0
-        l.relevance = int(relevance == 'mean')
+        l.relevance = RELEVANCE[relevance]
         l.losses, l.hits, l.pair_relevance, l.scratch = _ptr(losses), _ptr(hits), _ptr(rel), _ptr(scratch)
         if want_grads:
             l.d_h_score, l.d_start_logits, l.d_end_logits = _ptr(d[0]), _ptr(d[1]), _ptr(d[2])
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_group_loss(self.h, C.byref(l), stream))
+        self._call(self.lib.vsl_group_loss(self.h, C.byref(l), self._stream()))
         return (losses, hits, rel) + ((d[0], d[1], d[2]) if want_grads else (None, None, None))
 
     def _flush_loss(self):
         """Issue a pending lazy loss() as its own launch (the caller did not go on to backward() on its seeds)."""
-        pend, self._pending_loss = getattr(self, '_pending_loss', None), None
+        pend, self._pending_loss = self._pending_loss, None
         if pend is not None:
             l, io, _ = pend
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._call(self.lib.vsl_loss(self.h, C.byref(io), C.byref(l), stream))
+            self._call(self.lib.vsl_loss(self.h, C.byref(io), C.byref(l), self._stream()))
 
     def early_grad_offset(self):
         """First float offset of the block of `grads` that is final when `backward(..., early_event=)` fires its event."""
@@ -1098,13 +748,13 @@ class Engine:
         (grads = grads + g).  One optimizer step over K micro-batches is the first one with accumulate=False (it overwrites: nothing is zeroed), the
         others with accumulate=True, the last of them with `fused_step`: clip and AdamW then act on the accumulated bucket and its norm.  The
         micro-batches take the global loss normalisers and their first row as forward()'s `sample_offset`, like data-parallel shards."""
-        if accumulate and not self.has_grad_accumulation:
-            raise VslError('backward(accumulate=True): the loaded library has no gradient accumulation (vsl_backward_accumulate is missing)')
+        if accumulate:
+            self._need('grad_accumulation')
         io = self._last
         if io is not None and io.inference:
             raise VslError('backward(): the last forward was an inference forward, which saved nothing; run forward(inference=False) on the batch')
         B, T = io.B, io.T
-        pend = getattr(self, '_pending_loss', None)
+        pend = self._pending_loss
         fused_loss = None
         if pend is not None:
             d = pend[2][4]
@@ -1142,7 +792,7 @@ class Engine:
             gn = fused_step.get('grad_norm_out')
             fs.grad_norm_out = _ptr(gn) if gn is not None else None
             io.fused_step = C.cast(C.pointer(fs), C.c_void_p)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self._stream()
         try:
             if accumulate:
                 self._call(self.lib.vsl_backward_accumulate(self.h, C.byref(io), C.byref(self._last_shared) if self._last_shared is not None else None, stream))
@@ -1164,8 +814,7 @@ class Engine:
         Raises VslError when no backward has run since the last forward, when that forward saved nothing (inference, encode_video, localize), and
         when the last backward() had `fused_step` (the weight the product needs has been updated: call backward() without it, input_grads(), then
         adamw_step(norm_from_backward=True))."""
-        if not self.has_input_grads:
-            raise VslError('the loaded library has no input gradients (vsl_input_grads is missing)')
+        self._need('input_grads')
         io = self._last
         if io is None:
             raise VslError('input_grads(): no forward has run on this engine')
@@ -1176,8 +825,7 @@ class Engine:
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
         _chk(out, torch.float32, shape, 'out')
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_input_grads(self.h, C.byref(io), C.byref(sh) if sh is not None else None, _ptr(out), stream))
+        self._call(self.lib.vsl_input_grads(self.h, C.byref(io), C.byref(sh) if sh is not None else None, _ptr(out), self._stream()))
         return out
 
     def profile_select(self, kernel):
@@ -1225,26 +873,23 @@ class Engine:
             _chk(t, torch.float32, (n,), nm)
         hp = vsl_adamw(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(clip_norm or 0.0), int(step),
                        int(bool(hf_order)), int(bool(norm_from_backward)))
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._call(self.lib.vsl_adamw_step(self.h, _ptr(flat), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), C.byref(hp),
-                                           _ptr(grad_norm_out) if grad_norm_out is not None else None, stream))
+                                           _ptr(grad_norm_out) if grad_norm_out is not None else None, self._stream()))
 
     def extract_index(self, start_logits, end_logits):
         B, T = start_logits.shape
         _chk(start_logits, torch.float32, (B, T), 'start_logits')
         _chk(end_logits, torch.float32, (B, T), 'end_logits')
         idx = torch.empty(2, B, dtype=torch.int64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._call(self.lib.vsl_extract_index(self.h, _ptr(start_logits), _ptr(end_logits), B, T, _ptr(idx[0]),
-                                              _ptr(idx[1]), stream))
+                                              _ptr(idx[1]), self._stream()))
         return idx[0], idx[1]
 
     def extract_topk(self, start_logits, end_logits, k, nms_iou=1.0, max_span=0, lengths=None, v_mask=None, want_prob=True):
         """The k best spans per sample by greedy selection with temporal NMS (include/vslnet_hip.h, vsl_extract_topk; the written specification:
         vslnet_amd.spans.topk_spans_reference) -> TopkSpans.  Candidates are the spans inside the sample's valid length: `lengths` (B,) integers, or
         `v_mask` (B, T), a prefix mask (convert_length_to_mask) whose row sums are the lengths; neither: T.  nms_iou = 1 is plain top-k."""
-        if not self.has_topk:
-            raise VslError('the loaded library has no top-k span extraction (vsl_extract_topk is missing)')
+        self._need('topk')
         if lengths is not None and v_mask is not None:
             raise ValueError('extract_topk: give lengths or v_mask, not both')
         B, T = start_logits.shape
@@ -1257,17 +902,14 @@ class Engine:
             lengths = torch.as_tensor(lengths).to(device=self.device, dtype=torch.int32).contiguous()
             _chk(lengths, torch.int32, (B,), 'lengths')
         k, max_span = int(k), int(max_span)
-        for name, v in (('k', k), ('max_span', max_span)):   # (ctypes would wrap them: max_span = 2 ** 32 must not arrive as 0 = unlimited; the library checks the ranges)
-            if not -2 ** 31 <= v < 2 ** 31:
-                raise ValueError('extract_topk: %s=%d is not a C int' % (name, v))
+        _c_int('extract_topk', k=k, max_span=max_span)
         idx = torch.empty(2, B, max(k, 0), dtype=torch.int64, device=self.device)
         val = torch.empty(2 if want_prob else 1, B, max(k, 0), dtype=torch.float32, device=self.device)
         count = torch.empty(B, dtype=torch.int32, device=self.device)
         io = vsl_topk_io(start_logits.data_ptr(), end_logits.data_ptr(), lengths.data_ptr() if lengths is not None else None, B, T, k,
                          float(nms_iou), max_span, idx[0].data_ptr(), idx[1].data_ptr(), val[0].data_ptr(),
                          val[1].data_ptr() if want_prob else None, count.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_extract_topk(self.h, C.byref(io), stream))
+        self._call(self.lib.vsl_extract_topk(self.h, C.byref(io), self._stream()))
         return TopkSpans(idx[0], idx[1], val[0], val[1] if want_prob else None, count)
 
     def merge_topk(self, spans, group_index, G, k_out, tag=None):
@@ -1276,20 +918,8 @@ class Engine:
         `prob`); `group_index` (B,) int32 on the device: the group (query) of list b, a value outside [0, G) drops the list; `tag`: None (list b is tagged
         b), (B,) int32 (one tag per list: its video), or (B, k) int32 (one per slot: the `tag` of an earlier merge_topk whose result is merged again --
         pass TopkSpans(m.start, m.end, m.score, m.prob, m.count) of that CorpusMoments m).  Order: prob descending, then tag, list, slot ascending."""
-        if not self.has_merge_topk:
-            raise VslError('the loaded library has no cross-list merge (vsl_merge_topk is missing)')
-        if spans.prob is None:
-            raise ValueError('merge_topk: the spans carry no prob to rank by (extract_topk(want_prob=True))')
-        B, K = spans.start.shape
-        for name, v in (('G', G), ('k_out', k_out)):         # (ctypes would wrap them; the library checks the ranges)
-            if not -2 ** 31 <= v < 2 ** 31:
-                raise ValueError('merge_topk: %s=%d is not a C int' % (name, v))
-        _chk(spans.start, torch.int64, (B, K), 'spans.start')
-        _chk(spans.end, torch.int64, (B, K), 'spans.end')
-        _chk(spans.score, torch.float32, (B, K), 'spans.score')
-        _chk(spans.prob, torch.float32, (B, K), 'spans.prob')
-        _chk(spans.count, torch.int32, (B,), 'spans.count')
-        _chk(group_index, torch.int32, (B,), 'group_index')
+        self._need('merge_topk')
+        B, K, G, k_out = self._check_spans('merge_topk', spans, group_index, G, k_out)
         per_slot = tag is not None and tag.dim() == 2
         if tag is not None:
             _chk(tag, torch.int32, (B, K) if per_slot else (B,), 'tag')
@@ -1302,8 +932,7 @@ class Engine:
                           spans.count.data_ptr(), group_index.data_ptr(), tag.data_ptr() if tag is not None else None, int(per_slot),
                           i32[0].data_ptr(), i32[1].data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(), f32[0].data_ptr(), f32[1].data_ptr(),
                           count.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._call(self.lib.vsl_merge_topk(self.h, C.byref(io), stream))
+        self._call(self.lib.vsl_merge_topk(self.h, C.byref(io), self._stream()))
         return CorpusMoments(i32[0], i32[1], i64[0], i64[1], f32[0], f32[1], count)
 
 
